@@ -27,6 +27,13 @@ configs   (N = 1) = BASELINE.json configs[2] (8192^2 YCbCr 4:2:0) and configs[3]
             with PSNR), timed in the same run with their own algorithmic bytes.
 cpu_baseline (N = 1) = the faithful Python/NumPy per-block loop restatement of the reference
             (oracle/ref_loop.py, 1 core) on three planes; the C oracle's rate is given too.
+
+A plain run does only what `value` needs: set-up, spin-up and warm-up, the K timed steps, the line.
+--full adds everything else: the exact-tier census launch, the check against the oracle
+(verified_vs_oracle), the gather legs (N > 1), the configs legs and cpu_baseline (N = 1); the
+--no-* options leave out single parts of it.  --dump-outputs DIR writes a fixed, seeded sample of
+the last timed step's int16 stream (whole block rows, as float32) to DIR/coefficients.npy, with the
+sampled row numbers in DIR/block_rows.npy (per rank, suffixed _rank<r>, at N > 1).
 """
 import ctypes
 import argparse
@@ -73,10 +80,15 @@ def parse_args():
     ap.add_argument("--dry-run-stall", type=float, default=0.0, help="with --dry-run: seconds every rank stalls inside the watchdog-guarded region")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work at all: launcher + control plane + shard plan only (CPU tests)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[2]/[3] legs at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: exact-tier census, verification against the "
+                         "oracle, the gather legs (N > 1), the configs legs and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of what the last step computed to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the checks against the oracle")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the gather legs at N > 1")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the configs legs at N = 1")
     return ap.parse_args()
 
 
@@ -86,6 +98,32 @@ def forward_source_hash():
         with open(os.path.join(REPO, rel), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
+
+
+DUMP_SEED = 0
+DUMP_BYTES = 32 << 20          # float32 bytes of the dumped sample (the whole int16 stream is 32 GiB at N = 1)
+
+
+def dump_outputs(dirname, jpegx, out_ptr, lo, hi, size, total_planes, rank, world):
+    """Write what the last timed step left in the rank's output span: a fixed, seeded sample of whole block rows of
+    the batch's int16 zigzag stream (row r = plane r // (size / 8), block row r % (size / 8); each row is size / 8
+    blocks x 64 coefficients), as float32, plus the sampled global row numbers as float64.  The sample depends only
+    on the batch shape, so two builds compare row for row; at N > 1 each rank writes the rows of its own planes."""
+    L = jpegx.lib()
+    rows_per_plane = blocks_per_row = size // 8          # square planes
+    row_bytes = blocks_per_row * 64 * 2
+    total_rows = total_planes * rows_per_plane
+    n = min(total_rows, max(1, DUMP_BYTES // (row_bytes * 2)))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(total_rows, n, replace=False))
+    rows = rows[(rows >= lo * rows_per_plane) & (rows < hi * rows_per_plane)]
+    got = np.empty((rows.size, blocks_per_row, 64), np.int16)
+    for i, r in enumerate(rows):
+        jpegx.check(L.jpegx_memcpy_d2h(got[i].ctypes.data, out_ptr + int(r - lo * rows_per_plane) * row_bytes, row_bytes, None), "d2h")
+    jpegx.check(L.jpegx_device_synchronize(), "sync")
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(dirname, "coefficients%s.npy" % suffix), got.astype(np.float32))
+    np.save(os.path.join(dirname, "block_rows%s.npy" % suffix), rows.astype(np.float64))
 
 
 def cpu_baseline(size, kind, sample_planes=3):
@@ -467,7 +505,7 @@ def run(args, rank, local_rank, world, ctl, emit):
     device = 0 if (args.share_device or world == 1) else local_rank
     jpegx.check(L.jpegx_set_device(device), "jpegx_set_device")
 
-    gathering = world > 1 and not args.no_gather
+    gathering = world > 1 and args.full and not args.no_gather
     loopback = bool(args.share_device)
     # root keeps the whole batch's stream (its own planes are written in place); loop-back rehearsal: a
     # second buffer of the rank's own size stands in for the root's
@@ -523,23 +561,29 @@ def run(args, rank, local_rank, world, ctl, emit):
     barrier()
     t_max = ctl.allreduce_max(t_local)
     value = total_blocks_per_step * args.steps / t_max / 1e6
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, jpegx, out_ptr, lo, hi, size, total_planes, rank, world)
+        ctl.barrier()
 
+    # everything below the headline (census, verification, gather, configs, cpu_baseline) runs with --full only
     # --- exact-tier census (untimed): how many blocks took the float64 path -----------------------
-    cnt = jpegx.DeviceBuffer(16)
-    jpegx.check(L.jpegx_memset(cnt.ptr, 0, 16, stream), "memset")
-    jpegx.check(L.jpegx_set_debug_counters(cnt.ptr), "counters")
-    # on the first 16 planes only: the counters are two global atomics per wave, which over the whole batch
-    # (4.2 M waves on two addresses) would make this one instrumented launch six times longer than a step
-    cplanes = min(planes, 16)
-    jpegx.forward_fused_device(in_ptr, size * cplanes, W, out_ptr, args.mode, args.param, flags, stream=stream)
-    jpegx.check(L.jpegx_device_synchronize(), "sync")
-    jpegx.check(L.jpegx_set_debug_counters(None), "counters")
-    census = cnt.download((2,), np.uint64)
-    exact_frac = float(census[0]) / max(1.0, float(census[1]))
+    exact_frac = None
+    if args.full:
+        cnt = jpegx.DeviceBuffer(16)
+        jpegx.check(L.jpegx_memset(cnt.ptr, 0, 16, stream), "memset")
+        jpegx.check(L.jpegx_set_debug_counters(cnt.ptr), "counters")
+        # on the first 16 planes only: the counters are two global atomics per wave, which over the whole batch
+        # (4.2 M waves on two addresses) would make this one instrumented launch six times longer than a step
+        cplanes = min(planes, 16)
+        jpegx.forward_fused_device(in_ptr, size * cplanes, W, out_ptr, args.mode, args.param, flags, stream=stream)
+        jpegx.check(L.jpegx_device_synchronize(), "sync")
+        jpegx.check(L.jpegx_set_debug_counters(None), "counters")
+        census = cnt.download((2,), np.uint64)
+        exact_frac = round(float(census[0]) / max(1.0, float(census[1])), 5)
 
     # --- verification against the oracle (untimed): slices of the rank's first and last plane ------
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         import oracle
         from jpegx import synth
         vh = min(size, 512)
@@ -584,14 +628,15 @@ def run(args, rank, local_rank, world, ctl, emit):
                      "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "k_forward_fused_strip<3,nt>", "kernel_ms": round(kernel_ms, 4),
                      "algorithmic_bytes_per_launch": BYTES_PER_BLOCK * blocks_per_step},
-        "exact_tier_block_fraction": round(exact_frac, 5),
+        "exact_tier_block_fraction": exact_frac,
         "verified_vs_oracle": verified,
         # what ran when (every launch of this process, in order): untimed clock spin-up, the W declared warm-up
-        # steps, the K timed steps (value and roofline come from these alone), one instrumented census launch on at
-        # most 16 planes, then host-side verification; the configs / cpu_baseline legs follow at N = 1
+        # steps, the K timed steps (value and roofline come from these alone); with --full one instrumented census
+        # launch on at most 16 planes, then host-side verification, and the configs / cpu_baseline legs at N = 1
         "launches": {"spinup_ms": args.spinup_ms, "spinup": spin_launches, "warmup": args.warmup, "timed": args.steps,
-                     "census": 1, "note": "spin-up launches are full steps, untimed and not part of `warmup`; "
-                                          "cpu_baseline is a single-core host loop during which the GPU idles"},
+                     "census": 1 if args.full else 0, "note": "spin-up launches are full steps, untimed and not part of `warmup`; "
+                                                             "cpu_baseline is a single-core host loop during which the GPU idles"},
+        "full": bool(args.full),
         "device": jpegx.device_name(device),
     }
     # --- the one exchange of the path: RCCL gather of the int16 stream to rank 0 -------------------
@@ -627,7 +672,7 @@ def run(args, rank, local_rank, world, ctl, emit):
             if gather is None:
                 result["gather"] = {"error": "gather legs returned nothing"}
             leave_after_failed_exchange(rank, emit, result)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_configs:
             # free the batch first: the legs below allocate their own planes
             b_in.free()

@@ -15,7 +15,7 @@ A)
     rocprofv3 --kernel-trace --stats --output-format csv -d $R/hostapi_kt -- python3 microbench/host_api.py > $R/host_api_under_trace.txt 2> $R/host_api_under_trace.err; echo "hostapi trace rc=$?"
     python3 microbench/host_api.py > $R/host_api.txt 2> $R/host_api.err; echo "hostapi rc=$?"
     python3 microbench/host_api.py --image > $R/host_api_image.txt 2> $R/host_api_image.err; echo "hostapi image rc=$?"
-    python3 bench.py > $R/bench_n1.json 2> $R/bench_n1.err; echo "bench rc=$?"; tail -c 400 $R/bench_n1.json
+    python3 bench.py --full > $R/bench_n1.json 2> $R/bench_n1.err; echo "bench rc=$?"; tail -c 400 $R/bench_n1.json
     ;;
 B)
     bash profiles/collect_pmc_r03.sh $R/pmc > $R/collect_pmc.log 2>&1; echo "pmc rc=$?"; ls $R/pmc | head -40
