@@ -790,8 +790,12 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
     if ((rc = ensure_streams(pool, true))) return rc;
     const size_t packed_pitch = (size_t)cols * nbands;
     if (interleave && (rc = pool->d_packed.ensure((size_t)rows * packed_pitch))) return rc;      // before anything is enqueued
-    // the result array is usually fresh memory: touch its pages on a helper thread while the bands are uploaded and decoded
-    const size_t out_span = interleave ? (size_t)rows * out_pitch : (size_t)nbands * rows * out_pitch;
+    // the result array is usually fresh memory: touch its pages on a helper thread while the bands are uploaded and decoded.
+    // The touch writes a zero into every page, so it only runs on a destination whose rows lie back to back: every byte
+    // of that is a sample the copies below overwrite.  The bytes between the rows of a wider out_pitch, and those behind
+    // the last row, are the caller's and stay as they are.
+    const size_t row_bytes = (size_t)cols * (interleave ? nbands : 1);
+    const size_t out_span = (size_t)out_pitch == row_bytes ? (size_t)rows * (interleave ? 1 : nbands) * row_bytes : 0;
     BackgroundTouch touch(h_out, out_span);
     auto drain = [&]() { (void)hipStreamSynchronize(pool->aux[0]); (void)hipStreamSynchronize(pool->aux[1]); };
     int level[MAX_BANDS] = {};                              // per band: planned segments, 256-byte segments, the whole-stream scheme

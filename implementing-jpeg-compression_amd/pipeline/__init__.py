@@ -318,6 +318,9 @@ class Jpeg:
         self.config = config
 
     def compress(self, image):
+        nbands = len(image.getbands())
+        if nbands != 3:                                      # the reference's `y, cb, cr = image.split()`
+            raise ValueError("%s to unpack (expected 3, got %d)" % ("too many values" if nbands > 3 else "not enough values", nbands))
         whole = _compress_pixels(image, self.config)         # the picture's pixels as ONE array, the bands made on the device
         if whole is not None:
             return whole

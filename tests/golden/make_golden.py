@@ -269,6 +269,40 @@ def main():
     ext[:, 32:40] = 255 * (np.arange(8)[:, None] < 4)
     ext[:, 40:48] = np.where(np.sign(np.outer(C[1], C[1])) > 0, 255, 0)
     run_case("extremes", ext)
+    road_cases()
+
+
+def road_cases():
+    """Shapes the cases above leave out (tests/codec_oracle.py ROAD_CASES): ragged bands that need both Padding (to a
+    multiple of block_size) and DCTPadding (pooled samples to a multiple of 8) at block sizes 2-16, a 1-row and a
+    1-column band, extreme content at block_size 4 and 2x2 means on exact .5."""
+    def noise(h, w, seed):
+        return synth.generate_plane("noise", h, w, seed=seed, dtype=np.int64)
+
+    def smooth(h, w, seed):
+        return synth.generate_plane("smooth", h, w, seed=seed, dtype=np.int64)
+
+    run_case("ragged44x70b3", noise(44, 70, 11), block_size=3)
+    run_case("ragged37x53b2", noise(37, 53, 12), block_size=2)
+    run_case("ragged23x41b5", smooth(23, 41, 13), block_size=5)
+    run_case("ragged9x130b4", noise(9, 130, 14), block_size=4)
+    run_case("ragged1x17b2", noise(1, 17, 15), block_size=2)
+    run_case("ragged29x1b3", noise(29, 1, 16), block_size=3)
+    run_case("ragged50x50b16", smooth(50, 50, 17), block_size=16)
+    run_case("ragged7x300b7", noise(7, 300, 18), block_size=7)
+    # block_size 4, three pooled blocks: constant 255, a checkerboard of 4x4 tiles (pooled 0/255: the largest AC)
+    # and a checkerboard of pixels (every pooled sample 127.5)
+    ext = np.full((32, 96), 255, dtype=np.int64)
+    ext[:, 32:64] = 255 * ((np.add.outer(np.arange(32) // 4, np.arange(32) // 4)) & 1)
+    ext[:, 64:96] = 255 * ((np.add.outer(np.arange(32), np.arange(32))) & 1)
+    run_case("extremes32x96b4", ext, block_size=4)
+    # block_size 2 with every complete 2x2 tile summing to 2 (mod 4): the means are exact .5 values
+    rng = np.random.default_rng(20261016)
+    ties = rng.integers(0, 254, (48, 42)).astype(np.int64)
+    tile = ties.reshape(24, 2, 21, 2)
+    tile[:, 0, :, 0] += (2 - tile.sum(axis=(1, 3))) % 4
+    assert np.all(ties.reshape(24, 2, 21, 2).sum(axis=(1, 3)) % 4 == 2)
+    run_case("halfties47x41b2", ties[:47, :41], block_size=2)
 
 
 if __name__ == "__main__":

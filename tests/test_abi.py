@@ -95,3 +95,18 @@ def test_product_never_imports_the_oracle():
                 text = open(os.path.join(root, f), errors="replace").read()
                 assert "import oracle" not in text and "from oracle" not in text, os.path.join(root, f)
                 assert "jpegx_oracle" not in text or f == "jpegx_math.h", os.path.join(root, f)
+
+
+def test_codec_oracle_never_imports_the_product():
+    """tests/codec_oracle.py is the independent end-to-end reference: it may use NumPy and oracle/ only."""
+    import ast
+    tree = ast.parse(open(os.path.join(REPO, "tests", "codec_oracle.py")).read())
+    imported = set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Import):
+            imported.update(a.name.split(".")[0] for a in node.names)
+        elif isinstance(node, ast.ImportFrom):
+            imported.add((node.module or "").split(".")[0] if node.level == 0 else "<relative>")
+        elif isinstance(node, ast.Call) and getattr(node.func, "id", None) == "__import__":
+            imported.add("<dynamic>")
+    assert imported <= {"math", "numpy", "oracle"}, imported

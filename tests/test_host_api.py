@@ -322,3 +322,17 @@ def test_gpu_mode_accepts_stock_quantiser_objects_only():
     assert m.gpu_mode() is None
     cfg = Configuration(width=8, height=8, block_size=1, quantization=m)
     assert not pipeline._accelerated(cfg)                          # everything then runs step by step on the host objects
+
+
+@pytest.mark.parametrize("mode,bands", [("L", 1), ("LA", 2), ("RGBA", 4), ("CMYK", 4)])
+def test_jpeg_compress_refuses_pictures_without_three_bands(mode, bands):
+    """CompressedData holds three bands: the reference raises ValueError at `y, cb, cr = image.split()` for any other
+    count, before anything is computed.  No road may write a container with 1, 2 or 4 bands instead."""
+    from PIL import Image
+    im = Image.fromarray(np.zeros((16, 16, bands), np.uint8)[..., 0] if bands == 1 else np.zeros((16, 16, bands), np.uint8),
+                         mode=mode)
+    assert len(im.getbands()) == bands
+    for q in (QuantizationMethod("qtable"), QuantizationMethod("divide", divisor=40)):
+        cfg = Configuration(width=16, height=16, block_size=1, quantization=q)
+        with pytest.raises(ValueError, match="to unpack"):
+            pipeline.Jpeg(cfg).compress(im)
