@@ -1,0 +1,392 @@
+// jpegx_batch.cpp -- the batch codec on DEVICE buffers (include/jpegx.h): a stack of equally shaped planes -> one coded
+// byte stream with a per-plane index, and back.  For every plane the bytes are those of the reference's compress_band
+// (pipeline/__init__.py:71-76 for transform 'DCT', dct_size 8: SubSampling, BasisChange, Quantization, ZigzagOrder,
+// RunLengthEncoding pipeline/run_length_encoding.py:47-64, RleBytestream pipeline/rle_byte_stream.py:48-59), and the way
+// back is its decompress_band (pipeline/__init__.py:79-88; pipeline/rle_byte_stream.py:61-88,
+// pipeline/run_length_encoding.py:66-97).
+//
+// Planes of equal shape stacked behind each other ARE one tall plane: the block order of [nplanes * H][W] is plane after
+// plane, so the forward kernels, the scan and the emitter run once over nplanes * (H/8) * (W/8) blocks; what a batch adds
+// is the plane index (k_plane_index, jpegx_entropy.hip) and, on the way back, the cut into groups of whole planes that
+// one decode call can take.  Nothing is allocated here except the whole-stream decoder's scratch (level 2 of the
+// ladder), which is sized from a count read back from the device and therefore cannot be the caller's.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <mutex>
+
+#include "../../include/jpegx.h"
+#include "jpegx_entropy_decode.h"
+
+extern "C" void jpegx_internal_set_error(const char *msg);
+extern "C" int jpegx_internal_forward_u8_sized(const uint8_t *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, unsigned flags,
+                                               int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, jpegx_stream_t stream);
+extern "C" int jpegx_internal_forward_f32_sized(const float *d_in, int H, int W, ptrdiff_t pitch, int mode, double param, unsigned flags,
+                                                int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, int *sized,
+                                                jpegx_stream_t stream);
+extern "C" void jpegx_internal_entropy_views(void *d_workspace, long long nblocks, unsigned **block_bytes, unsigned **wave_bytes, unsigned **half_info);
+extern "C" int jpegx_internal_entropy_sizes_half(const int16_t *d_zz, long long nblocks, void *d_workspace, jpegx_stream_t stream);
+extern "C" int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);
+extern "C" int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
+                                                  jpegx_stream_t stream);
+extern "C" int jpegx_internal_entropy_emit2_guarded(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, size_t out_cap,
+                                                    jpegx_stream_t stream);
+
+namespace {
+
+int fail(int code, const char *msg)
+{
+    jpegx_internal_set_error(msg);
+    return code;
+}
+
+#define B_TRY(expr)                                                                         \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) {                                                             \
+            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
+            char buf_[400];                                                                 \
+            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));    \
+            jpegx_internal_set_error(buf_);                                                 \
+            return JPEGX_E_HIP;                                                             \
+        }                                                                                   \
+    } while (0)
+
+constexpr unsigned long long SIZES_ONLY = ~0ull;       // the capacity noted by a compress without destination
+constexpr long long MAX_BLOCKS = 0x7FFFFFC0LL;
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// shape of a batch: false (message set) when it is not one
+int check_batch_shape(int nplanes, int H, int W, long long *nb)
+{
+    if (nplanes <= 0) return fail(JPEGX_E_INVALID, "batch: the plane count must be positive");
+    if (H <= 0 || W <= 0 || (H % 8) != 0 || (W % 8) != 0) return fail(JPEGX_E_INVALID, "batch: plane height and width must be positive multiples of 8");
+    *nb = (long long)(H / 8) * (W / 8);
+    if (*nb > MAX_BLOCKS / nplanes) return fail(JPEGX_E_INVALID, "batch: more than 2^31 - 64 blocks in one batch");
+    return JPEGX_OK;
+}
+
+// ---- compress: [int16 stream][entropy workspace][batch head + plane index], each rounded up to 256 bytes -------------
+struct CompressWs {
+    int16_t *zz;
+    void *ews;
+    void *index;         // 16 bytes of head (the capacity of the last emit step), then nplanes + 1 offsets
+    size_t bytes;
+};
+
+CompressWs carve_compress(void *ws, int nplanes, long long nblocks)
+{
+    unsigned char *p = static_cast<unsigned char *>(ws);
+    CompressWs c;
+    size_t o = 0;
+    c.zz = reinterpret_cast<int16_t *>(p + o); o += up256((size_t)nblocks * 128);
+    c.ews = p + o; o += up256(jpegx_entropy_workspace_bytes(nblocks));
+    c.index = p + o; o += up256(16 + ((size_t)nplanes + 1) * 8);
+    c.bytes = o;
+    return c;
+}
+
+int enqueue_index_and_emit(const CompressWs &c, int nplanes, long long nb, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream)
+{
+    int rc = jpegx_internal_entropy_plane_index(nplanes, nb, c.ews, c.index, d_out ? out_cap : (size_t)SIZES_ONLY, stream);
+    if (rc || !d_out) return rc;
+    return jpegx_internal_entropy_emit2_guarded(c.zz, nb * nplanes, c.ews, d_out, out_cap, stream);
+}
+
+// ---- decompress: groups of whole planes -----------------------------------------------------------------------------
+// One decode call takes a stream below 4 GiB; the segmented scheme's scratch is 8 bytes per stream byte at its second
+// level, and the int16 stream of a group has to sit somewhere.  So a group is a run of whole planes of at most
+// GROUP_BLOCKS blocks and GROUP_BYTES bytes (one plane where a single plane is more than that).
+constexpr long long GROUP_BLOCKS = 1ll << 20;          // 128 MiB of int16 stream
+constexpr size_t GROUP_BYTES = (size_t)64 << 20;
+
+struct GroupLimits {
+    int planes;          // planes per group at most
+    size_t bytes;        // bytes per group at most (a lone plane may reach it: 185 bytes per block is the format's worst case)
+};
+
+GroupLimits group_limits(int nplanes, long long nb)
+{
+    GroupLimits g;
+    long long k = GROUP_BLOCKS / nb;
+    if (k < 1) k = 1;
+    g.planes = k > nplanes ? nplanes : (int)k;
+    const unsigned long long worst = 185ull * (unsigned long long)nb;
+    unsigned long long b = worst > GROUP_BYTES ? worst : GROUP_BYTES;
+    if (b > 0xFFFFFFEFull) b = 0xFFFFFFEFull;          // one decode call: below 4 GiB
+    g.bytes = (size_t)b;
+    return g;
+}
+
+struct DecompressWs {
+    int16_t *zz;
+    uint8_t *stage;      // the group's bytes: dword aligned, 16 zero bytes behind them
+    void *seg_state, *seg_scratch, *phase1;
+    size_t seg_state_cap;
+    size_t bytes;
+};
+
+DecompressWs carve_decompress(void *ws, size_t nbytes, int nplanes, long long nb)
+{
+    const GroupLimits g = group_limits(nplanes, nb);
+    const size_t bmax = nbytes < g.bytes ? nbytes : g.bytes;
+    const long long nbmax = nb * g.planes;
+    // the largest tables the segmented scheme can ask for: the smallest segments (level 1) over the longest group
+    const jpegx_decode::SegPlan worst = jpegx_decode::seg_plan(bmax, nbmax, 1);
+    unsigned char *p = static_cast<unsigned char *>(ws);
+    DecompressWs d;
+    size_t o = 0;
+    d.zz = reinterpret_cast<int16_t *>(p + o); o += up256((size_t)nbmax * 128);
+    d.stage = p + o; o += up256(bmax + 32);
+    d.seg_state = p + o; d.seg_state_cap = up256(worst.state_bytes); o += d.seg_state_cap;
+    d.seg_scratch = p + o; o += up256(worst.ws_bytes);
+    d.phase1 = p + o; o += up256(jpegx_decode::phase1_bytes(bmax));
+    d.bytes = o;
+    return d;
+}
+
+// Level 2 of the ladder sizes its scratch from the candidate count the device reports: one grow-only allocation per
+// device, owned by the library, shared by the batch calls on that device (one at a time) and freed by
+// jpegx_host_pool_release.
+constexpr int MAX_DEVICES = 16;
+struct Level2Scratch {
+    std::mutex mu;
+    void *p = nullptr;
+    size_t cap = 0;
+};
+Level2Scratch g_level2[MAX_DEVICES];
+
+struct WorkspaceLadder final : jpegx_decode::Ladder {
+    DecompressWs w;
+    std::unique_lock<std::mutex> level2;      // held from a group's level-2 enqueue until its verdict
+
+    int seg_memory(const jpegx_decode::SegPlan &plan, void **d_state, size_t *state_cap, bool *fresh, int *parity, void **d_scratch) override
+    {
+        if (plan.state_bytes > w.seg_state_cap) return fail(JPEGX_E_INVALID, "batch_decompress: workspace smaller than jpegx_batch_decompress_workspace_bytes");
+        *d_state = w.seg_state;
+        *state_cap = (plan.state_bytes + 255) & ~(size_t)255;
+        *fresh = true;                   // cleared by every call, like jpegx_entropy_decode on caller buffers
+        *parity = 0;
+        *d_scratch = w.seg_scratch;
+        return JPEGX_OK;
+    }
+    int phase1_memory(size_t, void **d_ws1) override
+    {
+        *d_ws1 = w.phase1;
+        return JPEGX_OK;
+    }
+    int phase2_memory(size_t bytes, void **d_ws2) override
+    {
+        int dev = 0;
+        B_TRY(hipGetDevice(&dev));
+        if (dev < 0 || dev >= MAX_DEVICES) return fail(JPEGX_E_UNSUPPORTED, "device index beyond the scratch table");
+        Level2Scratch &s = g_level2[dev];
+        level2 = std::unique_lock<std::mutex>(s.mu);
+        if (bytes > s.cap) {
+            if (s.p) (void)hipFree(s.p);
+            s.p = nullptr;
+            s.cap = 0;
+            B_TRY(hipMalloc(&s.p, bytes + bytes / 8));
+            s.cap = bytes + bytes / 8;
+        }
+        *d_ws2 = s.p;
+        return JPEGX_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// jpegx_host_pool_release: the level-2 scratch of the current device goes with the pool
+void jpegx_internal_batch_scratch_release(void)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (dev < 0 || dev >= MAX_DEVICES) return;
+    Level2Scratch &s = g_level2[dev];
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+}
+
+size_t jpegx_batch_workspace_bytes(int nplanes, int H, int W)
+{
+    if (nplanes <= 0 || H <= 0 || W <= 0) return 0;
+    const long long nb = (long long)((H + 7) / 8) * ((W + 7) / 8);
+    if (nb > MAX_BLOCKS / nplanes) return 0;
+    return carve_compress(nullptr, nplanes, nb * nplanes).bytes;
+}
+
+size_t jpegx_batch_max_bytes(int nplanes, int H, int W)
+{
+    if (nplanes <= 0 || H <= 0 || W <= 0) return 0;
+    const long long nb = (long long)((H + 7) / 8) * ((W + 7) / 8);
+    if (nb > MAX_BLOCKS / nplanes) return 0;
+    return (size_t)(nb * nplanes) * 188 + 64;      // 185 bytes per block at most, with the pooled roads' head room
+}
+
+int jpegx_batch_compress(const void *d_in, int elem_size, int nplanes, int H, int W, ptrdiff_t pitch, int bs, int mode, double param,
+                         unsigned flags, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream)
+{
+    if (!d_in || !d_workspace) return fail(JPEGX_E_INVALID, "batch_compress: null device pointer");
+    long long nb = 0;
+    int rc = check_batch_shape(nplanes, H, W, &nb);
+    if (rc) return rc;
+    if (elem_size != 1 && elem_size != 4) return fail(JPEGX_E_INVALID, "batch_compress: elem_size must be 1 (uint8) or 4 (fp32)");
+    if (elem_size == 4 && bs != 1) return fail(JPEGX_E_UNSUPPORTED, "batch_compress: fp32 planes are taken with block_size 1 only");
+    if (elem_size == 1 && bs != 1 && bs != 2 && bs != 4) return fail(JPEGX_E_UNSUPPORTED, "batch_compress: uint8 planes support block_size 1, 2 and 4");
+    if ((long long)nplanes * H > INT_MAX / bs) return fail(JPEGX_E_INVALID, "batch_compress: the stack has more than 2^31 rows");
+    const ptrdiff_t unit = elem_size == 4 ? 4 : 16;      // rows stay 16-byte aligned
+    if (pitch < (ptrdiff_t)W * bs || (pitch % unit) != 0)
+        return fail(JPEGX_E_INVALID, "batch_compress: pitch must be >= W * bs and keep rows 16-byte aligned (fp32: a multiple of 4 elements; uint8: of 16 bytes)");
+    if (!aligned16(d_in) || !aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_compress: planes and workspace must be 16-byte aligned");
+    const long long nblocks = nb * nplanes;
+    const CompressWs c = carve_compress(d_workspace, nplanes, nblocks);
+    unsigned *block_bytes = nullptr, *wave_bytes = nullptr, *half_info = nullptr;
+    jpegx_internal_entropy_views(c.ews, nblocks, &block_bytes, &wave_bytes, &half_info);
+    const int HH = nplanes * H;                          // the stack as one tall plane
+    if (elem_size == 4) {
+        int sized = 0;
+        rc = jpegx_internal_forward_f32_sized(static_cast<const float *>(d_in), HH, W, pitch, mode, param, flags, c.zz, block_bytes, wave_bytes,
+                                              half_info, &sized, stream);
+        if (rc) return rc;
+        // the column-wise tier and the all-float64 kernels do not size their blocks: one pass over the stream does
+        if (!sized && (rc = jpegx_internal_entropy_sizes_half(c.zz, nblocks, c.ews, stream))) return rc;
+    } else {
+        rc = jpegx_internal_forward_u8_sized(static_cast<const uint8_t *>(d_in), HH, W, pitch, bs, mode, param, flags, c.zz, block_bytes, wave_bytes,
+                                             half_info, stream);
+        if (rc) return rc;
+    }
+    if ((rc = jpegx_internal_entropy_scan(nblocks, c.ews, stream))) return rc;
+    return enqueue_index_and_emit(c, nplanes, nb, d_out, out_cap, stream);
+}
+
+int jpegx_batch_emit(void *d_workspace, int nplanes, int H, int W, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream)
+{
+    if (!d_workspace || !d_out) return fail(JPEGX_E_INVALID, "batch_emit: null device pointer");
+    long long nb = 0;
+    int rc = check_batch_shape(nplanes, H, W, &nb);
+    if (rc) return rc;
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_emit: workspace must be 16-byte aligned");
+    const CompressWs c = carve_compress(d_workspace, nplanes, nb * nplanes);
+    return enqueue_index_and_emit(c, nplanes, nb, d_out, out_cap, stream);
+}
+
+int jpegx_batch_compress_status(const void *d_workspace, int nplanes, int H, int W, unsigned long long *h_total,
+                                unsigned long long *h_plane_offsets, jpegx_stream_t stream)
+{
+    if (!d_workspace || !h_total) return fail(JPEGX_E_INVALID, "batch_compress_status: null pointer");
+    long long nb = 0;
+    int rc = check_batch_shape(nplanes, H, W, &nb);
+    if (rc) return rc;
+    const CompressWs c = carve_compress(const_cast<void *>(d_workspace), nplanes, nb * nplanes);
+    unsigned long long ehead[2] = {0, 0}, bhead[2] = {0, 0};
+    hipStream_t st = (hipStream_t)stream;
+    B_TRY(hipMemcpyAsync(ehead, c.ews, 16, hipMemcpyDeviceToHost, st));
+    B_TRY(hipMemcpyAsync(bhead, c.index, 16, hipMemcpyDeviceToHost, st));
+    if (h_plane_offsets)
+        B_TRY(hipMemcpyAsync(h_plane_offsets, static_cast<const unsigned char *>(c.index) + 16, ((size_t)nplanes + 1) * 8, hipMemcpyDeviceToHost, st));
+    B_TRY(hipStreamSynchronize(st));
+    *h_total = ehead[0];
+    if ((unsigned)(ehead[1] & 0xFFFFFFFFull) != 0)
+        return fail(JPEGX_E_INVALID, "BadRleCodeError: an amplitude needs more than 15 bits (|a| > 16383); nothing was written");
+    if (bhead[0] != SIZES_ONLY && ehead[0] > bhead[0]) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "batch: the coded stream needs %llu bytes, the buffer holds %llu; nothing was written", ehead[0], bhead[0]);
+        jpegx_internal_set_error(buf);
+        return 1;
+    }
+    return JPEGX_OK;
+}
+
+size_t jpegx_batch_decompress_workspace_bytes(size_t nbytes, int nplanes, int H, int W)
+{
+    if (nbytes == 0 || nplanes <= 0 || H <= 0 || W <= 0) return 0;
+    const long long nb = (long long)((H + 7) / 8) * ((W + 7) / 8);
+    if (nb > MAX_BLOCKS / nplanes) return 0;
+    return carve_decompress(nullptr, nbytes, nplanes, nb).bytes;
+}
+
+int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int H, int W, int bs, int mode,
+                           double param, unsigned flags, void *d_workspace, void *d_out, ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream)
+{
+    if (!d_bytes || !h_plane_offsets || !d_workspace || !d_out) return fail(JPEGX_E_INVALID, "batch_decompress: null pointer");
+    long long nb = 0;
+    int rc = check_batch_shape(nplanes, H, W, &nb);
+    if (rc) return rc;
+    if (out_type != JPEGX_OUT_F32 && out_type != JPEGX_OUT_I16 && out_type != JPEGX_OUT_U8) return fail(JPEGX_E_INVALID, "batch_decompress: unknown output type");
+    if (mode < JPEGX_Q_NONE || mode > JPEGX_Q_QTABLE) return fail(JPEGX_E_INVALID, "batch_decompress: unknown quantiser mode");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "batch_decompress: block_size must be in 1..255");
+    if (out_type != JPEGX_OUT_U8 && bs != 1) return fail(JPEGX_E_UNSUPPORTED, "batch_decompress: float and int16 samples come with block_size 1 only");
+    if ((long long)nplanes * H > INT_MAX / bs) return fail(JPEGX_E_INVALID, "batch_decompress: the stack has more than 2^31 rows");
+    const int esz = out_type == JPEGX_OUT_F32 ? 4 : (out_type == JPEGX_OUT_I16 ? 2 : 1);
+    const bool pieces8 = esz == 1 && bs != 2 && bs != 4;
+    if (out_pitch < (ptrdiff_t)W * bs || ((size_t)out_pitch * esz) % (pieces8 ? 8 : 16) != 0)
+        return fail(JPEGX_E_INVALID, "batch_decompress: output pitch must be >= W * bs and keep rows 16-byte (uint8 with block_size other than 2, 4: 8-byte) aligned");
+    if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_workspace) & 255u) != 0)
+        return fail(JPEGX_E_INVALID, "batch_decompress: output must be 16-byte, workspace 256-byte aligned");
+    for (int p = 0; p < nplanes; ++p) {
+        if (h_plane_offsets[p + 1] < h_plane_offsets[p]) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "batch_decompress: plane offsets must not decrease (plane %d starts at %llu, plane %d at %llu)", p, h_plane_offsets[p],
+                     p + 1, h_plane_offsets[p + 1]);
+            return fail(JPEGX_E_INVALID, buf);
+        }
+    }
+    const GroupLimits lim = group_limits(nplanes, nb);
+    WorkspaceLadder lad;
+    lad.w = carve_decompress(d_workspace, (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]), nplanes, nb);
+    hipStream_t st = (hipStream_t)stream;
+    for (int p0 = 0; p0 < nplanes;) {
+        // the next group: whole planes while both limits hold, one plane at least
+        int p1 = p0 + 1;
+        while (p1 < nplanes && p1 - p0 < lim.planes && h_plane_offsets[p1 + 1] - h_plane_offsets[p0] <= lim.bytes) ++p1;
+        const unsigned long long gbytes = h_plane_offsets[p1] - h_plane_offsets[p0];
+        const long long gblocks = nb * (p1 - p0);
+        char where[200];
+        if (gbytes > lim.bytes || gbytes < (unsigned long long)gblocks) {      // a block is 1 to 185 bytes
+            snprintf(where, sizeof(where), "batch_decompress: planes %d..%d: %llu bytes cannot be their %lld blocks", p0, p1 - 1, gbytes, gblocks);
+            return fail(JPEGX_E_INVALID, where);
+        }
+        // the group's bytes, dword aligned and with zeros behind them, as the decoder wants them
+        B_TRY(hipMemsetAsync(lad.w.stage + ((size_t)gbytes & ~(size_t)3), 0, 16 + ((size_t)gbytes & 3), st));
+        B_TRY(hipMemcpyAsync(lad.w.stage, d_bytes + h_plane_offsets[p0], (size_t)gbytes, hipMemcpyDeviceToDevice, st));
+        rc = jpegx_decode::LADDER_NEXT_LEVEL;
+        for (int level = 0; level < 3 && rc == jpegx_decode::LADDER_NEXT_LEVEL; ++level) {      // planned segments, 256-byte segments, the whole stream
+            rc = jpegx_decode::ladder_enqueue(lad, lad.w.stage, (size_t)gbytes, gblocks, lad.w.zz, st, level);
+            if (rc == JPEGX_OK) {
+                const hipError_t e = hipStreamSynchronize(st);
+                if (e != hipSuccess) {
+                    if (lad.level2.owns_lock()) lad.level2.unlock();
+                    B_TRY(e);
+                }
+                rc = jpegx_decode::ladder_status(lad);
+            }
+            if (lad.level2.owns_lock()) lad.level2.unlock();
+        }
+        if (rc == jpegx_decode::LADDER_NEXT_LEVEL) rc = fail(JPEGX_E_INVALID, "device decoder: no scheme took the stream");
+        if (rc == JPEGX_E_INVALID) {
+            snprintf(where, sizeof(where), "batch_decompress: planes %d..%d: their %llu bytes are not %lld well-formed blocks (%.80s)", p0, p1 - 1, gbytes,
+                     gblocks, jpegx_last_error());
+            return fail(JPEGX_E_INVALID, where);
+        }
+        if (rc) return rc;
+        const int GH = (p1 - p0) * H;
+        unsigned char *dst = static_cast<unsigned char *>(d_out) + (size_t)p0 * H * bs * (size_t)out_pitch * esz;
+        if (out_type == JPEGX_OUT_U8)
+            rc = jpegx_inverse_fused_u8_inflated(lad.w.zz, GH, W, mode, param, flags, bs, dst, out_pitch, stream);
+        else
+            rc = jpegx_inverse_fused(lad.w.zz, GH, W, mode, param, flags, dst, out_pitch, out_type, stream);
+        if (rc) return rc;
+        p0 = p1;
+    }
+    return JPEGX_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 #include <stdio.h>
 
 #include "../../include/jpegx.h"
+#include "jpegx_rle_sizes.h"
 
 extern "C" void jpegx_internal_set_error(const char *msg);  // jpegx_runtime.hip (thread-local string)
 
@@ -152,6 +153,54 @@ __global__ __launch_bounds__(64) void k_rle_sizes(const int16_t *__restrict__ zz
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
     if (lane == 0) W.wave_bytes[blockIdx.x] = sum;
+}
+
+// k_rle_sizes for the two-lanes-per-block emitter, behind a forward kernel that does not size its own blocks (the
+// column-wise strip tier, the all-float64 kernels): one pass over the int16 stream, same staging, the forward kernels'
+// rle_block_bytes on the block's 32 words -- so block_bytes, HALF_INFO and the wave's total with the bad-amplitude bit in
+// bit 31 (k_scan_* turn it into the error flag) are what a sizing forward kernel would have left.
+__global__ __launch_bounds__(64) void k_rle_sizes_half(const int16_t *__restrict__ zz, int nblk, void *ws)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[TILE_BYTES];
+    const Workspace W = carve(ws, nblk);
+    const int lane = threadIdx.x, g0 = blockIdx.x * 64, g = g0 + lane;
+    stage_tile(zz, g0, nblk, lane, lds);
+    unsigned w[32];
+    load_block(lds, lane, w);
+    bool bad;
+    unsigned half;
+    unsigned bytes = rle_block_bytes(w, bad, half);
+    if (g >= nblk) { bytes = 0; bad = false; }
+    if (g < nblk) { W.block_bytes[g] = bytes; W.half_info[g] = half; }
+    unsigned sum = bytes;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    if (lane == 0) W.wave_bytes[blockIdx.x] = sum | (__any(bad) ? 0x80000000u : 0u);
+}
+
+// Plane index of a batch (nplanes planes of nb blocks each, one stream): byte offset of every plane's first block b =
+// p nb from the scans' results -- chunk_off[w / SCAN_CHUNK] + wave_off[w] + the sizes of the blocks of wave w = b / 64 in
+// front of b (nb need not be a multiple of 64: a wave may straddle two planes) -- and the total behind the last.  One
+// wave per 64 planes, a lane per plane, at most 63 loads per lane.  Also notes the capacity the emit step that follows
+// is given (BatchHead), so that jpegx_batch_compress_status can tell "did not fit" without the caller repeating it.
+struct BatchHead {
+    unsigned long long out_cap;      // ~0: sizes only, nothing to emit
+    unsigned long long pad;
+};
+
+__global__ __launch_bounds__(64) void k_plane_index(int nplanes, int nb, const void *ws, int nblk, BatchHead *head,
+                                                    unsigned long long *plane_offsets, unsigned long long out_cap)
+{
+    const Workspace W = carve(const_cast<void *>(ws), nblk);
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p == 0) { head->out_cap = out_cap; head->pad = 0; }
+    if (p > nplanes) return;
+    if (p == nplanes) { plane_offsets[p] = *W.total; return; }
+    const long long b = (long long)p * nb;
+    const int w = (int)(b >> 6);
+    unsigned long long off = W.chunk_off[w / SCAN_CHUNK] + W.wave_off[w];
+    for (long long k = (long long)w * 64; k < b; ++k) off += W.block_bytes[k];
+    plane_offsets[p] = off;
 }
 
 // Two-level exclusive scan of the per-wave totals.  Level 1: one workgroup per SCAN_CHUNK waves,
@@ -336,13 +385,17 @@ __global__ __launch_bounds__(64) void k_rle_emit(const int16_t *__restrict__ zz,
 // of 32..63, from the bit offset and the last non-zero the forward kernel left in half_info).  A single 4096 x 4096
 // band is 4096 such workgroups -- a handful per CU -- and the time of this kernel is then the length of one lane's
 // dependent walk: 32 steps instead of 64.
+// GUARD (the batch entries): nothing is written either when the scanned total does not fit the caller's buffer -- the
+// total is on the device once the scan has run, one uniform load.
+template <bool GUARD>
 __global__ __launch_bounds__(128) void k_rle_emit2(const int16_t *__restrict__ zz, int nblk, const void *ws,
-                                                   unsigned char *__restrict__ out)
+                                                   unsigned char *__restrict__ out, unsigned long long out_cap)
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[EMIT_STAGE_BYTES];
     unsigned *stage = reinterpret_cast<unsigned *>(lds);
     const Workspace W = carve(const_cast<void *>(ws), nblk);
     if (*W.error != 0) return;                           // an amplitude beyond 15 bits: nothing is emitted (see k_rle_emit)
+    if (GUARD && *W.total > out_cap) return;
     const int t = threadIdx.x, lane = t & 63, half = t >> 6, g0 = blockIdx.x * 64, g = g0 + lane;
     {
         // the wave's 64 x 128 B of coefficients -> swizzled LDS tile, four LDS-DMA pieces per wave
@@ -486,7 +539,45 @@ int jpegx_internal_entropy_emit2(const int16_t *d_zz, long long nblocks, const v
     if (rc) return rc;
     if (!d_out) return fail(JPEGX_E_INVALID, "null output pointer");
     const int nblk = (int)nblocks;
-    hipLaunchKernelGGL(k_rle_emit2, dim3((nblk + 63) / 64), dim3(128), 0, (hipStream_t)stream, d_zz, nblk, d_workspace, d_out);
+    hipLaunchKernelGGL(k_rle_emit2<false>, dim3((nblk + 63) / 64), dim3(128), 0, (hipStream_t)stream, d_zz, nblk, d_workspace, d_out, 0ull);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+// the same for the batch entries (jpegx_batch.cpp): writes nothing either when the scanned total exceeds out_cap
+int jpegx_internal_entropy_emit2_guarded(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, size_t out_cap,
+                                         jpegx_stream_t stream)
+{
+    int rc = check_args(d_zz, nblocks, d_workspace);
+    if (rc) return rc;
+    if (!d_out) return fail(JPEGX_E_INVALID, "null output pointer");
+    const int nblk = (int)nblocks;
+    hipLaunchKernelGGL(k_rle_emit2<true>, dim3((nblk + 63) / 64), dim3(128), 0, (hipStream_t)stream, d_zz, nblk, d_workspace, d_out,
+                       (unsigned long long)out_cap);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+// sizes WITH half_info for a stream whose forward kernel left none (no scan: jpegx_internal_entropy_scan follows)
+int jpegx_internal_entropy_sizes_half(const int16_t *d_zz, long long nblocks, void *d_workspace, jpegx_stream_t stream)
+{
+    int rc = check_args(d_zz, nblocks, d_workspace);
+    if (rc) return rc;
+    const int nblk = (int)nblocks;
+    hipLaunchKernelGGL(k_rle_sizes_half, dim3((nblk + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_zz, nblk, d_workspace);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+// plane index of a batch after the scan: d_index = [BatchHead 16 bytes][nplanes + 1 offsets], 16-byte aligned
+int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
+                                       jpegx_stream_t stream)
+{
+    const long long nblocks = (long long)nplanes * blocks_per_plane;
+    if (!d_workspace || !d_index || nplanes <= 0 || blocks_per_plane <= 0 || nblocks > 0x7FFFFFC0LL) return fail(JPEGX_E_INVALID, "bad plane index arguments");
+    BatchHead *head = static_cast<BatchHead *>(d_index);
+    hipLaunchKernelGGL(k_plane_index, dim3((nplanes + 1 + 63) / 64), dim3(64), 0, (hipStream_t)stream, nplanes, (int)blocks_per_plane, d_workspace,
+                       (int)nblocks, head, reinterpret_cast<unsigned long long *>(head + 1), (unsigned long long)out_cap);
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

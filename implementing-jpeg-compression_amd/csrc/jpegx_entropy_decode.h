@@ -34,4 +34,29 @@ SegPlan seg_plan(size_t nbytes, long long nblocks, int level = 0, int filter = -
 // d_state + 64 * parity).  d_ws: plan.ws_bytes of scratch.
 void enqueue_segmented(const uint8_t *d_bytes, size_t nbytes, long long nblocks, const SegPlan &plan, void *d_state, size_t state_cap, bool fresh, int parity,
                        void *d_ws, int16_t *d_zz, hipStream_t st);
+
+// ---- the level ladder, shared by the pooled host roads (jpegx_hostpipe.cpp: a BandSlot) and the batch entry on caller
+// buffers (jpegx_batch.cpp).  One rung per call: level 0 = the segmented scheme with planned segments, 1 = with 256-byte
+// segments, 2 = the whole-stream scheme (phase 1, candidate count read back -- this synchronises `st` --, phase 2).  The
+// owner of the memory answers the three requests; the ladder keeps what it has to remember between a rung and its verdict.
+constexpr int LADDER_NEXT_LEVEL = 1;      // ladder_status: this rung could not take the stream, enqueue the next
+struct Ladder {
+    // first try: candidates that cannot start a block of non-negative samples are dropped (jpegx_entropy_decode.hip).  A
+    // stream with blocks that do start otherwise (DC 0 beside non-zero AC: very dark content) misses there and takes the
+    // second try; the filter then stays off for this working set's next calls, so that such content pays once in a while
+    unsigned filter_pause = 0;
+    bool last_filter = false;
+    int seg_parity = -1;                  // status block of the last rung (-1: the whole-stream scheme ran)
+    const void *status_at = nullptr;      // device address of that rung's 64 status bytes
+    // segmented scheme: plan.ws_bytes of scratch and >= plan.state_bytes of state (see enqueue_segmented for fresh / parity)
+    virtual int seg_memory(const SegPlan &plan, void **d_state, size_t *state_cap, bool *fresh, int *parity, void **d_ws) = 0;
+    virtual int phase1_memory(size_t bytes, void **d_ws1) = 0;
+    virtual int phase2_memory(size_t bytes, void **d_ws2) = 0;     // sized from the candidate count
+protected:
+    ~Ladder() = default;
+};
+// d_bytes: dword aligned, 16 zero bytes readable behind the stream.  JPEGX_OK or an error code (message set).
+int ladder_enqueue(Ladder &lad, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int16_t *d_zz, hipStream_t st, int level);
+// once the stream has been synchronised: JPEGX_OK, JPEGX_E_INVALID (not a sequence of well-formed blocks) or LADDER_NEXT_LEVEL
+int ladder_status(Ladder &lad);
 }  // namespace jpegx_decode

@@ -318,10 +318,15 @@ void k_forward_fused(const float *__restrict__ in, size_t pitch, int wb,
 // SOURCE address because the DMA's LDS destination is always base + lane * 16.
 // After the compute the dead strip is reused as the output tile.
 // ------------------------------------------------------------------------------------------------
-template <int VAR, bool NT>
+// SIZES: the entropy stage's byte count of every block from the registers, as k_forward_fused_u8 does it
+// (rle_block_bytes, after the exact tier has patched pk): block_bytes[block], half_info[block] and the wave's total
+// with the bad-amplitude bit into wave_bytes[wg] -- wg is the strip's number, which under the XCD-private order is not
+// blockIdx.x.  SIZES = false compiles to the code the kernel had before the parameter existed.
+template <int VAR, bool NT, bool SIZES = false>
 __device__ __forceinline__ void forward_strip_body(unsigned char *lds, int wg, const float *__restrict__ in, size_t pitch, int wb,
                                                    int nblk, const QuantParams &prm, int16_t *__restrict__ out,
-                                                   unsigned long long *counters)
+                                                   unsigned long long *counters, unsigned *__restrict__ block_bytes = nullptr,
+                                                   unsigned *__restrict__ wave_bytes = nullptr, unsigned *__restrict__ half_info = nullptr)
 {
     constexpr bool PIXEL = (VAR & 1) != 0;
     constexpr bool DC_EXACT = (VAR & 2) != 0;
@@ -404,6 +409,18 @@ __device__ __forceinline__ void forward_strip_body(unsigned char *lds, int wg, c
         __syncthreads();
     }
 
+    if (SIZES) {
+        bool bad;
+        unsigned half;
+        unsigned bytes = rle_block_bytes(pk, bad, half);
+        if (!valid) { bytes = 0; bad = false; }
+        if (valid) { block_bytes[g0 + lane] = bytes; half_info[g0 + lane] = half; }
+        unsigned sum = bytes;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        if (lane == 0) wave_bytes[wg] = sum | (__any(bad) ? 0x80000000u : 0u);
+    }
+
     // the strip is dead: reuse its first 8 KiB as the swizzled output tile
     __syncthreads();
 #pragma unroll
@@ -413,10 +430,11 @@ __device__ __forceinline__ void forward_strip_body(unsigned char *lds, int wg, c
     store_tile<NT>(lds, out, g0, nblk, lane);
 }
 
-template <int VAR, bool NT>
+template <int VAR, bool NT, bool SIZES = false>
 __global__ __launch_bounds__(64) void k_forward_fused_strip(const float *__restrict__ in, size_t pitch, int wb,
                                                             int nblk, QuantParams prm, int16_t *__restrict__ out,
-                                                            unsigned long long *counters)
+                                                            unsigned long long *counters, unsigned *__restrict__ block_bytes,
+                                                            unsigned *__restrict__ wave_bytes, unsigned *__restrict__ half_info)
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[STRIP_LDS_BYTES];
     int wg = blockIdx.x;
@@ -424,7 +442,7 @@ __global__ __launch_bounds__(64) void k_forward_fused_strip(const float *__restr
         wg = xcd_private_wg(blockIdx.x, (nblk + 63) >> 6, (prm.tune >> 8) & 31);
         if (wg >= ((nblk + 63) >> 6)) return;
     }
-    forward_strip_body<VAR, NT>(lds, wg, in, pitch, wb, nblk, prm, out, counters);
+    forward_strip_body<VAR, NT, SIZES>(lds, wg, in, pitch, wb, nblk, prm, out, counters, block_bytes, wave_bytes, half_info);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1340,9 +1358,15 @@ float max_abs_multiplier(const QuantParams &qp)
     return m;
 }
 
+// where a forward kernel that sizes its own blocks leaves the sizes (the entropy stage's workspace, jpegx_entropy.hip)
+struct SizeViews {
+    unsigned *block_bytes, *wave_bytes, *half_info;
+    bool sized;     // out: the launched kernel wrote them (the whole-block strip tier; every other tier leaves them to k_rle_sizes_half)
+};
+
 template <int BS, bool NT, int STAGED = 0>
 int launch_forward(const float *d_in, int H, int W, ptrdiff_t pitch, const QuantParams &qp, unsigned flags,
-                   int16_t *d_out, hipStream_t st)
+                   int16_t *d_out, hipStream_t st, SizeViews *sv = nullptr)
 {
     const int wb = W / 8, nblk = (H / 8) * wb;
     const dim3 grid((nblk + 63) / 64), block(64);
@@ -1389,12 +1413,24 @@ int launch_forward(const float *d_in, int H, int W, ptrdiff_t pitch, const Quant
             HIP_TRY(hipGetLastError());
             return JPEGX_OK;
         }
-        if (dc_exact)
-            hipLaunchKernelGGL((k_forward_fused_strip<3, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters);
+        unsigned *const none = nullptr;
+        if (sv) {
+            sv->sized = true;
+            if (dc_exact)
+                hipLaunchKernelGGL((k_forward_fused_strip<3, NT, true>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters,
+                                   sv->block_bytes, sv->wave_bytes, sv->half_info);
+            else if (pixel)
+                hipLaunchKernelGGL((k_forward_fused_strip<1, NT, true>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters,
+                                   sv->block_bytes, sv->wave_bytes, sv->half_info);
+            else
+                hipLaunchKernelGGL((k_forward_fused_strip<0, NT, true>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters,
+                                   sv->block_bytes, sv->wave_bytes, sv->half_info);
+        } else if (dc_exact)
+            hipLaunchKernelGGL((k_forward_fused_strip<3, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters, none, none, none);
         else if (pixel)
-            hipLaunchKernelGGL((k_forward_fused_strip<1, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters);
+            hipLaunchKernelGGL((k_forward_fused_strip<1, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters, none, none, none);
         else
-            hipLaunchKernelGGL((k_forward_fused_strip<0, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters);
+            hipLaunchKernelGGL((k_forward_fused_strip<0, NT>), g2, block, 0, st, d_in, (size_t)pitch, wb, nblk, q2, d_out, g_counters, none, none, none);
     } else {
         QuantParams qa = qp;
         scale_for_aan(&qa);
@@ -1412,8 +1448,8 @@ int launch_forward(const float *d_in, int H, int W, ptrdiff_t pitch, const Quant
 
 extern "C" {
 
-int jpegx_forward_fused_pooled(const float *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param,
-                               unsigned flags, int16_t *d_out, jpegx_stream_t stream)
+static int forward_f32_common(const float *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param,
+                              unsigned flags, int16_t *d_out, SizeViews *sv, jpegx_stream_t stream)
 {
     if (bs != 1 && bs != 2 && bs != 4) return fail(JPEGX_E_UNSUPPORTED, "fused mean-pool supports block_size 1, 2 and 4");
     int rc = check_plane(d_in, d_out, H, W, pitch / bs, 1);
@@ -1440,8 +1476,28 @@ int jpegx_forward_fused_pooled(const float *d_in, int H, int W, ptrdiff_t pitch,
     }
     if (bs == 2) return launch_forward<2, false>(d_in, H, W, pitch, qp, flags, d_out, st);
     if (bs == 4) return launch_forward<4, false>(d_in, H, W, pitch, qp, flags, d_out, st);
-    if (flags & JPEGX_F_TUNE_NO_NT) return launch_forward<1, false>(d_in, H, W, pitch, qp, flags, d_out, st);
-    return launch_forward<1, true>(d_in, H, W, pitch, qp, flags, d_out, st);
+    if (flags & JPEGX_F_TUNE_NO_NT) return launch_forward<1, false>(d_in, H, W, pitch, qp, flags, d_out, st, sv);
+    return launch_forward<1, true>(d_in, H, W, pitch, qp, flags, d_out, st, sv);
+}
+
+int jpegx_forward_fused_pooled(const float *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param,
+                               unsigned flags, int16_t *d_out, jpegx_stream_t stream)
+{
+    return forward_f32_common(d_in, H, W, pitch, bs, mode, param, flags, d_out, nullptr, stream);
+}
+
+// internal: jpegx_forward_fused with the entropy stage's block sizes written on the way where the dispatched tier can
+// (*sized = 1: the whole-block strip tier); *sized = 0: the stream is there, the sizes are the caller's to make
+// (jpegx_internal_entropy_sizes_half)
+int jpegx_internal_forward_f32_sized(const float *d_in, int H, int W, ptrdiff_t pitch, int mode, double param, unsigned flags,
+                                     int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, int *sized,
+                                     jpegx_stream_t stream)
+{
+    if (!block_bytes || !wave_bytes || !half_info || !sized) return fail(JPEGX_E_INVALID, "null workspace views");
+    SizeViews sv{block_bytes, wave_bytes, half_info, false};
+    const int rc = forward_f32_common(d_in, H, W, pitch, 1, mode, param, flags, d_out, &sv, stream);
+    *sized = sv.sized ? 1 : 0;
+    return rc;
 }
 
 int jpegx_forward_fused_planes(const jpegx_plane_desc *planes, int nplanes, int mode, double param, unsigned flags,

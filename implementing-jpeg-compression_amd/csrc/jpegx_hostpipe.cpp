@@ -33,6 +33,7 @@ extern "C" int jpegx_internal_forward_u8_sized(const uint8_t *d_in, int H, int W
 extern "C" void jpegx_internal_entropy_views(void *d_workspace, long long nblocks, unsigned **block_bytes, unsigned **wave_bytes, unsigned **half_info);
 extern "C" int jpegx_internal_entropy_emit2(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
 extern "C" int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);
+extern "C" void jpegx_internal_batch_scratch_release(void);
 
 namespace {
 
@@ -84,19 +85,40 @@ constexpr int MAX_DEVICES = 16;
 constexpr int MAX_BANDS = JPEGX_MAX_IMAGE_BANDS;
 
 // the device-side working set of one band
-struct BandSlot {
+struct BandSlot final : jpegx_decode::Ladder {     // the decoder's level ladder finds its memory in the slot's grow-only spans
     Span d_in, d_zz, d_ws, d_out, d_tmp;
     Span d_seg, d_seg_state;      // the segmented entropy decoder's scratch, and its state: that stays clean from call to call
     void *seg_clean = nullptr;    // the allocation that has been cleared
     size_t seg_clean_cap = 0;
     unsigned seg_calls = 0;
-    int seg_parity = -1;          // status block of the last decode (-1: the general scheme ran, status in d_ws)
     bool sized = false;           // compress: the forward kernel sized the blocks itself (half_info is there)
-    // decoder, first try: candidates that cannot start a block of non-negative samples are dropped (jpegx_entropy_decode.hip).
-    // A stream with blocks that do start otherwise (DC 0 beside non-zero AC: very dark content) misses there and takes the
-    // second try; the filter then stays off for this working set's next calls, so that such content pays once in a while
-    unsigned filter_pause = 0;
-    bool last_filter = false;
+
+    int seg_memory(const jpegx_decode::SegPlan &plan, void **d_state, size_t *state_cap, bool *fresh, int *parity, void **d_scratch) override
+    {
+        int rc;
+        if ((rc = d_seg.ensure(plan.ws_bytes)) || (rc = d_seg_state.ensure(plan.state_bytes))) return rc;
+        *fresh = d_seg_state.p != seg_clean || d_seg_state.cap != seg_clean_cap;
+        if (const char *ff = getenv("JPEGX_DECODE_FRESH")) *fresh = *fresh || (*ff && *ff != '0');      // tests: clear the state on every call
+        seg_clean = d_seg_state.p;
+        seg_clean_cap = d_seg_state.cap;
+        *parity = (int)(seg_calls++ & 1u);
+        *d_state = d_seg_state.p;
+        *state_cap = d_seg_state.cap;
+        *d_scratch = d_seg.p;
+        return JPEGX_OK;
+    }
+    int phase1_memory(size_t bytes, void **d_ws1) override
+    {
+        const int rc = d_ws.ensure(bytes);
+        *d_ws1 = d_ws.p;
+        return rc;
+    }
+    int phase2_memory(size_t bytes, void **d_ws2) override
+    {
+        const int rc = d_tmp.ensure(bytes);
+        *d_ws2 = d_tmp.p;
+        return rc;
+    }
 };
 
 // One job context: a stream set and grow-only buffers.  A device has POOL_CONTEXTS of them, so that jobs of several host
@@ -601,68 +623,83 @@ namespace {
 // stream's length only, no host round trip; decode_status afterwards may answer DECODE_RETRY_GENERAL ("next level") for a
 // stream whose densest stretch overflows a segment's tables.  level 1: the same with 256-byte segments.  level 2: the
 // pointer-jumping scheme over the whole stream, which reads the candidate count back in the middle.
-constexpr int DECODE_RETRY_GENERAL = 1;
+constexpr int DECODE_RETRY_GENERAL = jpegx_decode::LADDER_NEXT_LEVEL;
 
 thread_local int t_last_decode_level = -1;      // which scheme took the last stream on this thread (tests)
+}  // namespace
+
+// The ladder itself (jpegx_entropy_decode.h): one rung on any owner's memory.
+int jpegx_decode::ladder_enqueue(Ladder &lad, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int16_t *d_zz, hipStream_t st, int level)
+{
+    int rc;
+    const char *force = getenv("JPEGX_DECODE_GENERAL");    // tests / A-B runs: the general scheme from the start
+    if (force && *force && *force != '0') level = 2;
+    if (level == 1 && seg_plan(nbytes, nblocks, 0).seg == 256) level = 2;      // the first try had the smallest segments already
+    const SegPlan plan = seg_plan(nbytes, nblocks, level, (level == 0 && lad.filter_pause > 0) ? 0 : -1);
+    if (level == 0 && lad.filter_pause > 0) --lad.filter_pause;
+    lad.last_filter = plan.filter;
+    t_last_decode_level = level;
+    if (level < 2 && plan.ok) {
+        void *d_state = nullptr, *d_scratch = nullptr;
+        size_t state_cap = 0;
+        bool fresh = true;
+        int parity = 0;
+        if ((rc = lad.seg_memory(plan, &d_state, &state_cap, &fresh, &parity, &d_scratch))) return rc;
+        lad.seg_parity = parity;
+        lad.status_at = static_cast<const unsigned char *>(d_state) + 64 * parity;
+        enqueue_segmented(d_bytes, nbytes, nblocks, plan, d_state, state_cap, fresh, parity, d_scratch, d_zz, st);
+        HP_TRY(hipGetLastError());
+        return JPEGX_OK;
+    }
+    lad.seg_parity = -1;
+    void *d_ws1 = nullptr, *d_ws2 = nullptr;
+    if ((rc = lad.phase1_memory(phase1_bytes(nbytes), &d_ws1))) return rc;
+    lad.status_at = d_ws1;
+    enqueue_phase1(d_bytes, nbytes, d_ws1, st);
+    unsigned head[4] = {0, 0, 0, 0};
+    HP_TRY(hipMemcpyAsync(head, d_ws1, 16, hipMemcpyDeviceToHost, st));
+    HP_TRY(hipStreamSynchronize(st));
+    const unsigned ncand = head[0];
+    if (ncand == 0 || (long long)ncand < nblocks) return fail(JPEGX_E_INVALID, "entropy stream holds fewer blocks than the plane has");
+    if ((rc = lad.phase2_memory(phase2_bytes(ncand, nblocks), &d_ws2))) return rc;
+    enqueue_phase2(d_bytes, nbytes, nblocks, d_ws1, ncand, d_ws2, d_zz, st);
+    HP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_decode::ladder_status(Ladder &lad)
+{
+    unsigned head[16] = {0};
+    const bool seg = lad.seg_parity >= 0;
+    HP_TRY(hipMemcpy(head, lad.status_at, 64, hipMemcpyDeviceToHost));
+    if (seg && head[2] != 0) {
+        if ((head[2] & 4u) && lad.last_filter) lad.filter_pause = 64;      // the candidate filter missed a block start: without it for a while
+        return LADDER_NEXT_LEVEL;
+    }
+    if (head[1] != 0) return fail(JPEGX_E_INVALID, "entropy stream is not a sequence of well-formed blocks (device decoder)");
+    return JPEGX_OK;
+}
+
+namespace {
 
 int decode_on_device(BandSlot &slot, size_t nbytes, long long nblocks, hipStream_t st, int level)
 {
     int rc;
     if ((rc = slot.d_zz.ensure((size_t)nblocks * 128))) return rc;
-    const char *force = getenv("JPEGX_DECODE_GENERAL");    // tests / A-B runs: the general scheme from the start
-    if (force && *force && *force != '0') level = 2;
-    if (level == 1 && jpegx_decode::seg_plan(nbytes, nblocks, 0).seg == 256) level = 2;      // the first try had the smallest segments already
-    const jpegx_decode::SegPlan plan = jpegx_decode::seg_plan(nbytes, nblocks, level, (level == 0 && slot.filter_pause > 0) ? 0 : -1);
-    if (level == 0 && slot.filter_pause > 0) --slot.filter_pause;
-    slot.last_filter = plan.filter;
-    t_last_decode_level = level;
-    if (level < 2 && plan.ok) {
-        if ((rc = slot.d_seg.ensure(plan.ws_bytes)) || (rc = slot.d_seg_state.ensure(plan.state_bytes))) return rc;
-        bool fresh = slot.d_seg_state.p != slot.seg_clean || slot.d_seg_state.cap != slot.seg_clean_cap;
-        if (const char *ff = getenv("JPEGX_DECODE_FRESH")) fresh = fresh || (*ff && *ff != '0');      // tests: clear the state on every call
-        slot.seg_clean = slot.d_seg_state.p;
-        slot.seg_clean_cap = slot.d_seg_state.cap;
-        slot.seg_parity = (int)(slot.seg_calls++ & 1u);
-        jpegx_decode::enqueue_segmented(static_cast<const uint8_t *>(slot.d_in.p), nbytes, nblocks, plan, slot.d_seg_state.p, slot.d_seg_state.cap, fresh,
-                                        slot.seg_parity, slot.d_seg.p, static_cast<int16_t *>(slot.d_zz.p), st);
-        HP_TRY(hipGetLastError());
-        return JPEGX_OK;
-    }
-    slot.seg_parity = -1;
-    if ((rc = slot.d_ws.ensure(jpegx_decode::phase1_bytes(nbytes)))) return rc;
-    jpegx_decode::enqueue_phase1(static_cast<const uint8_t *>(slot.d_in.p), nbytes, slot.d_ws.p, st);
-    unsigned head[4] = {0, 0, 0, 0};
-    HP_TRY(hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st));
-    HP_TRY(hipStreamSynchronize(st));
-    const unsigned ncand = head[0];
-    if (ncand == 0 || (long long)ncand < nblocks) return fail(JPEGX_E_INVALID, "entropy stream holds fewer blocks than the plane has");
-    if ((rc = slot.d_tmp.ensure(jpegx_decode::phase2_bytes(ncand, nblocks)))) return rc;
-    jpegx_decode::enqueue_phase2(static_cast<const uint8_t *>(slot.d_in.p), nbytes, nblocks, slot.d_ws.p, ncand, slot.d_tmp.p,
-                                 static_cast<int16_t *>(slot.d_zz.p), st);
-    HP_TRY(hipGetLastError());
-    return JPEGX_OK;
+    return jpegx_decode::ladder_enqueue(slot, static_cast<const uint8_t *>(slot.d_in.p), nbytes, nblocks, static_cast<int16_t *>(slot.d_zz.p), st, level);
 }
 
 // after the stream has been synchronised: JPEGX_OK, an error, or DECODE_RETRY_GENERAL
 int decode_status(BandSlot &slot)
 {
-    unsigned head[16] = {0};
-    const bool seg = slot.seg_parity >= 0;
-    const unsigned char *src = seg ? static_cast<const unsigned char *>(slot.d_seg_state.p) + 64 * slot.seg_parity : static_cast<const unsigned char *>(slot.d_ws.p);
-    HP_TRY(hipMemcpy(head, src, 64, hipMemcpyDeviceToHost));
     if (const char *dump = getenv("JPEGX_DECODE_STATS")) {     // a -DJPEGX_DECODE_STATS build leaves per-segment time stamps in its scratch
-        if (seg) {
+        if (slot.seg_parity >= 0) {
             std::vector<unsigned char> raw(slot.d_seg.cap);
             HP_TRY(hipMemcpy(raw.data(), slot.d_seg.p, raw.size(), hipMemcpyDeviceToHost));
             if (FILE *f = fopen(dump, "wb")) { fwrite(raw.data(), 1, raw.size(), f); fclose(f); }
         }
     }
-    if (seg && head[2] != 0) {
-        if ((head[2] & 4u) && slot.last_filter) slot.filter_pause = 64;      // the candidate filter missed a block start: without it for a while
-        return DECODE_RETRY_GENERAL;
-    }
-    if (head[1] != 0) return fail(JPEGX_E_INVALID, "entropy stream is not a sequence of well-formed blocks (device decoder)");
-    return JPEGX_OK;
+    return jpegx_decode::ladder_status(slot);
 }
 
 int check_decompress_shape(const uint8_t *h_bytes, size_t nbytes, int H, int W, int bs)
@@ -993,6 +1030,7 @@ int jpegx_host_pool_release(void)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (pool->ev_x) { (void)hipEventDestroy(pool->ev_x); pool->ev_x = nullptr; }
     }
+    jpegx_internal_batch_scratch_release();      // the batch decoder's level-2 scratch of this device (jpegx_batch.cpp)
     return JPEGX_OK;
 }
 

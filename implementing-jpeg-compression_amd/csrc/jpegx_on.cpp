@@ -65,6 +65,14 @@ JPEGX_ON(jpegx_entropy_emit, (int device, const int16_t *d_zz, long long nblocks
 JPEGX_ON(jpegx_entropy_decode, (int device, const uint8_t *d_bytes, size_t nbytes, long long nblocks, void *d_workspace, int16_t *d_zz, int level, jpegx_stream_t stream),
          (d_bytes, nbytes, nblocks, d_workspace, d_zz, level, stream))
 JPEGX_ON(jpegx_entropy_decode_status, (int device, const void *d_workspace, jpegx_stream_t stream), (d_workspace, stream))
+JPEGX_ON(jpegx_batch_compress, (int device, const void *d_in, int elem_size, int nplanes, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, unsigned flags, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_in, elem_size, nplanes, H, W, pitch, bs, mode, param, flags, d_workspace, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_compress_status, (int device, const void *d_workspace, int nplanes, int H, int W, unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream),
+         (d_workspace, nplanes, H, W, h_total, h_plane_offsets, stream))
+JPEGX_ON(jpegx_batch_emit, (int device, void *d_workspace, int nplanes, int H, int W, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_workspace, nplanes, H, W, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_decompress, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int H, int W, int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out, ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream),
+         (d_bytes, h_plane_offsets, nplanes, H, W, bs, mode, param, flags, d_workspace, d_out, out_pitch, out_type, stream))
 JPEGX_ON(jpegx_host_compress_begin, (int device, const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, size_t *nbytes),
          (h_plane, elem_size, H, W, pitch, bs, mode, param, nbytes))
 JPEGX_ON(jpegx_host_compress_image, (int device, const void *const *h_planes, int nbands, int elem_size, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),

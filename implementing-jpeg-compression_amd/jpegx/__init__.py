@@ -136,6 +136,13 @@ SIGNATURES = {
     "jpegx_entropy_decode_workspace_bytes": [_sz, _c.c_longlong],
     "jpegx_entropy_decode": [_vp, _sz, _c.c_longlong, _vp, _vp, _int, _vp],
     "jpegx_entropy_decode_status": [_vp, _vp],
+    "jpegx_batch_workspace_bytes": [_int, _int, _int],
+    "jpegx_batch_max_bytes": [_int, _int, _int],
+    "jpegx_batch_compress": [_vp, _int, _int, _int, _int, _pd, _int, _int, _dbl, _uint, _vp, _vp, _sz, _vp],
+    "jpegx_batch_compress_status": [_vp, _int, _int, _int, _c.POINTER(_c.c_ulonglong), _vp, _vp],
+    "jpegx_batch_emit": [_vp, _int, _int, _int, _vp, _sz, _vp],
+    "jpegx_batch_decompress_workspace_bytes": [_sz, _int, _int, _int],
+    "jpegx_batch_decompress": [_vp, _vp, _int, _int, _int, _int, _int, _dbl, _uint, _vp, _vp, _pd, _int, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -149,11 +156,13 @@ SIGNATURES = {
 for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_generate_plane", "jpegx_forward_fused_pooled",
               "jpegx_forward_fused_u8", "jpegx_forward_fused_f64", "jpegx_forward_fused_planes", "jpegx_mean_pool_f64",
               "jpegx_inverse_fused_u8_inflated", "jpegx_entropy_sizes", "jpegx_entropy_total", "jpegx_entropy_block_sizes",
-              "jpegx_entropy_emit", "jpegx_entropy_decode", "jpegx_entropy_decode_status", "jpegx_host_compress_begin", "jpegx_host_compress_image", "jpegx_host_compress_image_packed", "jpegx_host_decompress_plane",
+              "jpegx_entropy_emit", "jpegx_entropy_decode", "jpegx_entropy_decode_status", "jpegx_batch_compress",
+              "jpegx_batch_compress_status", "jpegx_batch_emit", "jpegx_batch_decompress", "jpegx_host_compress_begin", "jpegx_host_compress_image", "jpegx_host_compress_image_packed", "jpegx_host_decompress_plane",
               "jpegx_host_decompress_plane_i64", "jpegx_host_decompress_image", "jpegx_host_entropy_decode_gpu",
               "jpegx_host_pool_release", "jpegx_comm_create_deadline"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
-RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes": _sz}   # everything else returns int
+RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
+            "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
 
 
 def lib():
@@ -842,3 +851,133 @@ def entropy_decode(blob, nblocks):
     check(lib().jpegx_host_entropy_decode(buf.ctypes.data if buf.size else None, buf.size, int(nblocks),
                                           out.ctypes.data), "jpegx_host_entropy_decode")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# batch codec on device buffers: a stack of planes -> one coded stream with a plane index, and back
+# ---------------------------------------------------------------------------------------------
+def batch_workspace_bytes(nplanes, height, width):
+    return lib().jpegx_batch_workspace_bytes(int(nplanes), int(height), int(width))
+
+
+def batch_max_bytes(nplanes, height, width):
+    return lib().jpegx_batch_max_bytes(int(nplanes), int(height), int(width))
+
+
+def batch_decompress_workspace_bytes(nbytes, nplanes, height, width):
+    return lib().jpegx_batch_decompress_workspace_bytes(int(nbytes), int(nplanes), int(height), int(width))
+
+
+def batch_compress_device(in_ptr, elem_size, nplanes, height, width, d_workspace, d_out, out_cap, mode="qtable", param=0.0,
+                          flags=0, pitch=None, block_size=1, stream=None, device=None):
+    """Enqueue jpegx_batch_compress: planes stacked [nplanes * height * block_size][pitch] (height, width after pooling;
+    pitch in elements, default width * block_size) -> coded bytes at d_out (None: sizes only).  Verdict and plane
+    index: batch_compress_status."""
+    args = (in_ptr, int(elem_size), int(nplanes), int(height), int(width), int(width * block_size if pitch is None else pitch),
+            int(block_size), mode_of(mode), float(param), int(flags), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress(*args) if device is None else L.jpegx_batch_compress_on(int(device), *args), "jpegx_batch_compress")
+
+
+def batch_compress_status(d_workspace, nplanes, height, width, stream=None, device=None):
+    """Synchronises; returns (rc, total, offsets): rc 0, 1 (did not fit the capacity of the last compress / emit) or
+    JPEGX_E_INVALID (-1: an amplitude beyond 15 bits); offsets: uint64 (nplanes + 1,), the last one = total."""
+    total = ctypes.c_ulonglong(0)
+    off = np.zeros(int(nplanes) + 1, dtype=np.uint64)
+    args = (d_workspace, int(nplanes), int(height), int(width), ctypes.byref(total), off.ctypes.data, stream)
+    L = lib()
+    rc = L.jpegx_batch_compress_status(*args) if device is None else L.jpegx_batch_compress_status_on(int(device), *args)
+    if rc not in (0, 1, -1):
+        check(rc, "jpegx_batch_compress_status")
+    return rc, total.value, off
+
+
+def batch_emit_device(d_workspace, nplanes, height, width, d_out, out_cap, stream=None, device=None):
+    args = (d_workspace, int(nplanes), int(height), int(width), d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_emit(*args) if device is None else L.jpegx_batch_emit_on(int(device), *args), "jpegx_batch_emit")
+
+
+def batch_decompress_device(d_bytes, plane_offsets, nplanes, height, width, d_workspace, d_out, out_pitch, block_size=1,
+                            mode="qtable", param=0.0, flags=0, out_type=OUT_U8, stream=None, device=None):
+    """jpegx_batch_decompress (synchronises the stream between groups and levels); plane_offsets: nplanes + 1 host
+    integers.  Returns the C return code's success; raises JpegxError otherwise."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(nplanes) + 1,):
+        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    args = (d_bytes, off.ctypes.data, int(nplanes), int(height), int(width), int(block_size), mode_of(mode), float(param),
+            int(flags), d_workspace, d_out, int(out_pitch), int(out_type), stream)
+    L = lib()
+    check(L.jpegx_batch_decompress(*args) if device is None else L.jpegx_batch_decompress_on(int(device), *args), "jpegx_batch_decompress")
+
+
+def batch_compress(planes, block_size=1, mode="qtable", param=0.0, pixel_input=None):
+    """[n][rows][cols] uint8 or float32 planes -> list of n byte strings, each what compress_plane gives for that plane.
+    Host convenience over the device entries (upload, sizes-only compress, status, emit into a buffer of exactly the
+    total, download); float32 planes take block_size 1 only."""
+    src = np.asarray(planes)
+    bs = int(block_size)
+    if src.ndim != 3 or src.shape[0] < 1:
+        raise JpegxError("expected [n][rows][cols] planes, got shape %r" % (src.shape,))
+    if src.dtype != np.uint8:
+        src = np.ascontiguousarray(src, dtype=np.float32)
+    n, hh, ww = src.shape
+    if hh % (8 * bs) or ww % (8 * bs):
+        raise JpegxError("planes must be a multiple of 8*block_size in both dimensions")
+    h, w = hh // bs, ww // bs
+    elem = 1 if src.dtype == np.uint8 else 4
+    flags = 0
+    if elem == 4 and (is_pixel_like(src.reshape(n * hh, ww)) if pixel_input is None else pixel_input):
+        flags = F_PIXEL_INPUT
+    pitch = (ww + 15) // 16 * 16 if elem == 1 else (ww + 3) // 4 * 4
+    a = np.zeros((n * hh, pitch), dtype=src.dtype)
+    a[:, :ww] = src.reshape(n * hh, ww)
+    require_device()
+    din, dws, dout = DeviceBuffer(a.nbytes), DeviceBuffer(batch_workspace_bytes(n, h, w)), None
+    try:
+        din.upload(a)
+        batch_compress_device(din.ptr, elem, n, h, w, dws.ptr, None, 0, mode, param, flags, pitch=pitch, block_size=bs)
+        rc, total, off = batch_compress_status(dws.ptr, n, h, w)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status")
+        dout = DeviceBuffer(max(1, total))
+        batch_emit_device(dws.ptr, n, h, w, dout.ptr, total)
+        rc, total2, off = batch_compress_status(dws.ptr, n, h, w)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit")
+        blob = dout.download((total,), np.uint8)
+        return [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(n)]
+    finally:
+        for b in (din, dws, dout):
+            if b is not None:
+                b.free()
+
+
+def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.0, out="u8"):
+    """n byte strings (one per plane, as batch_compress returns them) -> ndarray [n][height * block_size][width *
+    block_size]; (height, width) = the planes AFTER pooling.  out: "u8" (clamped, replicated block_size x block_size),
+    "i16" or "f32" (block_size 1)."""
+    blobs = [bytes(b) for b in blobs]
+    n, bs = len(blobs), int(block_size)
+    if n < 1:
+        raise JpegxError("expected at least one plane")
+    out_type = _OUT_BY_NAME[out]
+    dtype = np.dtype(_OUT_DTYPES[out_type])
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in blobs])
+    total = int(off[n])
+    stream_bytes = np.zeros(total + 16, dtype=np.uint8)               # 16 zero bytes behind the stream
+    stream_bytes[:total] = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    pitch = (width * bs * dtype.itemsize + 15) // 16 * 16 // dtype.itemsize
+    require_device()
+    din = DeviceBuffer(stream_bytes.nbytes)
+    dws = DeviceBuffer(max(256, batch_decompress_workspace_bytes(total, n, height, width)))
+    dout = DeviceBuffer(n * height * bs * pitch * dtype.itemsize)
+    try:
+        din.upload(stream_bytes)
+        batch_decompress_device(din.ptr, off, n, height, width, dws.ptr, dout.ptr, pitch, bs, mode, param, 0, out_type)
+        res = dout.download((n, height * bs, pitch), dtype)
+        return np.ascontiguousarray(res[:, :, :width * bs])
+    finally:
+        for b in (din, dws, dout):
+            b.free()

@@ -261,6 +261,61 @@ int jpegx_entropy_decode(const uint8_t *d_bytes, size_t nbytes, long long nblock
                          int level, jpegx_stream_t stream);
 int jpegx_entropy_decode_status(const void *d_workspace, jpegx_stream_t stream);
 
+/* ---- batch codec on device buffers: a stack of planes -> one coded byte stream with a plane index, and back ------
+ * For every plane what the reference's compress_band makes of it (pipeline/__init__.py:71-76 for transform 'DCT',
+ * dct_size 8; the entropy stage is pipeline/run_length_encoding.py:47-64 + pipeline/rle_byte_stream.py:48-59), with the
+ * planes' byte strings concatenated and a per-plane index beside them; the way back is decompress_band
+ * (pipeline/__init__.py:79-88; pipeline/rle_byte_stream.py:61-88, pipeline/run_length_encoding.py:66-97).
+ * A batch is `nplanes` planes of equal shape STACKED: one array [nplanes * H * bs][pitch], plane p starting at row
+ * p * H * bs.  H, W: sizes after pooling, multiples of 8 (padding stays the caller's); nplanes * (H/8) * (W/8) <=
+ * 2^31 - 64.  Everything lives in the caller's workspace (16-byte aligned; jpegx_malloc gives more).
+ * Footprints: the workspace is 128 bytes per block (the int16 stream) + jpegx_entropy_workspace_bytes + the index;
+ * jpegx_batch_max_bytes is the worst case of the coded stream, 185 bytes per block (64 x 23 bits + the end marker)
+ * rounded up to 188 + 64 bytes -- several times what pictures need.  The small-footprint road: compress with d_out ==
+ * NULL (sizes only), jpegx_batch_compress_status for the total, jpegx_batch_emit into a buffer of exactly that size
+ * (+ 16 zero bytes behind it if jpegx_batch_decompress is to read it from there).                                   */
+size_t jpegx_batch_workspace_bytes(int nplanes, int H, int W);
+size_t jpegx_batch_max_bytes(int nplanes, int H, int W);
+/* enqueue only: forward (sizing its blocks) -> scan -> plane index -> emit.  elem_size 4: fp32 planes, bs must be 1, any
+ * fp32 values, JPEGX_F_PIXEL_INPUT as for jpegx_forward_fused (pitch in elements, a multiple of 4).  elem_size 1: uint8
+ * planes, bs in {1, 2, 4}, the limits of jpegx_forward_fused_u8 (pitch in bytes, a multiple of 16).  d_out == NULL
+ * (out_cap ignored): sizes only, nothing emitted.  Nothing at all is written to d_out when the stream does not fit
+ * out_cap or an amplitude is beyond 15 bits.                                                                        */
+int jpegx_batch_compress(const void *d_in, int elem_size, int nplanes, int H, int W, ptrdiff_t pitch, int bs,
+                         int mode, double param, unsigned flags, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                         jpegx_stream_t stream);
+/* synchronises the stream.  JPEGX_OK; JPEGX_E_INVALID = BadRleCodeError (util.py:140-149: an amplitude beyond 15 bits) --
+ * nothing was written; 1 = total > out_cap of the last compress / emit on this workspace -- nothing was written,
+ * *h_total says how much is needed.  h_plane_offsets (may be NULL): nplanes + 1 byte offsets, the last one = total;
+ * plane p's bytes are [offset p, offset p + 1).                                                                     */
+int jpegx_batch_compress_status(const void *d_workspace, int nplanes, int H, int W, unsigned long long *h_total,
+                                unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+/* enqueue only: emit from a workspace whose sizes are in place (after a sizes-only or a too-small compress) */
+int jpegx_batch_emit(void *d_workspace, int nplanes, int H, int W, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+
+/* The way back.  d_bytes + plane index (a HOST array of nplanes + 1 offsets, as a container would store it) -> samples,
+ * stacked [nplanes * H * bs][out_pitch].  out_type JPEGX_OUT_U8: the clamp of pipeline/normalization.py:10-14 and
+ * SubSampling.invert (pipeline/subsampling.py:13-14) fused, bs in 1..255; JPEGX_OUT_F32 / _I16: bs must be 1, values as
+ * jpegx_inverse_fused defines them.  d_bytes must be readable for 16 bytes behind the last offset.
+ * NOT enqueue-only: the entropy decoding runs on the device in groups of whole planes (at most 2^20 blocks and 64 MiB
+ * of stream each, one plane at least; a group's bytes are first copied into the workspace), every group through the
+ * level ladder of the host roads (planned segments -> 256-byte segments -> the whole-stream scheme), and the call
+ * SYNCHRONISES THE STREAM after every group and level to read the verdict.  Levels 0 and 1 live in the workspace (256-
+ * byte aligned; about 128 bytes per block and 9 bytes per stream byte of the largest group).  The whole-stream scheme
+ * sizes its scratch from a candidate count read back from the device, so that scratch is the library's: one grow-only
+ * allocation per device (4 bytes x (1 + log4 of the group's blocks) per candidate, a candidate being a block start
+ * or a zero byte: some 3 GiB for a group of 64 MiB of single-byte blocks, a few per cent of that for pictures), taken
+ * only when a group reaches that level, held by one call at a time and freed by jpegx_host_pool_release.
+ * The plane index cuts the stream into groups and tells the caller where a plane's bytes are; offsets INSIDE a group
+ * are not needed by the decoder (blocks are self-delimiting) and are not verified against the block starts it finds.
+ * What is verified: offsets that do not decrease, and that every group's bytes hold exactly its planes' (H/8)(W/8)
+ * well-formed blocks each -- else JPEGX_E_INVALID with the group's first and last plane in the message; planes of
+ * earlier groups have been written by then.                                                                         */
+size_t jpegx_batch_decompress_workspace_bytes(size_t nbytes, int nplanes, int H, int W);
+int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int H, int W,
+                           int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out,
+                           ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -408,6 +463,16 @@ int jpegx_entropy_emit_on(int device, const int16_t *d_zz, long long nblocks, co
 int jpegx_entropy_decode_on(int device, const uint8_t *d_bytes, size_t nbytes, long long nblocks, void *d_workspace,
                             int16_t *d_zz, int level, jpegx_stream_t stream);
 int jpegx_entropy_decode_status_on(int device, const void *d_workspace, jpegx_stream_t stream);
+int jpegx_batch_compress_on(int device, const void *d_in, int elem_size, int nplanes, int H, int W, ptrdiff_t pitch, int bs,
+                            int mode, double param, unsigned flags, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                            jpegx_stream_t stream);
+int jpegx_batch_compress_status_on(int device, const void *d_workspace, int nplanes, int H, int W, unsigned long long *h_total,
+                                   unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+int jpegx_batch_emit_on(int device, void *d_workspace, int nplanes, int H, int W, uint8_t *d_out, size_t out_cap,
+                        jpegx_stream_t stream);
+int jpegx_batch_decompress_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes,
+                              int H, int W, int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out,
+                              ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream);
 int jpegx_host_compress_begin_on(int device, const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
                                  int mode, double param, size_t *nbytes);
 int jpegx_host_compress_image_on(int device, const void *const *h_planes, int nbands, int elem_size, int H, int W,
