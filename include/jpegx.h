@@ -173,7 +173,8 @@ int jpegx_forward_fused_u8(const uint8_t *d_in, int H, int W, ptrdiff_t pitch, i
 
 /* Inverse: replaces ZigzagOrder.invert (zigzag_order.py:101-119) + Quantization.invert
  * (quantization.py:20-30) + BasisChange.invert (basis_change.py:28-43, including its final
- * np.round).  d_in: int16 zigzag stream; d_out: [H][out_pitch] of out_type.                  */
+ * np.round).  d_in: int16 zigzag stream; d_out: [H][out_pitch] of out_type.  JPEGX_OUT_I16
+ * saturates: a sample beyond int16 is stored as -32768 or 32767 (JPEGX_OUT_F32 holds it exactly). */
 int jpegx_inverse_fused(const int16_t *d_in, int H, int W, int mode, double param, unsigned flags,
                         void *d_out, ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream);
 

@@ -86,8 +86,9 @@ int emul_forward(const float *in, int H, int W, int mode, double param, const fl
     return 0;
 }
 
-// inverse: int16 zigzag -> rounded int32 plane (unclamped), same two-tier logic
-int emul_inverse(const int16_t *in, int H, int W, int mode, double param, int32_t *out, double *stats)
+// inverse: int16 zigzag -> rounded int32 plane (unclamped), same two-tier logic.  rowmask (optional): per block, in
+// stream order, bit r set when output row r of the block holds a flagged sample -- the kernel's unit of exact work
+int emul_inverse_rows(const int16_t *in, int H, int W, int mode, double param, int32_t *out, double *stats, uint8_t *rowmask)
 {
     int wb = W / 8;
     long nflag = 0, nblkflag = 0;
@@ -132,13 +133,19 @@ int emul_inverse(const int16_t *in, int H, int W, int mode, double param, int32_
                 float r = rintf(v[n]);
                 int flag = !((fabsf(v[n] - r) + E) < JPEGX_SAFE_HALF);
                 int res = flag ? (int)rint(y64[n]) : (int)r;
-                if (flag) { ++nflag; blkflag = 1; }
+                if (flag) { ++nflag; blkflag |= 1 << (n >> 3); }
                 out[(size_t)(by * 8 + (n >> 3)) * W + bx * 8 + (n & 7)] = res;
             }
-            nblkflag += blkflag;
+            if (rowmask) rowmask[(size_t)by * wb + bx] = (uint8_t)blkflag;
+            nblkflag += blkflag != 0;
         }
     if (stats) { stats[0] = (double)nflag; stats[1] = (double)nblkflag; stats[2] = maxratio; }
     return 0;
+}
+
+int emul_inverse(const int16_t *in, int H, int W, int mode, double param, int32_t *out, double *stats)
+{
+    return emul_inverse_rows(in, H, W, mode, param, out, stats, nullptr);
 }
 
 }  // extern "C"
