@@ -31,6 +31,8 @@ F_TUNE_NO_NT = 0x100
 F_TUNE_NO_STRIP = 0x200
 F_TUNE_SKIP_EXACT = 0x400
 F_TUNE_WAVE_PER_BLOCK = 0x800
+F_TUNE_POOL_ROWS_LO = 0x1000
+F_TUNE_POOL_ROWS_HI = 0x2000
 F_TUNE_XCD_CONTIG = 0x10000
 F_TUNE_NO_XCD_CONTIG = 0x20000
 F_TUNE_COLUMN_UNITS = 0x40000
@@ -341,15 +343,17 @@ def _plane(a, dtype):
     return a
 
 
-def is_pixel_like(a):
-    """True when every sample is a non-negative multiple of 2^-8 below 2^9 (JPEGX_F_PIXEL_INPUT)."""
+def is_pixel_like(a, block_size=1):
+    """True when the plane keeps the promise of JPEGX_F_PIXEL_INPUT (include/jpegx.h): every sample a non-negative
+    multiple of 2^-8, at most 255; for a plane that is mean-pooled on load (block_size 2, 4): every sample an integer
+    0 .. 255."""
     a = np.asarray(a)
     if a.size == 0:
         return False
     if a.dtype.kind in "ui":
-        return bool(a.min() >= 0 and a.max() < 512)
-    s = a * 256.0
-    return bool(np.all(a >= 0) and np.all(a < 512) and np.all(s == np.rint(s)))
+        return bool(a.min() >= 0 and a.max() <= 255)
+    s = a * 256.0 if int(block_size) == 1 else a
+    return bool(np.all(a >= 0) and np.all(a <= 255) and np.all(s == np.rint(s)))
 
 
 def forward_fused(plane, mode="qtable", param=0.0, pixel_input=None, flags_extra=0):
@@ -405,7 +409,7 @@ def forward_fused_pooled(plane, block_size, mode="qtable", param=0.0, pixel_inpu
         raise JpegxError("pooled plane must be a multiple of 8*block_size in both dimensions")
     h, w = hh // bs, ww // bs
     if pixel_input is None:
-        pixel_input = is_pixel_like(a)
+        pixel_input = is_pixel_like(a, bs)
     out = np.empty((h // 8, w // 8, 64), dtype=np.int16)
     din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(out.nbytes)
     try:
@@ -782,7 +786,7 @@ def compress_plane(plane, block_size=1, mode="qtable", param=0.0):
         if as_u8:
             forward_fused_u8_device(din.ptr, h, w, dzz.ptr, mode, param, 0, pitch=ww, pool=bs)
         else:
-            forward_fused_device(din.ptr, h, w, dzz.ptr, mode, param, F_PIXEL_INPUT if is_pixel_like(a) else 0,
+            forward_fused_device(din.ptr, h, w, dzz.ptr, mode, param, F_PIXEL_INPUT if is_pixel_like(a, bs) else 0,
                                  pitch=ww, pool=bs)
         check(L.jpegx_entropy_sizes(dzz.ptr, nblocks, dws.ptr, None), "jpegx_entropy_sizes")
         total = ctypes.c_ulonglong(0)

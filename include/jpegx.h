@@ -51,9 +51,14 @@ typedef enum jpegx_quant_mode {
 } jpegx_quant_mode;
 
 /* flags for the fused kernels */
-#define JPEGX_F_PIXEL_INPUT 1u /* forward: every sample is a non-negative multiple of 2^-8 below 2^9  \
-                                  (8-bit pixels, or their 2x2/4x4 means), so partial sums are exact   \
-                                  in fp32; lets the kernel use DC as the error-bound scale            */
+#define JPEGX_F_PIXEL_INPUT 1u /* forward: every sample is a non-negative multiple of 2^-8, at most 255      \
+                                  (8-bit pixels, or their 2x2/4x4 means), so partial sums are exact in fp32   \
+                                  and |coefficient| <= 16320; lets the kernel use DC as the error-bound scale \
+                                  and pack without saturating.  Entries that mean-pool on load (bs 2, 4;      \
+                                  jpegx_forward_fused_pooled, _planes): every RAW sample is an integer        \
+                                  0..255 -- tile means of finer samples need more bits than the fp16 copies   \
+                                  and the fp32 sums of the pooled kernels hold.  A plane that breaks the      \
+                                  promise is transformed correctly WITHOUT the flag                           */
 #define JPEGX_F_CLAMP_U8 2u    /* inverse: fuse the clamp to [0,255] of pipeline/normalization.py:10-14 */
 /* tuning switches (A/B measurements in one process; results are identical either way) */
 #define JPEGX_F_TUNE_NO_NT 0x100u /* use the default cache policy instead of nontemporal accesses */

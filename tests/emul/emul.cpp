@@ -23,8 +23,14 @@ double emul_aan_g(int k) { static const double G[8] = {JPEGX_AAN_G}; return G[k]
 
 // stats[0] = flagged coefficients, stats[1] = blocks with >=1 flag,
 // stats[2] = max over coefficients of observed |t32 - t64| / (E F / q), the kernel's per-coefficient bound
-int emul_forward(const float *in, int H, int W, int mode, double param, const float *rq32,
-                 int pixel_input, int dc_exact, int16_t *out, float *out_dct32, double *stats)
+// in64 (optional): the samples the exact tier works on when they are not the fp32 ones -- the float64 tile means of a
+// pooled plane (np.mean: float64 sum, one division), where `in` holds the kernel's fp32 tile means.  efactor: the factor
+// on E of the pooled generic kernels, 1 + BS^2 / 16 (forward_fused_body), 1 everywhere else.  colmask / zzmask
+// (optional): per block, in stream order, bit l set when a coefficient (t, l) of column l is flagged -- the unit of the
+// column-wise exact tier (quantise_zigzag_pack_cols) -- and bit p set when zigzag position p is flagged.
+int emul_forward_masks(const float *in, const double *in64, int H, int W, int mode, double param, const float *rq32,
+                       int pixel_input, int dc_exact, float efactor, int16_t *out, float *out_dct32, double *stats,
+                       uint8_t *colmask, uint64_t *zzmask)
 {
     double rq64[64];
     for (int n = 0; n < 64; ++n) rq64[n] = 1.0 / (double)T_QT[n];
@@ -39,12 +45,13 @@ int emul_forward(const float *in, int H, int W, int mode, double param, const fl
             for (int i = 0; i < 8; ++i)
                 for (int j = 0; j < 8; ++j) {
                     float x = in[(size_t)(by * 8 + i) * W + bx * 8 + j];
-                    v[i * 8 + j] = x; a[i * 8 + j] = (double)x;
+                    v[i * 8 + j] = x;
+                    a[i * 8 + j] = in64 ? in64[(size_t)(by * 8 + i) * W + bx * 8 + j] : (double)x;
                     S += fabsf(x);
                 }
             jpegx_dct8x8_aan_f32(v);                 // scaled: v[k*8+l] = g_k g_l * coefficient (k, l)
             if (pixel_input) S = v[0];
-            const float E = jpegx_fwd_err_unit(S);
+            const float E = jpegx_fwd_err_unit(S) * efactor;
             // exact tier for everything (for statistics only)
             double m[64], y64[64];
             for (int i = 0; i < 8; ++i)
@@ -53,6 +60,8 @@ int emul_forward(const float *in, int H, int W, int mode, double param, const fl
                 for (int l = 0; l < 8; ++l) y64[k * 8 + l] = jpegx_dot8_ref(&T_C[k * 8], &m[l], 8);
             int16_t *o = out + ((size_t)by * wb + bx) * 64;
             int blkflag = 0;
+            unsigned cols = 0;
+            uint64_t zzs = 0;
             for (int p = 0; p < 64; ++p) {
                 int n = T_ZZ[p];
                 static const double G[8] = {JPEGX_AAN_G};
@@ -74,6 +83,8 @@ int emul_forward(const float *in, int H, int W, int mode, double param, const fl
                 int res;
                 if (flag) {
                     ++nflag; blkflag = 1;
+                    cols |= 1u << (n & 7);
+                    zzs |= (uint64_t)1 << p;
                     res = jpegx_clamp_i16(jpegx_quant_ref(y64[n], n, mode, param, rq64));
                 } else {
                     res = jpegx_clamp_i16((double)r);
@@ -81,9 +92,17 @@ int emul_forward(const float *in, int H, int W, int mode, double param, const fl
                 o[p] = (int16_t)res;
             }
             nblkflag += blkflag;
+            if (colmask) colmask[(size_t)by * wb + bx] = (uint8_t)cols;
+            if (zzmask) zzmask[(size_t)by * wb + bx] = zzs;
         }
     if (stats) { stats[0] = (double)nflag; stats[1] = (double)nblkflag; stats[2] = maxratio; }
     return 0;
+}
+
+int emul_forward(const float *in, int H, int W, int mode, double param, const float *rq32,
+                 int pixel_input, int dc_exact, int16_t *out, float *out_dct32, double *stats)
+{
+    return emul_forward_masks(in, nullptr, H, W, mode, param, rq32, pixel_input, dc_exact, 1.0f, out, out_dct32, stats, nullptr, nullptr);
 }
 
 // inverse: int16 zigzag -> rounded int32 plane (unclamped), same two-tier logic.  rowmask (optional): per block, in

@@ -298,7 +298,9 @@ def test_device_api_with_pitch_stream_and_events(gpu):
 
 
 def test_exact_tier_census_counters(gpu):
-    """jpegx_set_debug_counters reports how many blocks took the float64 tier (3-4 % on noise)."""
+    """jpegx_set_debug_counters reports how many blocks took the float64 tier (3-4 % on noise).  The exact census --
+    the kernels' count against the emulator's, block for block of constructed planes -- is in
+    tests/test_gpu_forward_adversarial.py."""
     import ctypes
     L = gpu.lib()
     h = w = 1024
