@@ -8,7 +8,9 @@
 //
 // Replaces, for 8-bit bands with transform 'DCT' / dct_size 8, the loops of pipeline/__init__.py:71-76,
 // 79-88 (one band) and :102-124 (Jpeg.compress / Jpeg.decompress: Y, Cb, Cr one after another) of the
-// reference; step 0 padding stays with the caller.
+// reference.  The _ragged entries take a band of any rows x cols: it is uploaded into a device plane of the padded shape
+// and the margins are filled there (jpegx_pad_edges: steps 0 and 2, pipeline/padding.py:8-12 + pipeline/dct_padding.py:8-9);
+// the entries without that suffix are the same job with rows = H * bs, cols = W * bs -- no margin, no extra launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -206,8 +208,9 @@ int ensure_streams(DevicePool *pool, bool image)
 // k, then of strip k + 1), the calling thread waits for a strip's last share and enqueues its copy, so only the last
 // strip's copy is not hidden behind the narrowing of the next.  What the narrowing costs is reading the wide array:
 // 128 MiB for a 4096^2 int64 band, ~13 ms on one core (JPEGX_NARROW_THREADS, default 8).
+// The device rows are `dst_pitch` bytes apart (the padded row of a ragged band; W for a band of whole tiles).
 template <typename T>
-int narrow_and_upload(const T *src, ptrdiff_t src_pitch, int H, int W, uint8_t *stage, void *d_dst, hipStream_t st)
+int narrow_and_upload(const T *src, ptrdiff_t src_pitch, int H, int W, uint8_t *stage, void *d_dst, ptrdiff_t dst_pitch, hipStream_t st)
 {
     const unsigned hw = std::thread::hardware_concurrency();
     static const int want = [] { const char *e = getenv("JPEGX_NARROW_THREADS"); return e && *e ? atoi(e) : 8; }();      // 8 / 16 / 32: 1.26-1.57 / 1.38-1.99 / 1.33-1.94 ms per int64 band (starting the threads costs more than sixteen gain)
@@ -244,7 +247,9 @@ int narrow_and_upload(const T *src, ptrdiff_t src_pitch, int H, int W, uint8_t *
         while (done[k].load(std::memory_order_acquire) < nthreads) __builtin_ia32_pause();
         const int r0 = rows_of(k), r1 = rows_of(k + 1);
         if (e == hipSuccess && r1 > r0)
-            e = hipMemcpyAsync(static_cast<uint8_t *>(d_dst) + (size_t)r0 * W, stage + (size_t)r0 * W, (size_t)(r1 - r0) * W, hipMemcpyHostToDevice, st);
+            e = dst_pitch == W
+                ? hipMemcpyAsync(static_cast<uint8_t *>(d_dst) + (size_t)r0 * W, stage + (size_t)r0 * W, (size_t)(r1 - r0) * W, hipMemcpyHostToDevice, st)
+                : hipMemcpy2DAsync(static_cast<uint8_t *>(d_dst) + (size_t)r0 * dst_pitch, (size_t)dst_pitch, stage + (size_t)r0 * W, (size_t)W, (size_t)W, (size_t)(r1 - r0), hipMemcpyHostToDevice, st);
     }
     for (auto &t : th) t.join();
     if (!ok) {
@@ -316,29 +321,34 @@ struct BackgroundTouch {
     void wait() { if (t.joinable()) t.join(); }
 };
 
-int check_compress_shape(const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs)
+// rows x cols: the band as the caller holds it, at most (H * bs) x (W * bs); `ragged`: an entry that pads on the device
+int check_compress_shape(const void *h_plane, int elem_size, int H, int W, int rows, int cols, ptrdiff_t pitch, int bs, bool ragged)
 {
     if (!h_plane) return fail(JPEGX_E_INVALID, "null pointer");
     if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "host_compress supports block_size 1..255");
     if (H <= 0 || W <= 0 || (H % 8) || (W % 8)) return fail(JPEGX_E_INVALID, "plane height and width (after pooling) must be positive multiples of 8");
     if ((long long)(H / 8) * (W / 8) > 0x7FFFFFC0LL) return fail(JPEGX_E_INVALID, "more than 2^31 blocks in one plane");
     if (elem_size != 1 && elem_size != 4 && elem_size != 8) return fail(JPEGX_E_UNSUPPORTED, "host_compress takes uint8, int32 or int64 samples");
-    if (pitch < (ptrdiff_t)W * bs) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if (rows < 1 || cols < 1 || rows > (long long)H * bs || cols > (long long)W * bs) return fail(JPEGX_E_INVALID, "band larger than its padded plane");
+    if (pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
     const bool fused_pool = bs == 1 || bs == 2 || bs == 4;
-    if (fused_pool && ((W * bs) % 16) != 0) return fail(JPEGX_E_UNSUPPORTED, "host_compress needs rows of a multiple of 16 samples");
+    // a ragged band whose padded row is 8 mod 16 (block_size 1 only) takes the float64 road in enqueue_front
+    if (!ragged && fused_pool && ((W * bs) % 16) != 0) return fail(JPEGX_E_UNSUPPORTED, "host_compress needs rows of a multiple of 16 samples");
     return JPEGX_OK;
 }
 
-// Steps 1 + 4..7 of one band enqueued on `st`: upload (narrowing wide integers through `stage`, pinned), fused
+// Steps 0..7 of one band enqueued on `st`: upload of rows x cols samples (narrowing wide integers through `stage`,
+// pinned) into a device plane of the padded shape [H * bs][W * bs], the margin fill when there is a margin, fused
 // forward (uint8 kernels for block_size 1, 2, 4; mean-pool + all-float64 forward otherwise), sizes + scans.
 // Afterwards the 16-byte head of slot.d_ws holds the total byte count and the error flag.
-int enqueue_front(DevicePool *pool, BandSlot &slot, uint8_t *stage, const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch,
-                  int bs, int mode, double param, hipStream_t st)
+int enqueue_front(DevicePool *pool, BandSlot &slot, uint8_t *stage, const void *h_plane, int elem_size, int H, int W, int rows, int cols,
+                  ptrdiff_t pitch, int bs, int mode, double param, hipStream_t st)
 {
     const int HH = H * bs, WW = W * bs;
     const size_t in_bytes = (size_t)HH * WW;
     const long long nblocks = (long long)(H / 8) * (W / 8);
-    const bool fused_pool = bs == 1 || bs == 2 || bs == 4;   // uint8 kernels with the mean folded in; else pool to float64 first
+    // uint8 kernels with the mean folded in (rows of a multiple of 16 bytes); else pool to float64 first
+    const bool fused_pool = (bs == 1 || bs == 2 || bs == 4) && (WW % 16) == 0;
     int rc;
     if ((rc = slot.d_in.ensure(in_bytes)) || (rc = slot.d_zz.ensure((size_t)nblocks * 128)) ||
         (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes(nblocks))))
@@ -350,15 +360,17 @@ int enqueue_front(DevicePool *pool, BandSlot &slot, uint8_t *stage, const void *
     } else if (elem_size != 1) {
         // wide integers: narrowed into the pinned staging area strip by strip, every strip on its way to the device while
         // the next is narrowed
-        rc = elem_size == 8 ? narrow_and_upload(static_cast<const int64_t *>(h_plane), pitch, HH, WW, stage, slot.d_in.p, st)
-                            : narrow_and_upload(static_cast<const int32_t *>(h_plane), pitch, HH, WW, stage, slot.d_in.p, st);
+        rc = elem_size == 8 ? narrow_and_upload(static_cast<const int64_t *>(h_plane), pitch, rows, cols, stage, slot.d_in.p, WW, st)
+                            : narrow_and_upload(static_cast<const int32_t *>(h_plane), pitch, rows, cols, stage, slot.d_in.p, WW, st);
         if (rc) return rc;
     } else {
-        hipError_t e = (src_pitch == WW)
-            ? hipMemcpyAsync(slot.d_in.p, src8, in_bytes, hipMemcpyHostToDevice, st)
-            : hipMemcpy2DAsync(slot.d_in.p, WW, src8, (size_t)src_pitch, WW, HH, hipMemcpyHostToDevice, st);
+        hipError_t e = (src_pitch == WW && cols == WW)
+            ? hipMemcpyAsync(slot.d_in.p, src8, (size_t)rows * WW, hipMemcpyHostToDevice, st)
+            : hipMemcpy2DAsync(slot.d_in.p, WW, src8, (size_t)src_pitch, cols, rows, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
     }
+    // steps 0 and 2 in place: returns without a launch when rows x cols is the padded shape already
+    if ((rc = jpegx_pad_edges(slot.d_in.p, 1, 1, rows, cols, bs, WW, st))) return rc;
     if (fused_pool) {
         // the forward kernel sizes its blocks from the registers (RunLengthEncoding's bit counts): no second pass over the
         // stream, and the scan that follows writes the workspace's head itself -- two launches, no memset
@@ -424,11 +436,18 @@ int head_verdict(const unsigned long long *head, unsigned long long *total)
 
 extern "C" {
 
-int jpegx_host_compress_begin(const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs, int mode,
-                              double param, size_t *nbytes)
+// rows / cols of a band that fills its padded plane: n * bs (0 -- refused by check_compress_shape, which names the bad argument
+// first -- when that is no valid size)
+static int whole_tiles(int n, int bs)
+{
+    return (n > 0 && bs >= 1 && bs <= 255 && (long long)n * bs <= 0x7FFFFFFFLL) ? n * bs : 0;
+}
+
+static int compress_begin_impl(const void *h_plane, int elem_size, int H, int W, int rows, int cols, ptrdiff_t pitch, int bs, int mode,
+                               double param, size_t *nbytes, bool ragged)
 {
     if (!nbytes) return fail(JPEGX_E_INVALID, "null pointer");
-    int rc = check_compress_shape(h_plane, elem_size, H, W, pitch, bs);
+    int rc = check_compress_shape(h_plane, elem_size, H, W, rows, cols, pitch, bs, ragged);
     if (rc) return rc;
     DevicePool *pool = nullptr;
     if ((rc = lock_pool(&pool))) return rc;
@@ -442,7 +461,7 @@ int jpegx_host_compress_begin(const void *h_plane, int elem_size, int H, int W, 
     // the sizes pass flagged an amplitude.  Its destination is therefore sized for the worst case (185 bytes per block).
     const long long nblocks = (long long)(H / 8) * (W / 8);
     if ((rc = slot.d_out.ensure((size_t)nblocks * 188 + 64)) || (rc = pool->h_head.ensure(16 * MAX_BANDS))) return bail(rc);
-    if ((rc = enqueue_front(pool, slot, static_cast<uint8_t *>(pool->h_in.p), h_plane, elem_size, H, W, pitch, bs, mode, param, st)))
+    if ((rc = enqueue_front(pool, slot, static_cast<uint8_t *>(pool->h_in.p), h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, st)))
         return bail(rc);
     unsigned long long *head = static_cast<unsigned long long *>(pool->h_head.p);
     if (hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(pool->ev[0], st) != hipSuccess) {
@@ -458,6 +477,28 @@ int jpegx_host_compress_begin(const void *h_plane, int elem_size, int H, int W, 
     pool->out_bytes = (size_t)total;
     *nbytes = (size_t)total;
     return JPEGX_OK;                       // the pool stays locked (and t_held set) until _finish / _abort
+}
+
+// H, W of the padded plane of a rows x cols band (jpegx_padded_shape), with the checks the ragged entries share
+static int ragged_shape(int rows, int cols, int bs, int *H, int *W)
+{
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "host_compress supports block_size 1..255");
+    return jpegx_padded_shape(rows, cols, bs, H, W);
+}
+
+int jpegx_host_compress_begin(const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs, int mode,
+                              double param, size_t *nbytes)
+{
+    return compress_begin_impl(h_plane, elem_size, H, W, whole_tiles(H, bs), whole_tiles(W, bs), pitch, bs, mode, param, nbytes, false);
+}
+
+int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int mode,
+                                     double param, size_t *nbytes)
+{
+    int H = 0, W = 0;
+    const int rc = ragged_shape(rows, cols, bs, &H, &W);
+    if (rc) return rc;
+    return compress_begin_impl(h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, nbytes, true);
 }
 
 int jpegx_host_compress_finish(uint8_t *h_out)
@@ -496,20 +537,20 @@ int jpegx_host_compress_abort(void)
 // destination's pages are touched by a few host threads (fresh memory: the kernel hands out zeroed pages one fault
 // at a time, which costs more than the copy itself) while the emit kernels run, then every band's bytes are
 // copied from the device straight to their place.
-static int compress_image_impl(const void *const *h_planes, const uint8_t *h_packed, int nbands, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
-                               int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes,
-                               jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+static int compress_image_impl(const void *const *h_planes, const uint8_t *h_packed, int nbands, int elem_size, int H, int W, int rows, int cols,
+                               bool ragged, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len,
+                               int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes)
 {
     if ((!h_planes && !h_packed) || !alloc || !nbytes || (prefix_len && !prefix)) return fail(JPEGX_E_INVALID, "null pointer");
     if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "compress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
     int rc;
     if (h_packed) {
-        if ((rc = check_compress_shape(h_packed, 1, H, W, (ptrdiff_t)W * bs, bs))) return rc;
-        if (pitch < (ptrdiff_t)W * bs * nbands) return fail(JPEGX_E_INVALID, "packed pitch smaller than a row of pixels");
-        if ((long long)H * bs > 65535) return fail(JPEGX_E_UNSUPPORTED, "packed pixels: more than 65535 rows");
+        if ((rc = check_compress_shape(h_packed, 1, H, W, rows, cols, (ptrdiff_t)cols, bs, ragged))) return rc;
+        if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "packed pitch smaller than a row of pixels");
+        if (rows > 65535) return fail(JPEGX_E_UNSUPPORTED, "packed pixels: more than 65535 rows");
     } else {
         for (int k = 0; k < nbands; ++k)
-            if ((rc = check_compress_shape(h_planes[k], elem_size, H, W, pitch, bs))) return rc;
+            if ((rc = check_compress_shape(h_planes[k], elem_size, H, W, rows, cols, pitch, bs, ragged))) return rc;
     }
     PoolLock lock;
     if (lock.rc) return lock.rc;
@@ -525,8 +566,8 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
     tr.mark("compress_image: pool ready");
     if (h_packed) {
         // [rows][cols][nbands] pixels (what np.asarray(image) gives: half the host time of image.split() + one array per
-        // band): one upload, the planes made on the device, then the bands as below without their own uploads
-        const int rows = H * bs, cols = W * bs;
+        // band): one upload, the planes made on the device (rows of the padded pitch; enqueue_front fills the margins),
+        // then the bands as below without their own uploads
         const size_t row_bytes = (size_t)cols * nbands;
         if ((rc = pool->d_packed.ensure((size_t)rows * row_bytes))) return rc;
         void *planes[MAX_BANDS] = {};
@@ -538,7 +579,7 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
             ? hipMemcpyAsync(pool->d_packed.p, h_packed, (size_t)rows * row_bytes, hipMemcpyHostToDevice, pool->aux[0])
             : hipMemcpy2DAsync(pool->d_packed.p, row_bytes, h_packed, (size_t)pitch, row_bytes, (size_t)rows, hipMemcpyHostToDevice, pool->aux[0]);
         if (e != hipSuccess) { drain(); return fail(JPEGX_E_HIP, "host to device copy failed"); }
-        if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, cols, pool->aux[0]))) { drain(); return rc; }
+        if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, (ptrdiff_t)W * bs, pool->aux[0]))) { drain(); return rc; }
         if (hipEventRecord(pool->ev_x, pool->aux[0]) != hipSuccess || hipStreamWaitEvent(pool->aux[1], pool->ev_x, 0) != hipSuccess) {
             drain();
             return fail(JPEGX_E_HIP, "event between the image job's streams failed");
@@ -548,7 +589,7 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
     for (int k = 0; k < nbands; ++k) {
         hipStream_t st = pool->aux[k & 1];
         uint8_t *stage = (!h_packed && elem_size != 1) ? static_cast<uint8_t *>(pool->h_in.p) + in_bytes * k : nullptr;
-        rc = enqueue_front(pool, pool->slot[k], stage, h_packed ? nullptr : h_planes[k], h_packed ? 1 : elem_size, H, W, pitch, bs, mode, param, st);
+        rc = enqueue_front(pool, pool->slot[k], stage, h_packed ? nullptr : h_planes[k], h_packed ? 1 : elem_size, H, W, rows, cols, pitch, bs, mode, param, st);
         if (!rc && hipMemcpyAsync(heads + 2 * k, pool->slot[k].d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess)
             rc = fail(JPEGX_E_HIP, "device to host copy failed");
         if (!rc && hipEventRecord(pool->ev[k], st) != hipSuccess) rc = fail(JPEGX_E_HIP, "hipEventRecord failed");
@@ -603,7 +644,20 @@ int jpegx_host_compress_image(const void *const *h_planes, int nbands, int elem_
                               jpegx_alloc_fn alloc, void *user, size_t *nbytes)
 {
     if (!h_planes) return fail(JPEGX_E_INVALID, "null pointer");
-    return compress_image_impl(h_planes, nullptr, nbands, elem_size, H, W, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes);
+    return compress_image_impl(h_planes, nullptr, nbands, elem_size, H, W, whole_tiles(H, bs), whole_tiles(W, bs), false, pitch, bs, mode, param,
+                               prefix, prefix_len, length_prefixes, alloc, user, nbytes);
+}
+
+int jpegx_host_compress_image_ragged(const void *const *h_planes, int nbands, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs,
+                                     int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes,
+                                     jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+{
+    if (!h_planes) return fail(JPEGX_E_INVALID, "null pointer");
+    int H = 0, W = 0;
+    const int rc = ragged_shape(rows, cols, bs, &H, &W);
+    if (rc) return rc;
+    return compress_image_impl(h_planes, nullptr, nbands, elem_size, H, W, rows, cols, true, pitch, bs, mode, param, prefix, prefix_len,
+                               length_prefixes, alloc, user, nbytes);
 }
 
 // the same from pixel-interleaved samples, [H * bs][W * bs][nbands] uint8 with rows `pitch` bytes apart (np.asarray(image))
@@ -612,7 +666,21 @@ int jpegx_host_compress_image_packed(const uint8_t *h_pixels, int nbands, int H,
                                      jpegx_alloc_fn alloc, void *user, size_t *nbytes)
 {
     if (!h_pixels) return fail(JPEGX_E_INVALID, "null pointer");
-    return compress_image_impl(nullptr, h_pixels, nbands, 1, H, W, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes);
+    return compress_image_impl(nullptr, h_pixels, nbands, 1, H, W, whole_tiles(H, bs), whole_tiles(W, bs), false, pitch, bs, mode, param,
+                               prefix, prefix_len, length_prefixes, alloc, user, nbytes);
+}
+
+// the same from [rows][cols][nbands] pixels of any size
+int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs,
+                                            int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes,
+                                            jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+{
+    if (!h_pixels) return fail(JPEGX_E_INVALID, "null pointer");
+    int H = 0, W = 0;
+    const int rc = ragged_shape(rows, cols, bs, &H, &W);
+    if (rc) return rc;
+    return compress_image_impl(nullptr, h_pixels, nbands, 1, H, W, rows, cols, true, pitch, bs, mode, param, prefix, prefix_len,
+                               length_prefixes, alloc, user, nbytes);
 }
 
 }  // extern "C"

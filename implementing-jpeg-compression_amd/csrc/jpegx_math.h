@@ -367,6 +367,28 @@ JPEGX_HD int jpegx_clamp_i16(double r)
 }
 
 // ---------------------------------------------------------------------------------------------
+// edge padding as a gather (pipeline/padding.py:8-12 + pipeline/dct_padding.py:8-9, both util.pad_array, util.py:17-41):
+// Padding replicates the last raw sample up to a multiple of block_size, DCTPadding the last POOLED sample up to a
+// multiple of 8 -- and a replicated pooled sample is the mean of a replicated bs x bs tile of raw samples.  Per axis
+// of n samples: P = ceil(n / bs) pooled samples, padded raw extent ceil(P / 8) * 8 * bs, and the raw sample that
+// belongs at padded position x is the one at jpegx_edge_src(x, n, bs).  jpegx/__init__.py edge_source_indices is the
+// NumPy twin; the host code that sizes buffers and the margin-fill kernel (jpegx_pad.hip) both come here.
+// ---------------------------------------------------------------------------------------------
+JPEGX_HD long long jpegx_pooled_extent(int n, int bs)       // samples after pooling and DCT padding: a multiple of 8
+{
+    const long long P = ((long long)n + bs - 1) / bs;
+    return (P + 7) / 8 * 8;
+}
+
+JPEGX_HD int jpegx_edge_src(int x, int n, int bs)
+{
+    const int P = (n + bs - 1) / bs;
+    const int q = x / bs;
+    const int s = (q < P - 1 ? q : P - 1) * bs + (x - q * bs);
+    return s < n - 1 ? s : n - 1;
+}
+
+// ---------------------------------------------------------------------------------------------
 // synthetic planes (jpegx/synth.py is the host twin)
 // ---------------------------------------------------------------------------------------------
 JPEGX_HD uint32_t jpegx_hash32(uint32_t x)

@@ -88,3 +88,11 @@ JPEGX_ON(jpegx_host_decompress_image, (int device, const uint8_t *const *h_bytes
 JPEGX_ON(jpegx_host_entropy_decode_gpu, (int device, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz), (h_bytes, nbytes, nblocks, h_zz))
 JPEGX_ON(jpegx_host_pool_release, (int device), ())
 JPEGX_ON(jpegx_comm_create_deadline, (int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128, double timeout_s), (comm, nranks, rank, id128, timeout_s))
+JPEGX_ON(jpegx_pad_edges, (int device, void *d_planes, int elem_size, int nplanes, int rows, int cols, int bs, ptrdiff_t pitch, jpegx_stream_t stream),
+         (d_planes, elem_size, nplanes, rows, cols, bs, pitch, stream))
+JPEGX_ON(jpegx_host_compress_begin_ragged, (int device, const void *h_plane, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param, size_t *nbytes),
+         (h_plane, elem_size, rows, cols, pitch, bs, mode, param, nbytes))
+JPEGX_ON(jpegx_host_compress_image_ragged, (int device, const void *const *h_planes, int nbands, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
+         (h_planes, nbands, elem_size, rows, cols, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
+JPEGX_ON(jpegx_host_compress_image_packed_ragged, (int device, const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
+         (h_pixels, nbands, rows, cols, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))

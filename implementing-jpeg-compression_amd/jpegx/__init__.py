@@ -126,6 +126,11 @@ SIGNATURES = {
     "jpegx_host_compress_image": [_vp, _int, _int, _int, _int, _pd, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
     "jpegx_host_decompress_image": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _int, _dbl, _vp, _pd, _int, _int, _int],
     "jpegx_host_compress_image_packed": [_vp, _int, _int, _int, _pd, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
+    "jpegx_padded_shape": [_int, _int, _int, _c.POINTER(_int), _c.POINTER(_int)],
+    "jpegx_pad_edges": [_vp, _int, _int, _int, _int, _int, _pd, _vp],
+    "jpegx_host_compress_begin_ragged": [_vp, _int, _int, _int, _pd, _int, _int, _dbl, _c.POINTER(_sz)],
+    "jpegx_host_compress_image_ragged": [_vp, _int, _int, _int, _int, _pd, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
+    "jpegx_host_compress_image_packed_ragged": [_vp, _int, _int, _int, _pd, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
     "jpegx_interleave_u8": [_vp, _int, _int, _int, _pd, _vp, _pd, _vp],
     "jpegx_deinterleave_u8": [_vp, _pd, _int, _int, _int, _vp, _pd, _vp],
     "jpegx_entropy_workspace_bytes": [_c.c_longlong],
@@ -161,7 +166,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_entropy_emit", "jpegx_entropy_decode", "jpegx_entropy_decode_status", "jpegx_batch_compress",
               "jpegx_batch_compress_status", "jpegx_batch_emit", "jpegx_batch_decompress", "jpegx_host_compress_begin", "jpegx_host_compress_image", "jpegx_host_compress_image_packed", "jpegx_host_decompress_plane",
               "jpegx_host_decompress_plane_i64", "jpegx_host_decompress_image", "jpegx_host_entropy_decode_gpu",
-              "jpegx_host_pool_release", "jpegx_comm_create_deadline"):
+              "jpegx_host_pool_release", "jpegx_comm_create_deadline", "jpegx_pad_edges", "jpegx_host_compress_begin_ragged",
+              "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
@@ -615,6 +621,49 @@ def forward_u8_block_sizes(plane, block_size=1, mode="qtable", param=0.0):
         dws.free()
 
 
+def padded_shape(rows, cols, block_size=1):
+    """(H, W) of a rows x cols band after pooling and DCT padding, both multiples of 8 (jpegx_padded_shape; host
+    arithmetic, no device needed): the padded raw plane is (H * block_size, W * block_size)."""
+    h, w = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().jpegx_padded_shape(int(rows), int(cols), int(block_size), ctypes.byref(h), ctypes.byref(w)), "jpegx_padded_shape")
+    return h.value, w.value
+
+
+def edge_source_indices(n, block_size=1):
+    """The written specification of jpegx_pad_edges for one axis of n samples: the int64 vector src of length N such
+    that padded[x] = band[src[x]], where P = ceil(n / bs) is the number of pooled samples, N = ceil(P / 8) * 8 * bs the
+    padded raw extent and src[x] = min(min(x // bs, P - 1) * bs + x % bs, n - 1).  Pooling band[src_y][:, src_x] over
+    bs x bs tiles gives what the reference makes of the band with Padding, SubSampling and DCTPadding."""
+    n, bs = int(n), int(block_size)
+    if n < 1 or bs < 1:
+        raise JpegxError("edge_source_indices: n and block_size must be at least 1")
+    pooled = -(-n // bs)
+    x = np.arange(-(-pooled // 8) * 8 * bs, dtype=np.int64)
+    return np.minimum(np.minimum(x // bs, pooled - 1) * bs + x % bs, n - 1)
+
+
+def pad_edges(planes, rows, cols, block_size=1, pitch=None):
+    """jpegx_pad_edges on a host array (test convenience, like the other stage wrappers): ``planes`` is the stacked
+    buffer [nplanes * H * bs][pitch] of uint8 or float32 with every rows x cols picture in the top left corner of its
+    plane; it goes up as it is, the margins are filled on the device, and the whole buffer comes back."""
+    a = np.ascontiguousarray(planes)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.float32):
+        raise JpegxError("expected a 2-D uint8 or float32 buffer of stacked planes")
+    bs = int(block_size)
+    h, _w = padded_shape(rows, cols, bs)
+    if a.shape[0] == 0 or a.shape[0] % (h * bs):
+        raise JpegxError("the buffer's rows must be a whole number of padded planes")
+    require_device()
+    buf = DeviceBuffer(a.nbytes)
+    try:
+        buf.upload(a)
+        check(lib().jpegx_pad_edges(buf.ptr, a.dtype.itemsize, a.shape[0] // (h * bs), int(rows), int(cols), bs,
+                                    a.shape[1] if pitch is None else int(pitch), None), "jpegx_pad_edges")
+        return buf.download(a.shape, a.dtype)
+    finally:
+        buf.free()
+
+
 _ELEM_OF = {np.dtype(np.uint8): 1, np.dtype(np.int32): 4, np.dtype(np.int64): 8}
 _pyapi = ctypes.pythonapi
 _pyapi.PyBytes_FromStringAndSize.restype = ctypes.py_object
@@ -623,25 +672,41 @@ _pyapi.PyBytes_AsString.restype = ctypes.c_void_p
 _pyapi.PyBytes_AsString.argtypes = [ctypes.py_object]
 
 
-def compress_plane_native(plane, block_size=1, mode="qtable", param=0.0):
+def _ragged_refused(hh, ww, bs, mode, param):
+    """What the ragged native entries do not take: an empty band, a block_size beyond 1..255 and, at block sizes 1, 2, 4,
+    a quantiser the uint8 kernels refuse (u8_path_ok: a divisor below 0.5)."""
+    if hh == 0 or ww == 0 or not 1 <= bs <= 255:
+        return True
+    return bs in (1, 2, 4) and not u8_path_ok(16, bs, 16, mode, param)
+
+
+def compress_plane_native(plane, block_size=1, mode="qtable", param=0.0, ragged=False):
     """compress_plane through libjpegx's native host pipeline (jpegx_host_compress_begin / _finish): pooled
     device buffers and stream, range check + narrowing of int32 / int64 bands in native threads, and the
     byte stream copied from the device straight into the returned ``bytes`` object.  Returns None when the
-    plane is not an 8-bit band in a layout that path takes (the caller then uses compress_plane)."""
+    plane is not an 8-bit band in a layout that path takes (the caller then uses compress_plane).
+    ``ragged``: a band of ANY rows x cols, padded on the device (jpegx_host_compress_begin_ragged: Padding and
+    DCTPadding as a margin fill in the padded device plane) -- the bytes of the reference's compress_band; without it
+    the plane must be whole 8 * block_size tiles already, as before."""
     src = plane if isinstance(plane, np.ndarray) else np.asarray(plane)
     bs = int(block_size)
     elem = _ELEM_OF.get(src.dtype)
     if elem is None or src.ndim != 2 or not src.flags.c_contiguous:
         return None
     hh, ww = src.shape
-    if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
-        return None
-    if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
-        return None
     L = lib()
     n = ctypes.c_size_t(0)
-    rc = L.jpegx_host_compress_begin(src.ctypes.data, elem, hh // bs, ww // bs, ww, bs, mode_of(mode), float(param),
-                                     ctypes.byref(n))
+    if ragged:
+        if _ragged_refused(hh, ww, bs, mode, param):
+            return None
+        rc = L.jpegx_host_compress_begin_ragged(src.ctypes.data, elem, hh, ww, ww, bs, mode_of(mode), float(param), ctypes.byref(n))
+    else:
+        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
+            return None
+        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
+            return None
+        rc = L.jpegx_host_compress_begin(src.ctypes.data, elem, hh // bs, ww // bs, ww, bs, mode_of(mode), float(param),
+                                         ctypes.byref(n))
     if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not an 8-bit band after all
         return None
     check(rc, "jpegx_host_compress_begin")
@@ -658,14 +723,15 @@ def compress_plane_native(plane, block_size=1, mode="qtable", param=0.0):
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)   # jpegx_alloc_fn
 
 
-def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix=None):
+def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
     """Steps 1-8 for all bands of one picture in ONE native job (jpegx_host_compress_image): the bands share one lock
     of the device's pool and alternate between two streams; once all byte counts are known libjpegx asks (through a
     callback) for ONE ``bytes`` object and copies every band from the device straight to its place in it.
     ``planes``: 2-D arrays of one shape and dtype (uint8 / int32 / int64), already padded to a multiple of
     8 * block_size.  With ``prefix`` (the container header) the result is the finished file -- prefix, then every
     band behind its '<L' byte count (file_format.generate_data); without it the list of the bands' byte strings.
-    None when the bands are not 8-bit planes in a layout this path takes."""
+    None when the bands are not 8-bit planes in a layout this path takes.
+    ``ragged``: bands of ANY rows x cols, padded on the device (jpegx_host_compress_image_ragged)."""
     arrs = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in planes]
     bs = int(block_size)
     if not arrs or len(arrs) > 4:
@@ -677,10 +743,14 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     if any(a.shape != a0.shape or a.dtype != a0.dtype or not a.flags.c_contiguous for a in arrs):
         return None
     hh, ww = a0.shape
-    if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
-        return None
-    if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
-        return None
+    if ragged:
+        if _ragged_refused(hh, ww, bs, mode, param):
+            return None
+    else:
+        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
+            return None
+        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
+            return None
     L = lib()
     box = []
 
@@ -692,8 +762,11 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
     sizes = (ctypes.c_size_t * len(arrs))()
     head = bytes(prefix) if prefix is not None else b""
-    rc = L.jpegx_host_compress_image(ptrs, len(arrs), elem, hh // bs, ww // bs, ww, bs, mode_of(mode), float(param),
-                                     head, len(head), 1 if prefix is not None else 0, cb, None, sizes)
+    tail = (ww, bs, mode_of(mode), float(param), head, len(head), 1 if prefix is not None else 0, cb, None, sizes)
+    if ragged:
+        rc = L.jpegx_host_compress_image_ragged(ptrs, len(arrs), elem, hh, ww, *tail)
+    else:
+        rc = L.jpegx_host_compress_image(ptrs, len(arrs), elem, hh // bs, ww // bs, *tail)
     if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not 8-bit bands after all
         return None
     check(rc, "jpegx_host_compress_image")
@@ -707,20 +780,27 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     return out
 
 
-def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix=None):
+def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
     """compress_image_native from pixel-interleaved samples: ``pixels`` is the (rows, cols, nbands) uint8 array that
     np.asarray(image) gives for a multi-band PIL image -- half the host time of image.split() plus an array per band; the
     planes are made on the device (jpegx_host_compress_image_packed).  rows and cols must be multiples of 8 * block_size
-    (no padding step in between).  Same bytes as compress_image_native; None when this road does not apply."""
+    unless ``ragged`` (jpegx_host_compress_image_packed_ragged: any rows x cols, padded on the device).  Same bytes as
+    compress_image_native; None when this road does not apply."""
     a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
     bs = int(block_size)
     if a.ndim != 3 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
         return None
     hh, ww, nb = a.shape
-    if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255 or hh > 65535:
+    if hh > 65535:
         return None
-    if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
-        return None
+    if ragged:
+        if _ragged_refused(hh, ww, bs, mode, param):
+            return None
+    else:
+        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
+            return None
+        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
+            return None
     L = lib()
     box = []
 
@@ -731,9 +811,11 @@ def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix
     cb = ALLOC_FN(alloc)
     sizes = (ctypes.c_size_t * nb)()
     head = bytes(prefix) if prefix is not None else b""
-    check(L.jpegx_host_compress_image_packed(a.ctypes.data, nb, hh // bs, ww // bs, ww * nb, bs, mode_of(mode), float(param),
-                                             head, len(head), 1 if prefix is not None else 0, cb, None, sizes),
-          "jpegx_host_compress_image_packed")
+    tail = (ww * nb, bs, mode_of(mode), float(param), head, len(head), 1 if prefix is not None else 0, cb, None, sizes)
+    if ragged:
+        check(L.jpegx_host_compress_image_packed_ragged(a.ctypes.data, nb, hh, ww, *tail), "jpegx_host_compress_image_packed_ragged")
+    else:
+        check(L.jpegx_host_compress_image_packed(a.ctypes.data, nb, hh // bs, ww // bs, *tail), "jpegx_host_compress_image_packed")
     whole = box[0]
     if prefix is not None:
         return whole

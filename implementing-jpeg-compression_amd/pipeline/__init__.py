@@ -163,23 +163,25 @@ def _bad_rle(exc):
 
 
 def _front_end_fused(band, config, with_entropy):
-    """Steps 0-6 (or 0-8 when with_entropy) on the GPU when the band needs no DCT padding: Padding
-    on the host (edge replication to a multiple of block_size), then SubSampling + BasisChange +
-    Quantization + ZigzagOrder inside jpegx_forward_fused_pooled, then optionally
-    RunLengthEncoding + RleBytestream (jpegx_entropy_*) with the coefficients never leaving the
-    device.  Returns None when not applicable."""
+    """Steps 0-6 (or 0-8 when with_entropy) on the GPU.  With the entropy stage an integer band of any shape is ONE
+    native call: range check, upload into a device plane of the padded shape, Padding and DCTPadding as a margin fill
+    there, SubSampling + BasisChange + Quantization + ZigzagOrder in the forward kernels, RunLengthEncoding +
+    RleBytestream (jpegx_entropy_*) with the coefficients never leaving the device.  What that call refuses (a band
+    outside 0..255, a divisor below 0.5 at block sizes 1, 2, 4) and the road without the entropy stage pad -- and, where
+    DCT padding is needed, pool -- on the host first.  Returns None when not applicable."""
     bs = config.block_size
     band = np.asarray(band)
     if not 1 <= bs <= 255 or band.ndim != 2 or band.size == 0 or band.dtype.kind not in "ui":
         return None
     import jpegx
     mode, param = config.quantization.gpu_mode()
-    padded = band if bs == 1 else padding.Padding(config).execute(band)
-    if with_entropy and not (padded.shape[0] % (8 * bs) or padded.shape[1] % (8 * bs)):
-        # the common case in one native call: range check, upload, steps 1+4..8, bytes back
-        blob = jpegx.compress_plane_native(np.ascontiguousarray(padded), bs, mode, param)
+    if with_entropy:
+        # one native call whatever the band's shape: range check, upload, steps 0..8, bytes back
+        native = band if band.dtype in (np.uint8, np.int32, np.int64) else band.astype(np.int64)
+        blob = jpegx.compress_plane_native(np.ascontiguousarray(native), bs, mode, param, ragged=True)
         if blob is not None:
             return blob
+    padded = band if bs == 1 else padding.Padding(config).execute(band)
     if bs not in (1, 2, 4) or (band.dtype != np.uint8 and (band.min() < 0 or band.max() > 255)):
         return None
     if padded.shape[0] % (8 * bs) or padded.shape[1] % (8 * bs):
@@ -345,8 +347,8 @@ class Jpeg:
 def _compress_pixels(image, config):
     """Jpeg.compress without `image.split()`: for a 4096 x 4096 picture PIL needs 25 ms to split the bands and hand each
     over as an array, 14 ms to hand over the interleaved pixels in one piece (np.asarray(image)) -- and the native job
-    behind either takes 1.5 ms.  Multi-band 8-bit pictures whose size needs no padding take this road; the bytes are
-    those of the per-band road.  None otherwise."""
+    behind either takes 1.5 ms.  Multi-band 8-bit pictures of any size take this road (the device pads: Padding and
+    DCTPadding are a margin fill in the padded device planes); the bytes are those of the per-band road.  None otherwise."""
     import jpegx
     if not (_accelerated(config) and _stock_registry()):
         return None
@@ -357,14 +359,15 @@ def _compress_pixels(image, config):
         return None
     if not 1 <= bs <= 255 or len(bands) != 3 or image.mode not in ("YCbCr", "RGB", "LAB", "HSV"):      # CompressedData holds three bands
         return None
-    if image.height % (8 * bs) or image.width % (8 * bs) or (config.height, config.width) != (image.height, image.width):
+    if (config.height, config.width) != (image.height, image.width):
         return None
     pixels = np.asarray(image)
     if pixels.dtype != np.uint8 or pixels.ndim != 3:
         return None
     mode, param = config.quantization.gpu_mode()
     try:
-        return jpegx.compress_image_packed(np.ascontiguousarray(pixels), bs, mode, param, prefix=file_format.create_header(config))
+        return jpegx.compress_image_packed(np.ascontiguousarray(pixels), bs, mode, param, prefix=file_format.create_header(config),
+                                           ragged=True)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 
@@ -372,8 +375,8 @@ def _compress_pixels(image, config):
 def _compress_image(arrays, config):
     """The three bands of one picture through ONE native job (jpegx_host_compress_image) that writes the finished
     container: the bytes of file_format.generate_data over three compress_band calls (pipeline/__init__.py:102-110,
-    file_format.py:86-93), with the bands alternating between two streams and no concatenation on the host.
-    None when the configuration or the bands do not take that road."""
+    file_format.py:86-93), with the bands alternating between two streams and no concatenation on the host; bands of
+    any size, padded on the device.  None when the configuration or the bands do not take that road."""
     import jpegx
     if not (_accelerated(config) and _stock_registry()):
         return None
@@ -381,11 +384,9 @@ def _compress_image(arrays, config):
     if not 1 <= bs <= 255 or any(a.ndim != 2 or a.size == 0 or a.dtype.kind not in "ui" for a in arrays):
         return None
     mode, param = config.quantization.gpu_mode()
-    padded = [np.ascontiguousarray(a if bs == 1 else padding.Padding(config).execute(a)) for a in arrays]
-    if any(p.shape[0] % (8 * bs) or p.shape[1] % (8 * bs) for p in padded):
-        return None                                         # DCT padding needed: the per-band road pools on the host first
     try:
-        return jpegx.compress_image_native(padded, bs, mode, param, prefix=file_format.create_header(config))
+        return jpegx.compress_image_native([np.ascontiguousarray(a) for a in arrays], bs, mode, param,
+                                           prefix=file_format.create_header(config), ragged=True)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 

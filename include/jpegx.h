@@ -18,7 +18,8 @@
  * The reference has no native boundary (it is pure Python); each entry point below names the
  * reference function(s) whose work it replaces, relative to /root/reference.
  *
- * Plane layout: row-major, `pitch` in ELEMENTS between rows, H and W multiples of 8.
+ * Plane layout: row-major, `pitch` in ELEMENTS between rows, H and W multiples of 8 (a band of any rows x cols gets
+ * there on the device: jpegx_padded_shape + jpegx_pad_edges, and the jpegx_host_compress_*_ragged jobs).
  * Coefficient stream layout ("zigzag stream"): int16 [H/8][W/8][64], block-row-major, the 64
  * coefficients of a block contiguous in zigzag order -- pipeline/zigzag_order.py:85-99.
  */
@@ -273,8 +274,11 @@ int jpegx_entropy_decode_status(const void *d_workspace, jpegx_stream_t stream);
  * planes' byte strings concatenated and a per-plane index beside them; the way back is decompress_band
  * (pipeline/__init__.py:79-88; pipeline/rle_byte_stream.py:61-88, pipeline/run_length_encoding.py:66-97).
  * A batch is `nplanes` planes of equal shape STACKED: one array [nplanes * H * bs][pitch], plane p starting at row
- * p * H * bs.  H, W: sizes after pooling, multiples of 8 (padding stays the caller's); nplanes * (H/8) * (W/8) <=
- * 2^31 - 64.  Everything lives in the caller's workspace (16-byte aligned; jpegx_malloc gives more).
+ * p * H * bs.  H, W: sizes after pooling, multiples of 8; nplanes * (H/8) * (W/8) <= 2^31 - 64.  Pictures of any rows x
+ * cols: H, W from jpegx_padded_shape, the pictures copied into the stacked buffer at its padded pitch (plane p at row
+ * p * H * bs, each in the top left corner of its plane), then jpegx_pad_edges on that buffer and this call on the same
+ * stream; on the way back jpegx_batch_decompress writes planes of the padded shape and the caller reads rows x cols of each.
+ * Everything lives in the caller's workspace (16-byte aligned; jpegx_malloc gives more).
  * Footprints: the workspace is 128 bytes per block (the int16 stream) + jpegx_entropy_workspace_bytes + the index;
  * jpegx_batch_max_bytes is the worst case of the coded stream, 185 bytes per block (64 x 23 bits + the end marker)
  * rounded up to 188 + 64 bytes -- several times what pictures need.  The small-footprint road: compress with d_out ==
@@ -321,6 +325,22 @@ size_t jpegx_batch_decompress_workspace_bytes(size_t nbytes, int nplanes, int H,
 int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int H, int W,
                            int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out,
                            ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream);
+
+/* ---- edge padding on the device: Padding.execute (pipeline/padding.py:8-12) + DCTPadding.execute
+ * (pipeline/dct_padding.py:8-9), i.e. util.pad_array (util.py:17-41) before and after SubSampling -----------------
+ * jpegx_padded_shape: H, W of a rows x cols band AFTER pooling and DCT padding, both multiples of 8 -- per axis
+ * P = ceil(n / bs) pooled samples, ceil(P / 8) * 8 after padding (the arithmetic of DCTPadding.invert,
+ * pipeline/dct_padding.py:11-21); the padded RAW plane is (H * bs) x (W * bs).  Host arithmetic only, no device needed.
+ * bs in 1..255; JPEGX_E_INVALID for rows or cols below 1 or a padded plane beyond 32-bit sizes.
+ * jpegx_pad_edges (enqueue only): `nplanes` planes stacked [nplanes * H * bs][pitch] of uint8 (elem_size 1, pitch in
+ * bytes) or fp32 (elem_size 4, pitch in elements), each holding its rows x cols picture in the top left corner.  Writes
+ * the samples with x >= cols or y >= rows inside every plane's (H * bs) x (W * bs) rectangle -- nothing else, not the
+ * picture, not the pitch slack -- so that pooling the result gives what the reference pools and pads: a replicated pooled
+ * sample is the mean of a replicated bs x bs tile, so padded[y][x] = picture[src(y)][src(x)] with, per axis,
+ * src(x) = min(min(x / bs, P - 1) * bs + x % bs, n - 1).  No launch when there is no margin.                        */
+int jpegx_padded_shape(int rows, int cols, int bs, int *H, int *W);
+int jpegx_pad_edges(void *d_planes, int elem_size, int nplanes, int rows, int cols, int bs, ptrdiff_t pitch,
+                    jpegx_stream_t stream);
 
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
@@ -386,6 +406,13 @@ int jpegx_host_compress_begin(const void *h_plane, int elem_size, int H, int W, 
                               int mode, double param, size_t *nbytes);
 int jpegx_host_compress_finish(uint8_t *h_out);
 int jpegx_host_compress_abort(void);
+/* _begin for a band of ANY rows x cols, steps 0 and 2 included (Padding.execute, pipeline/padding.py:8-12;
+ * DCTPadding.execute, pipeline/dct_padding.py:8-9): h_plane is [rows][pitch], uploaded into a device plane of the padded
+ * shape (jpegx_padded_shape) whose margins jpegx_pad_edges fills before the forward kernel; the rest, _finish and _abort as
+ * above.  rows x cols of whole 8 * bs tiles: the very job of jpegx_host_compress_begin, no extra launch or copy.  bs 1 with
+ * a padded row of 8 mod 16 samples takes the float64 road (same bytes) instead of JPEGX_E_UNSUPPORTED.             */
+int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs,
+                                     int mode, double param, size_t *nbytes);
 /* The way back (decompress_band, pipeline/__init__.py:79-88, transform 'DCT', dct_size 8): the band's byte
  * stream up, RleBytestream.invert + RunLengthEncoding.invert (pipeline/rle_byte_stream.py:61-88,
  * pipeline/run_length_encoding.py:66-97) ON THE DEVICE -- the stream has no index, block starts are recovered
@@ -426,6 +453,18 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
 int jpegx_host_compress_image_packed(const uint8_t *h_pixels, int nbands, int H, int W, ptrdiff_t pitch, int bs,
                                      int mode, double param, const void *prefix, size_t prefix_len,
                                      int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+/* The two compress_image jobs for pictures of ANY rows x cols (Jpeg.compress, pipeline/__init__.py:102-110, with
+ * Padding.execute and DCTPadding.execute, pipeline/padding.py:8-12 and pipeline/dct_padding.py:8-9, done on the device):
+ * the parents' arguments with rows, cols -- the bands as the caller holds them, [rows][pitch] / [rows][cols][nbands] --
+ * in place of H, W; every band lands in a device plane of the padded shape and has its margins filled there
+ * (jpegx_pad_edges).  Same bytes as padding on the host first; whole 8 * bs tiles: the parents' job, nothing added. */
+int jpegx_host_compress_image_ragged(const void *const *h_planes, int nbands, int elem_size, int rows, int cols,
+                                     ptrdiff_t pitch, int bs, int mode, double param, const void *prefix,
+                                     size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user,
+                                     size_t *nbytes);
+int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                            int bs, int mode, double param, const void *prefix, size_t prefix_len,
+                                            int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes);
 /* pixel-interleaved [rows][cols][nbands] (rows in_pitch bytes apart) -> device planes [rows][pitch] (uint8, pitch a multiple of 4) */
 int jpegx_deinterleave_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int nbands, int rows, int cols, void *const *d_planes,
                           ptrdiff_t pitch, jpegx_stream_t stream);
@@ -479,6 +518,18 @@ int jpegx_batch_emit_on(int device, void *d_workspace, int nplanes, int H, int W
 int jpegx_batch_decompress_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes,
                               int H, int W, int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out,
                               ptrdiff_t out_pitch, int out_type, jpegx_stream_t stream);
+int jpegx_pad_edges_on(int device, void *d_planes, int elem_size, int nplanes, int rows, int cols, int bs, ptrdiff_t pitch,
+                       jpegx_stream_t stream);
+int jpegx_host_compress_begin_ragged_on(int device, const void *h_plane, int elem_size, int rows, int cols, ptrdiff_t pitch,
+                                        int bs, int mode, double param, size_t *nbytes);
+int jpegx_host_compress_image_ragged_on(int device, const void *const *h_planes, int nbands, int elem_size, int rows, int cols,
+                                        ptrdiff_t pitch, int bs, int mode, double param, const void *prefix,
+                                        size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user,
+                                        size_t *nbytes);
+int jpegx_host_compress_image_packed_ragged_on(int device, const uint8_t *h_pixels, int nbands, int rows, int cols,
+                                               ptrdiff_t pitch, int bs, int mode, double param, const void *prefix,
+                                               size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user,
+                                               size_t *nbytes);
 int jpegx_host_compress_begin_on(int device, const void *h_plane, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
                                  int mode, double param, size_t *nbytes);
 int jpegx_host_compress_image_on(int device, const void *const *h_planes, int nbands, int elem_size, int H, int W,
