@@ -50,14 +50,18 @@ int fail(const char *msg)
 
 }  // namespace
 
-extern "C" int jpegx_host_entropy_decode(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz)
+namespace {
+
+// The sequential parse for blocks of `len` coefficients (64 for dct_size 8, N * N in general) into int16 or int32.
+template <typename T>
+int decode_blocks(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int len, T *h_zz)
 {
     if (!h_bytes || !h_zz) return fail("null host pointer");
     if (nblocks <= 0) return fail("block count must be positive");
     BitCursor cur(h_bytes, nbytes);
     for (long long b = 0; b < nblocks; ++b) {
-        int16_t *blk = h_zz + b * 64;
-        memset(blk, 0, 128);                         // zeros are the common case: only non-zeros are written below
+        T *blk = h_zz + b * len;
+        memset(blk, 0, sizeof(T) * (size_t)len);     // zeros are the common case: only non-zeros are written below
         int n = 0;                                   // coefficients placed so far
         for (;;) {
             if (cur.bits_left() < 8) return fail("entropy stream ends inside a block");
@@ -70,7 +74,7 @@ extern "C" int jpegx_host_entropy_decode(const uint8_t *h_bytes, size_t nbytes, 
                     break;
                 }
                 if (run != 15) return fail("BadRleCodeError: zero size with a non-terminal run");
-                if (n + 15 > 64) return fail("zero chain overruns the block");      // FIFTEEN zeros (util.py:134-154)
+                if (n + 15 > len) return fail("zero chain overruns the block");      // FIFTEEN zeros (util.py:134-154)
                 n += 15;
                 continue;
             }
@@ -80,13 +84,88 @@ extern "C" int jpegx_host_entropy_decode(const uint8_t *h_bytes, size_t nbytes, 
             cur.bitpos += 8 + size;
             const unsigned mag = bits & ((1u << (size - 1)) - 1u);
             n += (int)run;
-            if (n >= 64) return fail("run overruns the block");
-            blk[n++] = (int16_t)((bits >> (size - 1)) ? (int)mag : -(int)mag);       // sign bit '1' = positive
+            if (n >= len) return fail("run overruns the block");
+            blk[n++] = (T)((bits >> (size - 1)) ? (int)mag : -(int)mag);             // sign bit '1' = positive
         }
     }
     // bytes (whole blocks) behind the last block: the reference parses them too and then fails in its reshape
     // (run_length_encoding.py:77-79)
     if (cur.bits_left() > 0) return fail("ValueError: the entropy stream holds more than the plane's blocks");
+    return JPEGX_OK;
+}
+
+// MSB-first bit writer; with out == nullptr it only counts.
+struct BitSink {
+    uint8_t *out;
+    size_t nbytes = 0;
+    uint64_t acc = 0;
+    int have = 0;                                    // bits waiting in acc (below 8 between calls)
+    explicit BitSink(uint8_t *o) : out(o) {}
+    void put(unsigned value, int nbits)              // nbits <= 24
+    {
+        acc = (acc << nbits) | value;
+        have += nbits;
+        while (have >= 8) {
+            have -= 8;
+            if (out) out[nbytes] = (uint8_t)(acc >> have);
+            ++nbytes;
+        }
+    }
+    void pad_to_byte() { if (have) put(0u, 8 - have); }
+};
+
+// RunLengthEncoding.execute + RleBytestream.execute for one stream (pipeline/run_length_encoding.py:47-64,
+// pipeline/rle_byte_stream.py:48-59); false when an amplitude needs more than 15 bits
+bool encode_blocks(const int32_t *zz, long long nblocks, int len, BitSink *sink)
+{
+    for (long long b = 0; b < nblocks; ++b) {
+        const int32_t *blk = zz + b * len;
+        int prev = -1;
+        for (int i = 0; i < len; ++i) {
+            const int32_t v = blk[i];
+            if (v == 0) continue;
+            const unsigned mag = v < 0 ? 0u - (unsigned)v : (unsigned)v;
+            if (mag > 16383u) return false;
+            const int digits = 32 - __builtin_clz(mag);
+            int zeros = i - prev - 1;
+            for (; zeros >= 15; zeros -= 15) sink->put(0xF0u, 8);                    // (15, 0, 0): FIFTEEN zeros
+            sink->put(((unsigned)zeros << 4) | (unsigned)(digits + 1), 8);
+            sink->put(((v > 0 ? 1u : 0u) << digits) | mag, digits + 1);
+            prev = i;
+        }
+        sink->put(0u, 8);                                                            // end of block
+        sink->pad_to_byte();
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int jpegx_host_entropy_decode(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz)
+{
+    return decode_blocks(h_bytes, nbytes, nblocks, 64, h_zz);
+}
+
+extern "C" int jpegx_host_entropy_decode_n(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len, int32_t *h_zz)
+{
+    if (block_len < 1 || block_len > 1024) return fail("block length must be 1 .. 1024");
+    return decode_blocks(h_bytes, nbytes, nblocks, block_len, h_zz);
+}
+
+extern "C" int jpegx_host_entropy_encode_n(const int32_t *h_zz, long long nblocks, int block_len, uint8_t *h_out, size_t cap,
+                                           size_t *nbytes)
+{
+    if (!h_zz || !nbytes) return fail("null host pointer");
+    if (nblocks <= 0) return fail("block count must be positive");
+    if (block_len < 1 || block_len > 1024) return fail("block length must be 1 .. 1024");
+    BitSink count(nullptr);
+    if (!encode_blocks(h_zz, nblocks, block_len, &count))
+        return fail("BadRleCodeError: an amplitude needs more than 15 bits (|a| > 16383)");
+    *nbytes = count.nbytes;
+    if (!h_out) return JPEGX_OK;                     // size query
+    if (cap < count.nbytes) return fail("output buffer too small");
+    BitSink sink(h_out);
+    encode_blocks(h_zz, nblocks, block_len, &sink);
     return JPEGX_OK;
 }
 

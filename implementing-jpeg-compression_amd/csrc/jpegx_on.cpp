@@ -96,3 +96,11 @@ JPEGX_ON(jpegx_host_compress_image_ragged, (int device, const void *const *h_pla
          (h_planes, nbands, elem_size, rows, cols, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
 JPEGX_ON(jpegx_host_compress_image_packed_ragged, (int device, const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
          (h_pixels, nbands, rows, cols, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
+JPEGX_ON(jpegx_forward_fused_n, (int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, int mode, double param, int32_t *d_out, jpegx_stream_t stream),
+         (d_in, H, W, pitch, N, mode, param, d_out, stream))
+JPEGX_ON(jpegx_inverse_fused_n, (int device, const int32_t *d_in, int H, int W, int N, int mode, double param, unsigned flags, void *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_in, H, W, N, mode, param, flags, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_dct_f64_n, (int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_in, H, W, pitch, N, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_idct_f64_n, (int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch, int do_round, jpegx_stream_t stream),
+         (d_in, H, W, pitch, N, d_out, out_pitch, do_round, stream))

@@ -150,6 +150,17 @@ SIGNATURES = {
     "jpegx_batch_emit": [_vp, _int, _int, _int, _vp, _sz, _vp],
     "jpegx_batch_decompress_workspace_bytes": [_sz, _int, _int, _int],
     "jpegx_batch_decompress": [_vp, _vp, _int, _int, _int, _int, _int, _dbl, _uint, _vp, _vp, _pd, _int, _vp],
+    "jpegx_forward_fused_n": [_vp, _int, _int, _pd, _int, _int, _dbl, _vp, _vp],
+    "jpegx_inverse_fused_n": [_vp, _int, _int, _int, _int, _dbl, _uint, _vp, _pd, _vp],
+    "jpegx_dct_f64_n": [_vp, _int, _int, _pd, _int, _vp, _pd, _vp],
+    "jpegx_idct_f64_n": [_vp, _int, _int, _pd, _int, _vp, _pd, _int, _vp],
+    "jpegx_dct_tables_n": [_int, _vp, _vp, _vp, _vp],
+    "jpegx_host_forward_fused_n": [_vp, _int, _int, _int, _int, _dbl, _vp],
+    "jpegx_host_inverse_fused_n": [_vp, _int, _int, _int, _int, _dbl, _uint, _vp, _pd],
+    "jpegx_host_dct_f64_n": [_vp, _int, _int, _int, _vp],
+    "jpegx_host_idct_f64_n": [_vp, _int, _int, _int, _vp, _int],
+    "jpegx_host_entropy_encode_n": [_vp, _c.c_longlong, _int, _vp, _sz, _c.POINTER(_sz)],
+    "jpegx_host_entropy_decode_n": [_vp, _sz, _c.c_longlong, _int, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -167,7 +178,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_batch_compress_status", "jpegx_batch_emit", "jpegx_batch_decompress", "jpegx_host_compress_begin", "jpegx_host_compress_image", "jpegx_host_compress_image_packed", "jpegx_host_decompress_plane",
               "jpegx_host_decompress_plane_i64", "jpegx_host_decompress_image", "jpegx_host_entropy_decode_gpu",
               "jpegx_host_pool_release", "jpegx_comm_create_deadline", "jpegx_pad_edges", "jpegx_host_compress_begin_ragged",
-              "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged"):
+              "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged", "jpegx_forward_fused_n",
+              "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
@@ -936,6 +948,102 @@ def entropy_decode(blob, nblocks):
     out = np.empty((int(nblocks), 64), dtype=np.int16)
     check(lib().jpegx_host_entropy_decode(buf.ctypes.data if buf.size else None, buf.size, int(nblocks),
                                           out.ctypes.data), "jpegx_host_entropy_decode")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# any DCT size (csrc/jpegx_dctn.hip): transform 'DCT', dct_size N in 2..32, all float64 in one documented order
+# ---------------------------------------------------------------------------------------------
+def _plane_n(a, n, dtype=np.float64):
+    a = _plane(a, dtype)
+    n = int(n)
+    if a.size == 0 or a.shape[0] % max(n, 1) or a.shape[1] % max(n, 1):
+        raise JpegxError("expected a non-empty plane of whole %d x %d blocks, got shape %r" % (n, n, a.shape))
+    return a, n
+
+
+def _stream_n(zz, n):
+    z = np.ascontiguousarray(zz, dtype=np.int32)
+    n = int(n)
+    if z.ndim != 3 or z.shape[2] != n * n or z.size == 0:
+        raise JpegxError("expected a (H/N, W/N, N*N) coefficient stream for N = %d, got %r" % (n, z.shape))
+    return z, n
+
+
+def dct_tables_n(n):
+    """(C, Cn, Dinv, zigzag) as the dct_size-n kernels use them: transforms.dct_matrix, dct_matrix_normalized, the
+    diagonal of normalization_matrix and Zigzag(n).flat_indices().  Host arithmetic only, no device needed."""
+    n = int(n)
+    m = max(n, 1)
+    c, cn, dinv, zig = np.empty((m, m)), np.empty((m, m)), np.empty(m), np.empty(m * m, dtype=np.uint16)
+    check(lib().jpegx_dct_tables_n(n, c.ctypes.data, cn.ctypes.data, dinv.ctypes.data, zig.ctypes.data), "jpegx_dct_tables_n")
+    return c, cn, dinv, zig
+
+
+def forward_fused_n(plane, n, mode="none", param=0.0):
+    """float64 plane (H, W) -> int32 (H/n, W/n, n*n): BasisChange + Quantization + ZigzagOrder.execute for dct_size n."""
+    a, n = _plane_n(plane, n)
+    h, w = a.shape
+    out = np.empty((h // n, w // n, n * n), dtype=np.int32)
+    check(lib().jpegx_host_forward_fused_n(a.ctypes.data, h, w, n, mode_of(mode), float(param), out.ctypes.data),
+          "jpegx_host_forward_fused_n")
+    return out
+
+
+def inverse_fused_n(zz, n, mode="none", param=0.0, out="i32", out_pitch=None):
+    """int32 (H/n, W/n, n*n) -> (H, W) samples: ZigzagOrder + Quantization + BasisChange.invert (rounded) for dct_size n;
+    out 'i32' (unclamped) or 'u8' (clamped to 0..255, Normalization.invert fused)."""
+    z, n = _stream_n(zz, n)
+    h, w = z.shape[0] * n, z.shape[1] * n
+    if out not in ("i32", "u8"):
+        raise JpegxError("inverse_fused_n: out must be 'i32' or 'u8'")
+    pitch = w if out_pitch is None else int(out_pitch)
+    res = np.zeros((h, max(pitch, w)), dtype=np.int32 if out == "i32" else np.uint8)
+    check(lib().jpegx_host_inverse_fused_n(z.ctypes.data, h, w, n, mode_of(mode), float(param), F_CLAMP_U8 if out == "u8" else 0,
+                                           res.ctypes.data, pitch), "jpegx_host_inverse_fused_n")
+    return res if pitch == w else res[:, :w]
+
+
+def dct_f64_n(plane, n):
+    """BasisChange.execute (DCT, dct_size n): the float64 coefficients of every n x n block in its place."""
+    a, n = _plane_n(plane, n)
+    out = np.empty_like(a)
+    check(lib().jpegx_host_dct_f64_n(a.ctypes.data, a.shape[0], a.shape[1], n, out.ctypes.data), "jpegx_host_dct_f64_n")
+    return out
+
+
+def idct_f64_n(plane, n, do_round=True):
+    """BasisChange.invert (DCT, dct_size n); do_round applies the np.round of basis_change.py:43."""
+    a, n = _plane_n(plane, n)
+    out = np.empty_like(a)
+    check(lib().jpegx_host_idct_f64_n(a.ctypes.data, a.shape[0], a.shape[1], n, out.ctypes.data, 1 if do_round else 0),
+          "jpegx_host_idct_f64_n")
+    return out
+
+
+def entropy_encode_n(zz, block_len=None):
+    """int32 (..., block_len) zigzag stream -> bytes: RunLengthEncoding.execute + RleBytestream.execute for blocks of any
+    length, sequentially on the host (no device needed)."""
+    z = np.ascontiguousarray(zz, dtype=np.int32)
+    block_len = int(z.shape[-1] if block_len is None and z.ndim else block_len or 0)
+    if z.size == 0 or block_len < 1 or z.size % block_len:
+        raise JpegxError("expected a non-empty stream of whole blocks of %d coefficients, got %r" % (block_len, z.shape))
+    nblocks = z.size // block_len
+    n = ctypes.c_size_t(0)
+    L = lib()
+    check(L.jpegx_host_entropy_encode_n(z.ctypes.data, nblocks, block_len, None, 0, ctypes.byref(n)), "jpegx_host_entropy_encode_n")
+    blob = _pyapi.PyBytes_FromStringAndSize(None, n.value)          # uninitialised bytes, filled below
+    check(L.jpegx_host_entropy_encode_n(z.ctypes.data, nblocks, block_len, _pyapi.PyBytes_AsString(blob), n.value, ctypes.byref(n)),
+          "jpegx_host_entropy_encode_n")
+    return blob
+
+
+def entropy_decode_n(blob, nblocks, block_len):
+    """bytes -> int32 (nblocks, block_len): RleBytestream.invert + RunLengthEncoding.invert (host, sequential)."""
+    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    out = np.empty((max(int(nblocks), 0), max(int(block_len), 0)), dtype=np.int32)
+    check(lib().jpegx_host_entropy_decode_n(buf.ctypes.data if buf.size else None, buf.size, int(nblocks), int(block_len),
+                                            out.ctypes.data if out.size else None), "jpegx_host_entropy_decode_n")
     return out
 
 

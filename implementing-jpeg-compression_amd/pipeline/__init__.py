@@ -6,6 +6,11 @@ BasisChange, Quantization, ZigzagOrder -- are replaced by ONE fused GPU kernel l
 (libjpegx ``jpegx_forward_fused`` / ``jpegx_inverse_fused``) whose integer output is bit-exact
 with the step-by-step float64 pipeline.  There is no CPU fallback for the accelerated
 configuration: without libjpegx.so or a GPU the call raises ``jpegx.JpegxError``.
+
+Any other dct_size 2..32 with transform 'DCT' takes the all-float64 kernels of csrc/jpegx_dctn.hip
+(``jpegx_forward_fused_n`` / ``jpegx_inverse_fused_n``, entropy stage by libjpegx's sequential host coder) when a
+device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
+NumPy road runs, exactly as the reference does it.
 """
 import json
 
@@ -14,7 +19,7 @@ import numpy as np
 import file_format
 from quantizers import DiscardingQuantizer, DivisionQuantizer, JpegQuantizationTable, RoundingQuantizer
 from util import band_to_array
-from . import (basis_change, dct_padding, normalization, padding, quantization,  # noqa: F401  (registration)
+from . import (basis_change, dct_padding, geometry, normalization, padding, quantization,  # noqa: F401  (registration)
                rle_byte_stream, run_length_encoding, subsampling, zigzag_order)
 from .base import step_classes
 
@@ -94,6 +99,122 @@ class Configuration:
         elif quantization.name == "qtable" and dct_size != 8:
             raise BadQuantizationError()
         self.quantization = quantization
+
+
+# dct_size other than 8: planes below this many samples stay on the host NumPy road.  Measured (DESIGN.md 4.7,
+# profiles/dct_sizes.json): at 1024 samples, the smallest plane measured, the device road already takes 0.06-0.13 ms
+# against 1.0-1.2 ms on the host, and its lead only grows with the plane; below that nothing was measured, and planes
+# of a few blocks are what unit tests and a machine's first steps with the step classes use
+DCTN_MIN_SAMPLES = 1024
+
+_device_seen = False
+
+
+def _device_usable():
+    """True when libjpegx loads and sees a GPU; never raises (a machine without one keeps the host road)."""
+    global _device_seen
+    if not _device_seen:
+        try:
+            import jpegx
+            _device_seen = jpegx.device_count() > 0
+        except Exception:
+            return False
+    return _device_seen
+
+
+def _dctn_config(config):
+    n = config.dct_size
+    return config.transform == "DCT" and isinstance(n, (int, np.integer)) and 2 <= n <= 32 and n != 8 and _device_usable()
+
+
+def dctn_on_device(config, samples):
+    """The dispatch rule for dct_size != 8: transform 'DCT', 2 <= dct_size <= 32, a plane of at least
+    DCTN_MIN_SAMPLES samples and a usable device."""
+    return samples >= max(DCTN_MIN_SAMPLES, 1) and _dctn_config(config)
+
+
+def _dctn_mode(config):
+    """(mode, param) for the dct_size-N kernels (stock 'none', 'discard', 'divide' quantisers), else None."""
+    args = config.quantization.gpu_mode()
+    return args if args is not None and args[0] != "qtable" else None
+
+
+def _hot_forward_n(pre, config):
+    """Steps 4+5+6 for dct_size N in one launch: int32 (H/N, W/N, N*N), or None when this plane stays on the host
+    (too small, not real, not whole blocks, or coefficients that could leave the int32 range)."""
+    n = config.dct_size
+    pre = np.asarray(pre)
+    args = _dctn_mode(config)
+    if args is None or pre.ndim != 2 or pre.dtype.kind not in "fiu" or not dctn_on_device(config, pre.size) \
+            or pre.shape[0] % n or pre.shape[1] % n:
+        return None
+    mode, param = args
+    pre = pre.astype(np.float64, copy=False)
+    reach = max(abs(float(pre.max())), abs(float(pre.min()))) * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0)
+    if not reach < 2.0 ** 31:                       # also catches NaN
+        return None
+    import jpegx
+    return jpegx.forward_fused_n(pre, n, mode, param)
+
+
+def _hot_inverse_n(zz, config):
+    """Steps 6+5+4 inverted for dct_size N in one launch (int samples), or None when the stream stays on the host."""
+    n = config.dct_size
+    zz = np.asarray(zz)
+    args = _dctn_mode(config)
+    if args is None or zz.ndim != 3 or zz.shape[2] != n * n or zz.dtype.kind not in "fiu" \
+            or not dctn_on_device(config, zz.size):
+        return None
+    if zz.dtype != np.int32:
+        if np.abs(zz).max() >= 2 ** 31 or not np.array_equal(zz, np.rint(zz)):
+            return None
+        zz = zz.astype(np.int32)
+    import jpegx
+    return jpegx.inverse_fused_n(zz, n, *args).astype(int)
+
+
+def _compress_band_n(a, config):
+    """compress_band for dct_size != 8 with the three hot steps as one device launch: host steps 0-3 as they are,
+    jpegx_forward_fused_n, then -- in a stock registry -- libjpegx's sequential entropy coder.  None when the road does
+    not apply; the caller then walks the steps on the host as before."""
+    import jpegx
+    todo = list(step_classes)
+    at = _hot_run(todo)
+    if at is None or _dctn_mode(config) is None:
+        return None
+    for cls in todo[:at]:
+        a = cls(config).execute(a)
+    zz = _hot_forward_n(a, config)
+    rest = todo[at + 3:]
+    if zz is None:
+        rest = todo[at:]
+    elif _stock_registry():
+        try:
+            return jpegx.entropy_encode_n(zz, config.dct_size ** 2)
+        except jpegx.JpegxError:
+            pass                                    # an amplitude beyond 15 bits: the host step raises the reference's error
+        a = zz.astype(np.float64)
+    else:
+        a = zz.astype(np.float64)                   # what Quantization + ZigzagOrder hand to the next step
+    for cls in rest:
+        a = cls(config).execute(a)
+    return a
+
+
+def _decode_stream_n(blob, config):
+    """Steps 8+7 inverted by libjpegx's sequential parser: int32 (hb, wb, N*N), or None (a malformed stream: the host
+    steps then name the fault as they always did)."""
+    import jpegx
+    rle = run_length_encoding.RunLengthEncoding(config)
+    hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
+    nn = config.dct_size ** 2
+    if not isinstance(blob, (bytes, bytearray)) or not len(blob) or hb * wb <= 0 or _dctn_mode(config) is None \
+            or not dctn_on_device(config, hb * wb * nn):
+        return None
+    try:
+        return jpegx.entropy_decode_n(blob, hb * wb, nn).reshape(hb, wb, nn)
+    except jpegx.JpegxError:
+        return None
 
 
 def _accelerated(config):
@@ -227,6 +348,10 @@ def compress_band(a, config):
     fused = _accelerated(config)
     todo = list(step_classes)
     try:
+        if not fused and _dctn_config(config):
+            out = _compress_band_n(a, config)
+            if out is not None:
+                return out
         if fused and _stock_registry():
             blob = _front_end_fused(a, config, with_entropy=True)
             if blob is not None:
@@ -260,6 +385,19 @@ def decompress_band_u8(compression_result, config):
                 return jpegx.decompress_plane(a, hb * 8, wb * 8, config.block_size, mode, param)[:config.height, :config.width]
             except jpegx.JpegxError:
                 pass
+    if not _accelerated(config) and _stock_registry():
+        zz = _decode_stream_n(a, config)
+        if zz is not None:
+            # inverse with the clamp fused, then the geometry steps on uint8: crop the DCT padding, replicate, crop
+            n, bs = config.dct_size, config.block_size
+            (rows, cols), _, pooled, _ = geometry.band_geometry(config)
+            try:
+                plane = jpegx.inverse_fused_n(zz, n, *_dctn_mode(config), out="u8")[:pooled[0], :pooled[1]]
+            except jpegx.JpegxError as exc:
+                raise _bad_rle(exc)
+            if bs != 1:
+                plane = np.repeat(np.repeat(plane, bs, axis=0), bs, axis=1)
+            return np.ascontiguousarray(plane[:rows, :cols])
     return decompress_band(compression_result, config).astype(np.uint8)
 
 
@@ -292,6 +430,13 @@ def decompress_band(compression_result, config):
             if band is not None:
                 return band
             todo = todo[2:]
+        if not fused and _stock_registry():
+            zz = _decode_stream_n(a, config)
+            band = None if zz is None else _hot_inverse_n(zz, config)
+            if band is not None:
+                for cls in todo[5:]:                         # Normalization, DCTPadding, SubSampling, Padding
+                    band = cls(config).invert(band)
+                return band
         at = _hot_run(list(reversed(todo))) if fused else None      # position counted in forward order
         at = None if at is None else len(todo) - 3 - at             # -> index of ZigzagOrder in the reversed list
         for k, cls in enumerate(todo):

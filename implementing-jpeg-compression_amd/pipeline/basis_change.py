@@ -1,9 +1,12 @@
 """Step 4: per-block change of basis (reference: pipeline/basis_change.py).
 
 transform 'DCT' with dct_size 8 -- the hot path -- runs on the GPU (libjpegx float64 kernels,
-bit-identical to the reference's float64 output).  Other DCT sizes and the 'DFT' option are
-outside the accelerated path and are evaluated on the host.
+bit-identical to the reference's float64 output).  The other DCT sizes 2..32 run on the GPU as well
+(libjpegx's all-float64 kernels for a run-time size, csrc/jpegx_dctn.hip) when a device is usable and the plane
+holds at least pipeline.DCTN_MIN_SAMPLES samples, otherwise on the host like the 'DFT' option.
 """
+import sys
+
 import numpy as np
 
 from transforms import DCT
@@ -27,12 +30,21 @@ class BasisChange(AlgorithmStep):
                 and array.ndim == 2 and array.shape[0] % 8 == 0 and array.shape[1] % 8 == 0
                 and array.size > 0 and not np.iscomplexobj(array))
 
+    def _on_gpu_n(self, array):
+        n = self._config.dct_size
+        return (array.ndim == 2 and array.size > 0 and array.dtype.kind in "fiu"
+                and sys.modules[__package__].dctn_on_device(self._config, array.size)
+                and array.shape[0] % n == 0 and array.shape[1] % n == 0)
+
     def execute(self, array):
         transform, n = self._config.transform, self._config.dct_size
         array = np.asarray(array)
         if self._on_gpu(array):
             import jpegx
             return jpegx.dct8x8_f64(array.astype(np.float64))
+        if self._on_gpu_n(array):
+            import jpegx
+            return jpegx.dct_f64_n(array, n)
         if transform == "DCT":
             res = np.zeros(array.shape, dtype=float)
             self.apply_blockwise(array, DCT(n).transform_2d, n, res)
@@ -48,6 +60,9 @@ class BasisChange(AlgorithmStep):
         if self._on_gpu(array):
             import jpegx
             return jpegx.idct8x8_f64(array.astype(np.float64), do_round=True).astype(int)
+        if self._on_gpu_n(array):
+            import jpegx
+            return jpegx.idct_f64_n(array, n, do_round=True).astype(int)
         res = np.zeros(array.shape, dtype=float)
         if transform == "DCT":
             self.apply_blockwise(array, DCT(n).transform_2d_inverse, n, res)

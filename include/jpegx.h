@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define JPEGX_VERSION 100 /* major*10000 + minor*100 + patch */
+#define JPEGX_VERSION 200 /* major*10000 + minor*100 + patch */
 
 /* error codes */
 #define JPEGX_OK 0
@@ -229,6 +229,49 @@ int jpegx_zigzag(const void *d_in, int H, int W, ptrdiff_t pitch, int elem_size,
                  jpegx_stream_t stream);
 int jpegx_unzigzag(const void *d_in, int H, int W, int elem_size, void *d_out, ptrdiff_t out_pitch,
                    jpegx_stream_t stream);
+
+/* ---- any DCT size: steps 4-6 and their inverses for transform 'DCT', dct_size N in 2..32 (csrc/jpegx_dctn.hip) --------
+ * All float64 in ONE documented order -- every dot product is acc = c[0] x[0]; acc = fma(c[n], x[n], acc), n ascending --
+ * with the reference's matrices (transforms.py:4-26) built on the host in double.  For N != 8 the reference's own
+ * summation order is its BLAS's, so these entries agree with it within a derived bound, not bit for bit;
+ * N = 8 is accepted but the bit-exact 8x8 entries above remain the road for dct_size 8.
+ * Planes: H and W multiples of N, pitch in elements.  Coefficient stream: int32 [H/N][W/N][N*N], block-row-major, a
+ * block's coefficients contiguous in the zigzag order of pipeline/zigzag_order.py:27-79 (int32: a DC of 255 N^2 does not
+ * fit int16 above N = 8; values beyond int32 saturate).  Quantisers: JPEGX_Q_NONE, _DISCARD, _DIVIDE; JPEGX_Q_QTABLE is
+ * JPEGX_E_INVALID (pipeline/__init__.py:60-61 raises BadQuantizationError for it).  The first call for a size on a device
+ * allocates and uploads that size's tables (the one exception to "entries only enqueue"); later calls only enqueue.   */
+/* BasisChange.execute (pipeline/basis_change.py:11-18, transforms.py:46-58) + Quantization.execute
+ * (pipeline/quantization.py:8-18, quantizers.py:4-31) + ZigzagOrder.execute (pipeline/zigzag_order.py:85-99) */
+int jpegx_forward_fused_n(const double *d_in, int H, int W, ptrdiff_t pitch, int N, int mode, double param, int32_t *d_out,
+                          jpegx_stream_t stream);
+/* ZigzagOrder.invert + Quantization.invert + BasisChange.invert with its np.round (pipeline/basis_change.py:28-43,
+ * transforms.py:60-69).  flags 0: int32 samples [H][out_pitch], unclamped; JPEGX_F_CLAMP_U8: uint8 samples with the clamp
+ * of pipeline/normalization.py:10-14 fused.                                                                            */
+int jpegx_inverse_fused_n(const int32_t *d_in, int H, int W, int N, int mode, double param, unsigned flags, void *d_out,
+                          ptrdiff_t out_pitch, jpegx_stream_t stream);
+/* the transform alone, plane to plane (the coefficients of a block in place of the block): BasisChange.execute / .invert */
+int jpegx_dct_f64_n(const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch,
+                    jpegx_stream_t stream);
+int jpegx_idct_f64_n(const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch, int do_round,
+                     jpegx_stream_t stream);
+/* The tables the kernels use, host only (no device needed): C[k][n] = cos(pi / N * (n + 0.5) * k) (transforms.py:4-11),
+ * Cn = rows of C scaled to unit length (transforms.py:14-20), Dinv[k] = 1 / |row k| (transforms.py:23-26), zigzag[p] =
+ * i * N + j of the p-th cell of the scan.  C, Cn: N*N doubles; Dinv: N; zigzag: N*N.                                */
+int jpegx_dct_tables_n(int N, double *C, double *Cn, double *Dinv, uint16_t *zigzag);
+/* synchronous host-pointer forms (contiguous planes; arguments are checked before any device is touched; the inverse
+ * writes W samples of every row and leaves the out_pitch - W behind them as the caller had them) */
+int jpegx_host_forward_fused_n(const double *h_in, int H, int W, int N, int mode, double param, int32_t *h_out);
+int jpegx_host_inverse_fused_n(const int32_t *h_in, int H, int W, int N, int mode, double param, unsigned flags, void *h_out,
+                               ptrdiff_t out_pitch);
+int jpegx_host_dct_f64_n(const double *h_in, int H, int W, int N, double *h_out);
+int jpegx_host_idct_f64_n(const double *h_in, int H, int W, int N, double *h_out, int do_round);
+/* The entropy stage for blocks of block_len coefficients (N*N; 1..1024) ON THE HOST, no device needed: the sequential
+ * coder of RunLengthEncoding + RleBytestream (pipeline/run_length_encoding.py:47-97, pipeline/rle_byte_stream.py:48-88).
+ * encode: h_out may be NULL to query the size; an amplitude beyond 15 bits is JPEGX_E_INVALID with "BadRleCodeError" in the
+ * message (util.py:140-149).  decode: the refusals and messages of jpegx_host_entropy_decode.                        */
+int jpegx_host_entropy_encode_n(const int32_t *h_zz, long long nblocks, int block_len, uint8_t *h_out, size_t cap,
+                                size_t *nbytes);
+int jpegx_host_entropy_decode_n(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len, int32_t *h_zz);
 
 /* ---- entropy stage on the device ---------------------------------------
  * Replaces RunLengthEncoding.execute (pipeline/run_length_encoding.py:47-64) + RleBytestream.execute
@@ -546,6 +589,14 @@ int jpegx_host_decompress_image_on(int device, const uint8_t *const *h_bytes, co
                                    int W, int bs, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows,
                                    int cols, int interleave);
 int jpegx_host_entropy_decode_gpu_on(int device, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz);
+int jpegx_forward_fused_n_on(int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, int mode, double param,
+                             int32_t *d_out, jpegx_stream_t stream);
+int jpegx_inverse_fused_n_on(int device, const int32_t *d_in, int H, int W, int N, int mode, double param, unsigned flags,
+                             void *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_dct_f64_n_on(int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch,
+                       jpegx_stream_t stream);
+int jpegx_idct_f64_n_on(int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch,
+                        int do_round, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
