@@ -154,7 +154,12 @@ def _hot_forward_n(pre, config):
     if not reach < 2.0 ** 31:                       # also catches NaN
         return None
     import jpegx
-    return jpegx.forward_fused_n(pre, n, mode, param)
+    zz = jpegx.forward_fused_n(pre, n, mode, param)
+    # a coefficient in [2^31 - 0.5, 2^31) rounds to 2^31, which the kernel saturates to 2^31 - 1: not the reference's
+    # integer, so such a plane stays on the host as well (-2^31 itself is an int32)
+    if reach > 2.0 ** 31 - 1.0 and zz.max() == 2 ** 31 - 1:
+        return None
+    return zz
 
 
 def _hot_inverse_n(zz, config):

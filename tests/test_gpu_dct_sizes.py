@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import dctn_criterion as crit
+from dctn_dev import forward_dev, inverse_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -49,25 +50,6 @@ def ref_dct_of(kind, n, h, w):
     return out
 
 
-def forward_dev(gpu, plane, n, mode, param, pitch=None, on=False, stream=None):
-    """jpegx_forward_fused_n on device pointers: pitch, the _on twin and a stream as asked."""
-    h, w = plane.shape
-    pitch = pitch or w
-    buf = np.full((h, pitch), np.nan)
-    buf[:, :w] = plane
-    din, dout = gpu.DeviceBuffer(buf.nbytes), gpu.DeviceBuffer(h * w * 4)
-    try:
-        din.upload(buf)
-        L = gpu.lib()
-        args = (din.ptr, h, w, pitch, n, gpu.mode_of(mode), float(param), dout.ptr, stream)
-        gpu.check(L.jpegx_forward_fused_n_on(0, *args) if on else L.jpegx_forward_fused_n(*args), "jpegx_forward_fused_n")
-        gpu.check(L.jpegx_stream_synchronize(stream), "sync")
-        return dout.download((h // n, w // n, n * n), np.int32)
-    finally:
-        din.free()
-        dout.free()
-
-
 @pytest.mark.parametrize("n,h,w,pitch", SHAPES)
 def test_forward_fused_n(gpu, n, h, w, pitch):
     from pipeline.zigzag_order import Zigzag
@@ -89,28 +71,6 @@ def test_forward_fused_n(gpu, n, h, w, pitch):
         zz = gpu.forward_fused_n(plane, n, "none")
         assert np.array_equal(zz, np.rint(coef).astype(np.int32).reshape(h // n, n, w // n, n).swapaxes(1, 2)
                               .reshape(h // n, w // n, n * n)[:, :, Zigzag(n).flat_indices()])
-
-
-def inverse_dev(gpu, zz, n, mode, param, u8=False, out_pitch=None, on=False, stream=None):
-    hb, wb, _ = zz.shape
-    h, w = hb * n, wb * n
-    pitch = out_pitch or w
-    esz = 1 if u8 else 4
-    din, dout = gpu.DeviceBuffer(zz.nbytes), gpu.DeviceBuffer(h * pitch * esz)
-    try:
-        din.upload(np.ascontiguousarray(zz, dtype=np.int32))
-        fill = np.full((h, pitch), 77, dtype=np.uint8 if u8 else np.int32)
-        dout.upload(fill)
-        L = gpu.lib()
-        args = (din.ptr, h, w, n, gpu.mode_of(mode), float(param), gpu.F_CLAMP_U8 if u8 else 0, dout.ptr, pitch, stream)
-        gpu.check(L.jpegx_inverse_fused_n_on(0, *args) if on else L.jpegx_inverse_fused_n(*args), "jpegx_inverse_fused_n")
-        gpu.check(L.jpegx_stream_synchronize(stream), "sync")
-        res = dout.download((h, pitch), fill.dtype)
-        assert np.all(res[:, w:] == 77), "the pitch slack was written"
-        return res[:, :w]
-    finally:
-        din.free()
-        dout.free()
 
 
 @pytest.mark.parametrize("n,h,w,pitch", SHAPES)
