@@ -23,6 +23,7 @@
 
 #include "../../include/jpegx.h"
 #include "jpegx_rle_sizes.h"
+#include "jpegx_entropy_ws.h"
 
 extern "C" void jpegx_internal_set_error(const char *msg);  // jpegx_runtime.hip (thread-local string)
 
@@ -33,49 +34,9 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TILE_BYTES = 64 * 128;
 __device__ __forceinline__ int tile_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
-// workspace layout (bytes): [0,8) total, [8,12) error flag, [16, ...) 64-bit byte offset of every
-// scan chunk (SCAN_CHUNK waves), then per wave its total and its 32-bit offset inside the chunk
-// (both 16-byte aligned arrays), then block sizes (u32 x nblocks)
-constexpr int SCAN_CHUNK = 4096;   // waves per level-1 scan workgroup (1024 threads x 4)
-
-struct Workspace {
-    unsigned long long *total;
-    unsigned *error;
-    unsigned long long *chunk_off;   // [nchunks + 1]
-    unsigned *wave_bytes;            // [nw rounded up to SCAN_CHUNK]
-    unsigned *wave_off;              // [nw rounded up to SCAN_CHUNK], offset inside the wave's chunk
-    unsigned *block_bytes;           // [nblocks]
-    unsigned *half_info;             // [nblocks] bits of the codes of coefficients 0..31 | (1 + last non-zero among them) << 12 (forward kernels that size their own blocks)
-};
-
-__host__ __device__ inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-__host__ __device__ inline Workspace carve(void *ws, long long nblocks)
-{
-    const long long nw = (nblocks + 63) / 64;
-    const long long nchunks = (nw + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    unsigned char *p = reinterpret_cast<unsigned char *>(ws);
-    Workspace w;
-    w.total = reinterpret_cast<unsigned long long *>(p);
-    w.error = reinterpret_cast<unsigned *>(p + 8);
-    w.chunk_off = reinterpret_cast<unsigned long long *>(p + 16);
-    size_t off = align16(16 + (size_t)(nchunks + 1) * 8);
-    w.wave_bytes = reinterpret_cast<unsigned *>(p + off);
-    off += (size_t)nchunks * SCAN_CHUNK * 4;
-    w.wave_off = reinterpret_cast<unsigned *>(p + off);
-    off += (size_t)nchunks * SCAN_CHUNK * 4;
-    w.block_bytes = reinterpret_cast<unsigned *>(p + off);
-    off += align16((size_t)nblocks * 4);
-    w.half_info = reinterpret_cast<unsigned *>(p + off);
-    return w;
-}
-
-size_t workspace_bytes(long long nblocks)
-{
-    const long long nw = (nblocks + 63) / 64;
-    const long long nchunks = (nw + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    return align16(16 + (size_t)(nchunks + 1) * 8) + 2 * (size_t)nchunks * SCAN_CHUNK * 4 + 2 * align16((size_t)nblocks * 4);
-}
+// the workspace (total, error flag, chunk / wave offsets, block sizes, half_info): jpegx_entropy_ws.h, shared with the
+// run-time block length stage (jpegx_entropy_n.hip)
+using namespace jpegx_entropy_ws;
 
 // the wave's 64 x 128 B of coefficients -> swizzled LDS tile (LDS-DMA, as in k_inverse_fused)
 __device__ __forceinline__ void stage_tile(const int16_t *__restrict__ zz, int g0, int nblk, int lane, unsigned char *lds)

@@ -501,6 +501,57 @@ int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int row
     return compress_begin_impl(h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, nbytes, true);
 }
 
+// The band job for dct_size N (2..32): the float64 plane that leaves step 3 up, jpegx_forward_fused_n, the run-time block
+// length entropy stage (csrc/jpegx_entropy_n.hip), the bytes left in slot 0's d_out for _finish.  The emitter is enqueued
+// once the size is known: a block of N * N coefficients has no small worst case to size the destination by beforehand.
+int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param, size_t *nbytes)
+{
+    if (!h_plane || !nbytes) return fail(JPEGX_E_INVALID, "null pointer");
+    if (N < 2 || N > 32) return fail(JPEGX_E_INVALID, "dct_size must be 2 .. 32");
+    if (H <= 0 || W <= 0 || (H % N) != 0 || (W % N) != 0) return fail(JPEGX_E_INVALID, "plane height and width must be positive multiples of dct_size");
+    if (pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if ((long long)H * W > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one plane");
+    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE)
+        return fail(JPEGX_E_INVALID, "dct_size other than 8 takes the quantisers none, discard and divide");
+    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
+        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
+    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
+        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
+    const long long nblocks = (long long)(H / N) * (W / N);
+    const int len = N * N;
+    DevicePool *pool = nullptr;
+    int rc;
+    if ((rc = lock_pool(&pool))) return rc;
+    auto bail = [&](int code) { unlock_pool(pool); return code; };
+    if ((rc = ensure_streams(pool, false))) return bail(rc);
+    BandSlot &slot = pool->slot[0];
+    hipStream_t st = pool->stream;
+    if ((rc = slot.d_in.ensure((size_t)H * W * 8)) || (rc = slot.d_zz.ensure((size_t)H * W * 4)) ||
+        (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len))) || (rc = pool->h_head.ensure(16 * MAX_BANDS)))
+        return bail(rc);
+    auto drain = [&](int code) { (void)hipStreamSynchronize(st); return bail(code); };
+    hipError_t e = pitch == W ? hipMemcpyAsync(slot.d_in.p, h_plane, (size_t)H * W * 8, hipMemcpyHostToDevice, st)
+                              : hipMemcpy2DAsync(slot.d_in.p, (size_t)W * 8, h_plane, (size_t)pitch * 8, (size_t)W * 8, (size_t)H, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { (void)hipGetLastError(); return drain(fail(JPEGX_E_HIP, "host to device copy failed")); }
+    const int32_t *d_zz = static_cast<const int32_t *>(slot.d_zz.p);
+    if ((rc = jpegx_forward_fused_n(static_cast<const double *>(slot.d_in.p), H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
+        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)))
+        return drain(rc);
+    unsigned long long *head = static_cast<unsigned long long *>(pool->h_head.p);
+    if (hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError();
+        return drain(fail(JPEGX_E_HIP, "device to host copy failed"));
+    }
+    unsigned long long total = 0;
+    if ((rc = head_verdict(head, &total))) return bail(rc);          // an amplitude beyond 15 bits: the stream is idle, the context goes back
+    if ((rc = slot.d_out.ensure((size_t)total + 64))) return bail(rc);
+    if ((rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st))) return drain(rc);
+    pool->open = true;
+    pool->out_bytes = (size_t)total;
+    *nbytes = (size_t)total;
+    return JPEGX_OK;                       // the pool stays locked (and t_held set) until _finish / _abort
+}
+
 int jpegx_host_compress_finish(uint8_t *h_out)
 {
     DevicePool *pool = t_held;             // this thread's open job, whatever its current device is by now

@@ -104,3 +104,9 @@ JPEGX_ON(jpegx_dct_f64_n, (int device, const double *d_in, int H, int W, ptrdiff
          (d_in, H, W, pitch, N, d_out, out_pitch, stream))
 JPEGX_ON(jpegx_idct_f64_n, (int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch, int do_round, jpegx_stream_t stream),
          (d_in, H, W, pitch, N, d_out, out_pitch, do_round, stream))
+JPEGX_ON(jpegx_entropy_sizes_n, (int device, const int32_t *d_zz, long long nblocks, int block_len, void *d_workspace, jpegx_stream_t stream),
+         (d_zz, nblocks, block_len, d_workspace, stream))
+JPEGX_ON(jpegx_entropy_emit_n, (int device, const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace, uint8_t *d_out, jpegx_stream_t stream),
+         (d_zz, nblocks, block_len, d_workspace, d_out, stream))
+JPEGX_ON(jpegx_host_compress_begin_n, (int device, const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param, size_t *nbytes),
+         (h_plane, H, W, pitch, N, mode, param, nbytes))

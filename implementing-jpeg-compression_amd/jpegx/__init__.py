@@ -139,6 +139,10 @@ SIGNATURES = {
     "jpegx_entropy_block_sizes": [_vp, _c.c_longlong, _vp, _vp],
     "jpegx_entropy_emit": [_vp, _c.c_longlong, _vp, _vp, _vp],
     "jpegx_host_entropy_encode": [_vp, _c.c_longlong, _vp, _sz, _c.POINTER(_sz)],
+    "jpegx_entropy_workspace_bytes_n": [_c.c_longlong, _int],
+    "jpegx_entropy_sizes_n": [_vp, _c.c_longlong, _int, _vp, _vp],
+    "jpegx_entropy_emit_n": [_vp, _c.c_longlong, _int, _vp, _vp, _vp],
+    "jpegx_host_compress_begin_n": [_vp, _int, _int, _pd, _int, _int, _dbl, _c.POINTER(_sz)],
     "jpegx_host_entropy_decode": [_vp, _sz, _c.c_longlong, _vp],
     "jpegx_entropy_decode_workspace_bytes": [_sz, _c.c_longlong],
     "jpegx_entropy_decode": [_vp, _sz, _c.c_longlong, _vp, _vp, _int, _vp],
@@ -179,9 +183,10 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_decompress_plane_i64", "jpegx_host_decompress_image", "jpegx_host_entropy_decode_gpu",
               "jpegx_host_pool_release", "jpegx_comm_create_deadline", "jpegx_pad_edges", "jpegx_host_compress_begin_ragged",
               "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged", "jpegx_forward_fused_n",
-              "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n"):
+              "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n", "jpegx_entropy_sizes_n", "jpegx_entropy_emit_n",
+              "jpegx_host_compress_begin_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
-RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
+RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
 
 
@@ -1021,20 +1026,69 @@ def idct_f64_n(plane, n, do_round=True):
     return out
 
 
-def entropy_encode_n(zz, block_len=None):
-    """int32 (..., block_len) zigzag stream -> bytes: RunLengthEncoding.execute + RleBytestream.execute for blocks of any
-    length, sequentially on the host (no device needed)."""
+def _stream_any_n(zz, block_len):
+    """The argument checks of entropy_encode_n and entropy_encode_n_gpu: (contiguous int32 stream, block_len, nblocks)."""
     z = np.ascontiguousarray(zz, dtype=np.int32)
     block_len = int(z.shape[-1] if block_len is None and z.ndim else block_len or 0)
     if z.size == 0 or block_len < 1 or z.size % block_len:
         raise JpegxError("expected a non-empty stream of whole blocks of %d coefficients, got %r" % (block_len, z.shape))
-    nblocks = z.size // block_len
+    return z, block_len, z.size // block_len
+
+
+def entropy_encode_n(zz, block_len=None):
+    """int32 (..., block_len) zigzag stream -> bytes: RunLengthEncoding.execute + RleBytestream.execute for blocks of any
+    length, sequentially on the host (no device needed)."""
+    z, block_len, nblocks = _stream_any_n(zz, block_len)
     n = ctypes.c_size_t(0)
     L = lib()
     check(L.jpegx_host_entropy_encode_n(z.ctypes.data, nblocks, block_len, None, 0, ctypes.byref(n)), "jpegx_host_entropy_encode_n")
     blob = _pyapi.PyBytes_FromStringAndSize(None, n.value)          # uninitialised bytes, filled below
     check(L.jpegx_host_entropy_encode_n(z.ctypes.data, nblocks, block_len, _pyapi.PyBytes_AsString(blob), n.value, ctypes.byref(n)),
           "jpegx_host_entropy_encode_n")
+    return blob
+
+
+def entropy_encode_n_gpu(zz, block_len=None):
+    """entropy_encode_n on the device (csrc/jpegx_entropy_n.hip): upload, jpegx_entropy_sizes_n, jpegx_entropy_total,
+    jpegx_entropy_emit_n, download.  Same bytes, same refusals."""
+    z, block_len, nblocks = _stream_any_n(zz, block_len)
+    L = lib()
+    ws_bytes = L.jpegx_entropy_workspace_bytes_n(nblocks, block_len)
+    if ws_bytes == 0:
+        raise JpegxError("the device coder takes blocks of 1 .. 1024 coefficients and streams below 2^31 coefficients, got %r" % (z.shape,))
+    dzz, dws, dout = DeviceBuffer(z.nbytes), DeviceBuffer(ws_bytes), None
+    try:
+        dzz.upload(z)
+        check(L.jpegx_entropy_sizes_n(dzz.ptr, nblocks, block_len, dws.ptr, None), "jpegx_entropy_sizes_n")
+        total = ctypes.c_ulonglong(0)
+        check(L.jpegx_entropy_total(dws.ptr, ctypes.byref(total), None), "jpegx_entropy_total")
+        dout = DeviceBuffer(max(total.value, 1))
+        check(L.jpegx_entropy_emit_n(dzz.ptr, nblocks, block_len, dws.ptr, dout.ptr, None), "jpegx_entropy_emit_n")
+        return dout.download((total.value,), np.uint8).tobytes()
+    finally:
+        dzz.free()
+        dws.free()
+        if dout is not None:
+            dout.free()
+
+
+def compress_plane_n(plane, n, mode="none", param=0.0):
+    """float64 plane (H, W) of whole n x n blocks -> bytes: steps 4-8 for dct_size n as one pooled device job
+    (jpegx_host_compress_begin_n / _finish) -- what entropy_encode_n(forward_fused_n(plane, n, mode, param)) returns, without
+    the coefficient stream leaving the device.  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits."""
+    a, n = _plane_n(plane, n)
+    h, w = a.shape
+    L = lib()
+    nbytes = ctypes.c_size_t(0)
+    check(L.jpegx_host_compress_begin_n(a.ctypes.data, h, w, w, n, mode_of(mode), float(param), ctypes.byref(nbytes)),
+          "jpegx_host_compress_begin_n")
+    try:
+        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes.value)      # uninitialised bytes, filled below
+        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
+    except BaseException:
+        L.jpegx_host_compress_abort()
+        raise
+    check(rc, "jpegx_host_compress_finish")
     return blob
 
 

@@ -8,7 +8,9 @@ with the step-by-step float64 pipeline.  There is no CPU fallback for the accele
 configuration: without libjpegx.so or a GPU the call raises ``jpegx.JpegxError``.
 
 Any other dct_size 2..32 with transform 'DCT' takes the all-float64 kernels of csrc/jpegx_dctn.hip
-(``jpegx_forward_fused_n`` / ``jpegx_inverse_fused_n``, entropy stage by libjpegx's sequential host coder) when a
+(``jpegx_forward_fused_n`` / ``jpegx_inverse_fused_n``, entropy stage by libjpegx's sequential host coder; with
+``DCTN_ENTROPY_MIN_SAMPLES`` set, compressing runs the entropy stage on the device behind the forward kernel,
+csrc/jpegx_entropy_n.hip) when a
 device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
 NumPy road runs, exactly as the reference does it.
 """
@@ -107,6 +109,12 @@ class Configuration:
 # of a few blocks are what unit tests and a machine's first steps with the step classes use
 DCTN_MIN_SAMPLES = 1024
 
+# The device entropy stage behind the forward kernel as one job (jpegx.compress_plane_n): planes of at least this many
+# samples take it; None: the job road is off and compress_band keeps jpegx_forward_fused_n + the host coder.  Measured
+# (profiles/dctn_entropy.json): the job road is 5-7x faster on a 3000 x 4000 band and wins from 16384 samples
+# on, loses 13-17 us below, and lost 3 % at one N = 24 size above -- so it is not the default; 16384 is the value to set.
+DCTN_ENTROPY_MIN_SAMPLES = None
+
 _device_seen = False
 
 
@@ -178,10 +186,39 @@ def _hot_inverse_n(zz, config):
     return jpegx.inverse_fused_n(zz, n, *args).astype(int)
 
 
+def _device_job_n(pre, config):
+    """Steps 4-8 for dct_size N as one pooled device job (jpegx.compress_plane_n: forward kernel + the run-time block length
+    entropy stage, the coefficient stream never leaves the device), or None: the job road is switched off
+    (DCTN_ENTROPY_MIN_SAMPLES), _hot_forward_n's preconditions do not hold, a coefficient could reach 2^31 - 1 (where the
+    kernel's saturation would go unseen), or the job met an amplitude beyond 15 bits -- the caller's road then ends in the
+    host step raising the reference's BadRleCodeError with its own text."""
+    n = config.dct_size
+    pre = np.asarray(pre)
+    args = _dctn_mode(config)
+    if DCTN_ENTROPY_MIN_SAMPLES is None or pre.size < DCTN_ENTROPY_MIN_SAMPLES:
+        return None
+    if args is None or pre.ndim != 2 or pre.dtype.kind not in "fiu" or not dctn_on_device(config, pre.size) \
+            or pre.shape[0] % n or pre.shape[1] % n:
+        return None
+    mode, param = args
+    pre = pre.astype(np.float64, copy=False)
+    reach = max(abs(float(pre.max())), abs(float(pre.min()))) * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0)
+    if not reach <= 2.0 ** 31 - 1.0:                # also catches NaN
+        return None
+    import jpegx
+    try:
+        return jpegx.compress_plane_n(pre, n, mode, param)
+    except jpegx.JpegxError as exc:
+        if "BadRleCodeError" not in str(exc):
+            raise
+        return None
+
+
 def _compress_band_n(a, config):
-    """compress_band for dct_size != 8 with the three hot steps as one device launch: host steps 0-3 as they are,
-    jpegx_forward_fused_n, then -- in a stock registry -- libjpegx's sequential entropy coder.  None when the road does
-    not apply; the caller then walks the steps on the host as before."""
+    """compress_band for dct_size != 8: host steps 0-3 as they are, then the three hot steps as one device launch
+    (jpegx_forward_fused_n) and -- in a stock registry -- libjpegx's sequential entropy coder on the host; or, where the
+    job road is switched on (DCTN_ENTROPY_MIN_SAMPLES) and the registry is stock, steps 4-8 as one device job
+    (_device_job_n).  None when the road does not apply; the caller then walks the steps on the host as before."""
     import jpegx
     todo = list(step_classes)
     at = _hot_run(todo)
@@ -189,6 +226,10 @@ def _compress_band_n(a, config):
         return None
     for cls in todo[:at]:
         a = cls(config).execute(a)
+    if _stock_registry():
+        blob = _device_job_n(a, config)
+        if blob is not None:
+            return blob                             # steps 4-8 in one device job
     zz = _hot_forward_n(a, config)
     rest = todo[at + 3:]
     if zz is None:

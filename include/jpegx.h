@@ -294,6 +294,18 @@ int jpegx_entropy_emit(const int16_t *d_zz, long long nblocks, const void *d_wor
 /* host convenience; h_out may be NULL to query the size only */
 int jpegx_host_entropy_encode(const int16_t *h_zz, long long nblocks, uint8_t *h_out, size_t cap,
                               size_t *nbytes);
+/* The same stage for blocks of a RUN-TIME length (dct_size 2..32: block_len = N*N; any 1..1024 is taken): int32 stream
+ * [nblocks][block_len] -> the bytes of jpegx_host_entropy_encode_n, i.e. RunLengthEncoding.execute
+ * (pipeline/run_length_encoding.py:47-64) + RleBytestream.execute (pipeline/rle_byte_stream.py:48-59) with
+ * util.RunLengthCode (util.py:134-221).  Parallel over coefficients (csrc/jpegx_entropy_n.hip).  Same usage and the same
+ * workspace layout as above: jpegx_entropy_sizes_n (enqueue: sizes, group totals, scans) -> jpegx_entropy_total /
+ * jpegx_entropy_block_sizes (as they are) -> jpegx_entropy_emit_n (enqueue; writes nothing at all when the sizes pass
+ * flagged an amplitude beyond 15 bits, util.py:140-149).  d_zz 4-byte, d_workspace 16-byte aligned; nblocks * block_len
+ * below 2^31; d_out may start at any byte.  A workspace may be reused from call to call without clearing.        */
+size_t jpegx_entropy_workspace_bytes_n(long long nblocks, int block_len);
+int jpegx_entropy_sizes_n(const int32_t *d_zz, long long nblocks, int block_len, void *d_workspace, jpegx_stream_t stream);
+int jpegx_entropy_emit_n(const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace, uint8_t *d_out,
+                         jpegx_stream_t stream);
 
 /* Inverse of the entropy stage ON THE DEVICE, device pointers in and out (what jpegx_host_entropy_decode_gpu and the
  * jpegx_host_decompress_* jobs run on their pooled buffers): RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) +
@@ -456,6 +468,15 @@ int jpegx_host_compress_abort(void);
  * a padded row of 8 mod 16 samples takes the float64 road (same bytes) instead of JPEGX_E_UNSUPPORTED.             */
 int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs,
                                      int mode, double param, size_t *nbytes);
+/* _begin for dct_size N in 2..32 on the plane that leaves step 3 (float64 [H][pitch], H and W whole N x N blocks, fewer
+ * than 2^31 samples): upload, jpegx_forward_fused_n (BasisChange + Quantization + ZigzagOrder.execute, pipeline/
+ * basis_change.py:11-18, quantization.py:8-18, zigzag_order.py:85-99), jpegx_entropy_sizes_n, the size read back,
+ * jpegx_entropy_emit_n (RunLengthEncoding + RleBytestream.execute, pipeline/run_length_encoding.py:47-64,
+ * rle_byte_stream.py:48-59) -- the coefficient stream never leaves the device.  _finish and _abort as above.  An
+ * amplitude beyond 15 bits is JPEGX_E_INVALID with "BadRleCodeError" in the message (util.py:140-149); the job context is
+ * given back and no job is open then.                                                                             */
+int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param,
+                                size_t *nbytes);
 /* The way back (decompress_band, pipeline/__init__.py:79-88, transform 'DCT', dct_size 8): the band's byte
  * stream up, RleBytestream.invert + RunLengthEncoding.invert (pipeline/rle_byte_stream.py:61-88,
  * pipeline/run_length_encoding.py:66-97) ON THE DEVICE -- the stream has no index, block starts are recovered
@@ -597,6 +618,12 @@ int jpegx_dct_f64_n_on(int device, const double *d_in, int H, int W, ptrdiff_t p
                        jpegx_stream_t stream);
 int jpegx_idct_f64_n_on(int device, const double *d_in, int H, int W, ptrdiff_t pitch, int N, double *d_out, ptrdiff_t out_pitch,
                         int do_round, jpegx_stream_t stream);
+int jpegx_entropy_sizes_n_on(int device, const int32_t *d_zz, long long nblocks, int block_len, void *d_workspace,
+                             jpegx_stream_t stream);
+int jpegx_entropy_emit_n_on(int device, const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace,
+                            uint8_t *d_out, jpegx_stream_t stream);
+int jpegx_host_compress_begin_n_on(int device, const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode,
+                                   double param, size_t *nbytes);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
