@@ -10,49 +10,14 @@
 // is the plane index (k_plane_index, jpegx_entropy.hip) and, on the way back, the cut into groups of whole planes that
 // one decode call can take.  Nothing is allocated here except the whole-stream decoder's scratch (level 2 of the
 // ladder), which is sized from a count read back from the device and therefore cannot be the caller's.
-#include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdint.h>
-#include <stdio.h>
 
 #include <mutex>
 
-#include "../../include/jpegx.h"
 #include "jpegx_entropy_decode.h"
-
-extern "C" void jpegx_internal_set_error(const char *msg);
-extern "C" int jpegx_internal_forward_u8_sized(const uint8_t *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, unsigned flags,
-                                               int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, jpegx_stream_t stream);
-extern "C" int jpegx_internal_forward_f32_sized(const float *d_in, int H, int W, ptrdiff_t pitch, int mode, double param, unsigned flags,
-                                                int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, int *sized,
-                                                jpegx_stream_t stream);
-extern "C" void jpegx_internal_entropy_views(void *d_workspace, long long nblocks, unsigned **block_bytes, unsigned **wave_bytes, unsigned **half_info);
-extern "C" int jpegx_internal_entropy_sizes_half(const int16_t *d_zz, long long nblocks, void *d_workspace, jpegx_stream_t stream);
-extern "C" int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);
-extern "C" int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
-                                                  jpegx_stream_t stream);
-extern "C" int jpegx_internal_entropy_emit2_guarded(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, size_t out_cap,
-                                                    jpegx_stream_t stream);
+#include "jpegx_shared.h"
 
 namespace {
-
-int fail(int code, const char *msg)
-{
-    jpegx_internal_set_error(msg);
-    return code;
-}
-
-#define B_TRY(expr)                                                                         \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
-            char buf_[400];                                                                 \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));    \
-            jpegx_internal_set_error(buf_);                                                 \
-            return JPEGX_E_HIP;                                                             \
-        }                                                                                   \
-    } while (0)
 
 constexpr unsigned long long SIZES_ONLY = ~0ull;       // the capacity noted by a compress without destination
 constexpr long long MAX_BLOCKS = 0x7FFFFFC0LL;
@@ -182,7 +147,7 @@ struct WorkspaceLadder final : jpegx_decode::Ladder {
     int phase2_memory(size_t bytes, void **d_ws2) override
     {
         int dev = 0;
-        B_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipGetDevice(&dev));
         if (dev < 0 || dev >= MAX_DEVICES) return fail(JPEGX_E_UNSUPPORTED, "device index beyond the scratch table");
         Level2Scratch &s = g_level2[dev];
         level2 = std::unique_lock<std::mutex>(s.mu);
@@ -190,7 +155,7 @@ struct WorkspaceLadder final : jpegx_decode::Ladder {
             if (s.p) (void)hipFree(s.p);
             s.p = nullptr;
             s.cap = 0;
-            B_TRY(hipMalloc(&s.p, bytes + bytes / 8));
+            HIP_TRY(hipMalloc(&s.p, bytes + bytes / 8));
             s.cap = bytes + bytes / 8;
         }
         *d_ws2 = s.p;
@@ -288,11 +253,11 @@ int jpegx_batch_compress_status(const void *d_workspace, int nplanes, int H, int
     const CompressWs c = carve_compress(const_cast<void *>(d_workspace), nplanes, nb * nplanes);
     unsigned long long ehead[2] = {0, 0}, bhead[2] = {0, 0};
     hipStream_t st = (hipStream_t)stream;
-    B_TRY(hipMemcpyAsync(ehead, c.ews, 16, hipMemcpyDeviceToHost, st));
-    B_TRY(hipMemcpyAsync(bhead, c.index, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ehead, c.ews, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bhead, c.index, 16, hipMemcpyDeviceToHost, st));
     if (h_plane_offsets)
-        B_TRY(hipMemcpyAsync(h_plane_offsets, static_cast<const unsigned char *>(c.index) + 16, ((size_t)nplanes + 1) * 8, hipMemcpyDeviceToHost, st));
-    B_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(h_plane_offsets, static_cast<const unsigned char *>(c.index) + 16, ((size_t)nplanes + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *h_total = ehead[0];
     if ((unsigned)(ehead[1] & 0xFFFFFFFFull) != 0)
         return fail(JPEGX_E_INVALID, "BadRleCodeError: an amplitude needs more than 15 bits (|a| > 16383); nothing was written");
@@ -355,8 +320,8 @@ int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_p
             return fail(JPEGX_E_INVALID, where);
         }
         // the group's bytes, dword aligned and with zeros behind them, as the decoder wants them
-        B_TRY(hipMemsetAsync(lad.w.stage + ((size_t)gbytes & ~(size_t)3), 0, 16 + ((size_t)gbytes & 3), st));
-        B_TRY(hipMemcpyAsync(lad.w.stage, d_bytes + h_plane_offsets[p0], (size_t)gbytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(lad.w.stage + ((size_t)gbytes & ~(size_t)3), 0, 16 + ((size_t)gbytes & 3), st));
+        HIP_TRY(hipMemcpyAsync(lad.w.stage, d_bytes + h_plane_offsets[p0], (size_t)gbytes, hipMemcpyDeviceToDevice, st));
         rc = jpegx_decode::LADDER_NEXT_LEVEL;
         for (int level = 0; level < 3 && rc == jpegx_decode::LADDER_NEXT_LEVEL; ++level) {      // planned segments, 256-byte segments, the whole stream
             rc = jpegx_decode::ladder_enqueue(lad, lad.w.stage, (size_t)gbytes, gblocks, lad.w.zz, st, level);
@@ -364,13 +329,13 @@ int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_p
                 const hipError_t e = hipStreamSynchronize(st);
                 if (e != hipSuccess) {
                     if (lad.level2.owns_lock()) lad.level2.unlock();
-                    B_TRY(e);
+                    HIP_TRY(e);
                 }
                 rc = jpegx_decode::ladder_status(lad);
             }
             if (lad.level2.owns_lock()) lad.level2.unlock();
         }
-        if (rc == jpegx_decode::LADDER_NEXT_LEVEL) rc = fail(JPEGX_E_INVALID, "device decoder: no scheme took the stream");
+        if (rc == jpegx_decode::LADDER_NEXT_LEVEL) rc = jpegx_decode::ladder_exhausted();
         if (rc == JPEGX_E_INVALID) {
             snprintf(where, sizeof(where), "batch_decompress: planes %d..%d: their %llu bytes are not %lld well-formed blocks (%.80s)", p0, p1 - 1, gbytes,
                      gblocks, jpegx_last_error());

@@ -24,8 +24,8 @@
 #include "../../include/jpegx.h"
 #include "jpegx_rle_sizes.h"
 #include "jpegx_entropy_ws.h"
+#include "jpegx_shared.h"
 
-extern "C" void jpegx_internal_set_error(const char *msg);  // jpegx_runtime.hip (thread-local string)
 
 namespace {
 
@@ -436,23 +436,6 @@ __global__ __launch_bounds__(128) void k_rle_emit2(const int16_t *__restrict__ z
         }
     }
 }
-
-int fail(int code, const char *msg)
-{
-    jpegx_internal_set_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
-            char buf_[400];                                                                \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));   \
-            return fail(JPEGX_E_HIP, buf_);                                                \
-        }                                                                                  \
-    } while (0)
 
 int check_args(const void *zz, long long nblocks, const void *ws)
 {

@@ -1,5 +1,6 @@
 // jpegx_entropy_decode.h -- internal interface between the device entropy decoder's kernels
-// (jpegx_entropy_decode.hip) and the host orchestration that owns the buffers (jpegx_hostpipe.cpp).
+// (jpegx_entropy_decode.hip), the level ladder over them (jpegx_decode_ladder.cpp) and the host orchestration that
+// owns the buffers (jpegx_hostpipe.cpp, jpegx_batch.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -59,4 +60,7 @@ protected:
 int ladder_enqueue(Ladder &lad, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int16_t *d_zz, hipStream_t st, int level);
 // once the stream has been synchronised: JPEGX_OK, JPEGX_E_INVALID (not a sequence of well-formed blocks) or LADDER_NEXT_LEVEL
 int ladder_status(Ladder &lad);
+__attribute__((visibility("hidden"))) int ladder_exhausted();      // the refusal of a stream that the last rung handed on as well (JPEGX_E_INVALID, message set)
+// the ranges one decode call takes: 1 .. 2^31-64 blocks, a stream of 1 byte .. just below 4 GiB (message set otherwise)
+__attribute__((visibility("hidden"))) int check_stream_args(size_t nbytes, long long nblocks);
 }  // namespace jpegx_decode

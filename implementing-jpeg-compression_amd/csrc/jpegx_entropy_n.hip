@@ -26,9 +26,8 @@
 
 #include "../../include/jpegx.h"
 #include "jpegx_entropy_ws.h"
+#include "jpegx_shared.h"
 
-extern "C" void jpegx_internal_set_error(const char *msg);  // jpegx_runtime.hip (thread-local string)
-extern "C" int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);   // jpegx_entropy.hip
 
 namespace {
 
@@ -260,23 +259,6 @@ __global__ __launch_bounds__(64) void k_emit_n(const int32_t *__restrict__ zz, i
         }
     }
 }
-
-int fail(int code, const char *msg)
-{
-    jpegx_internal_set_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
-            char buf_[400];                                                                \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));   \
-            return fail(JPEGX_E_HIP, buf_);                                                \
-        }                                                                                  \
-    } while (0)
 
 int check_args(const void *zz, long long nblocks, int block_len, const void *ws)
 {

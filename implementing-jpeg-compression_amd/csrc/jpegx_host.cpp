@@ -9,9 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/jpegx.h"
-
-extern "C" void jpegx_internal_set_error(const char *msg);
+#include "jpegx_shared.h"
 
 namespace {
 
@@ -42,11 +40,7 @@ struct BitCursor {
     void align_to_byte() { bitpos = (bitpos + 7) & ~(size_t)7; }   // drop the zero padding after an EOB
 };
 
-int fail(const char *msg)
-{
-    jpegx_internal_set_error(msg);
-    return JPEGX_E_INVALID;
-}
+int fail(const char *msg) { return fail(JPEGX_E_INVALID, msg); }
 
 }  // namespace
 

@@ -11,9 +11,6 @@
 // reference.  The _ragged entries take a band of any rows x cols: it is uploaded into a device plane of the padded shape
 // and the margins are filled there (jpegx_pad_edges: steps 0 and 2, pipeline/padding.py:8-12 + pipeline/dct_padding.py:8-9);
 // the entries without that suffix are the same job with rows = H * bs, cols = W * bs -- no margin, no extra launch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -25,37 +22,10 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/jpegx.h"
 #include "jpegx_entropy_decode.h"
-
-extern "C" void jpegx_internal_set_error(const char *msg);
-// the uint8 forward kernels sizing their own blocks for the entropy stage (jpegx_forward.hip, jpegx_entropy.hip)
-extern "C" int jpegx_internal_forward_u8_sized(const uint8_t *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, unsigned flags,
-                                               int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, jpegx_stream_t stream);
-extern "C" void jpegx_internal_entropy_views(void *d_workspace, long long nblocks, unsigned **block_bytes, unsigned **wave_bytes, unsigned **half_info);
-extern "C" int jpegx_internal_entropy_emit2(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
-extern "C" int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);
-extern "C" void jpegx_internal_batch_scratch_release(void);
+#include "jpegx_shared.h"
 
 namespace {
-
-int fail(int code, const char *msg)
-{
-    jpegx_internal_set_error(msg);
-    return code;
-}
-
-#define HP_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
-            char buf_[400];                                                                 \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));    \
-            jpegx_internal_set_error(buf_);                                                 \
-            return JPEGX_E_HIP;                                                             \
-        }                                                                                   \
-    } while (0)
 
 // a grow-only allocation (device or pinned host)
 struct Span {
@@ -71,7 +41,7 @@ struct Span {
             cap = 0;
         }
         const size_t want = bytes + bytes / 8 + 4096;          // head room: similar bands follow
-        if (pinned) HP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault)); else HP_TRY(hipMalloc(&p, want));
+        if (pinned) HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault)); else HIP_TRY(hipMalloc(&p, want));
         cap = want;
         return JPEGX_OK;
     }
@@ -155,7 +125,7 @@ thread_local int t_held_device = -1;
 int lock_pool(DevicePool **out)
 {
     int dev = 0;
-    HP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= MAX_DEVICES) return fail(JPEGX_E_UNSUPPORTED, "device index beyond the pool table");
     if (t_held != nullptr)
         return fail(JPEGX_E_INVALID, t_held->open ? "a compress job is open on this thread: finish or abort it first"
@@ -182,25 +152,59 @@ void unlock_pool(DevicePool *pool)
     }
 }
 
-struct PoolLock {     // scope form
-    DevicePool *pool = nullptr;
-    int rc;
-    PoolLock() { rc = lock_pool(&pool); }
-    ~PoolLock() { if (pool) unlock_pool(pool); }
-};
-
 int ensure_streams(DevicePool *pool, bool image)
 {
-    if (!pool->stream) HP_TRY(hipStreamCreateWithFlags(&pool->stream, hipStreamNonBlocking));
-    if (!pool->ev[0]) HP_TRY(hipEventCreateWithFlags(&pool->ev[0], hipEventDisableTiming));      // band jobs wait on it for the stream's size
+    if (!pool->stream) HIP_TRY(hipStreamCreateWithFlags(&pool->stream, hipStreamNonBlocking));
+    if (!pool->ev[0]) HIP_TRY(hipEventCreateWithFlags(&pool->ev[0], hipEventDisableTiming));      // band jobs wait on it for the stream's size
     if (image) {
         for (int i = 0; i < 2; ++i)
-            if (!pool->aux[i]) HP_TRY(hipStreamCreateWithFlags(&pool->aux[i], hipStreamNonBlocking));
+            if (!pool->aux[i]) HIP_TRY(hipStreamCreateWithFlags(&pool->aux[i], hipStreamNonBlocking));
         for (int i = 0; i < MAX_BANDS; ++i)
-            if (!pool->ev[i]) HP_TRY(hipEventCreateWithFlags(&pool->ev[i], hipEventDisableTiming));
-        if (!pool->ev_x) HP_TRY(hipEventCreateWithFlags(&pool->ev_x, hipEventDisableTiming));
+            if (!pool->ev[i]) HIP_TRY(hipEventCreateWithFlags(&pool->ev[i], hipEventDisableTiming));
+        if (!pool->ev_x) HIP_TRY(hipEventCreateWithFlags(&pool->ev_x, hipEventDisableTiming));
     }
     return JPEGX_OK;
+}
+
+// One job on one context: the lock, and the streams the job puts its work on.  Whatever way the job leaves -- unless it
+// says done() (its own last step was to synchronise) or hold() -- the destructor waits for those streams before the
+// context goes back to other threads: their jobs would otherwise regrow buffers that kernels still read, or reuse pinned
+// staging that a copy still writes.  The wait's own result is dropped: the job's code and message are the ones to report.
+struct Job {
+    DevicePool *pool = nullptr;
+    int rc;                                    // of taking the lock
+    hipStream_t used[2] = {nullptr, nullptr};
+    bool settled = false, held = false;
+    Job() { rc = lock_pool(&pool); }
+    Job(const Job &) = delete;
+    int streams(bool image)                    // create them where missing; from here on the job may enqueue
+    {
+        const int r = ensure_streams(pool, image);
+        if (!r) { used[0] = image ? pool->aux[0] : pool->stream; used[1] = image ? pool->aux[1] : nullptr; }
+        return r;
+    }
+    int done() { settled = true; return JPEGX_OK; }
+    int hold() { held = true; return JPEGX_OK; }      // the context stays this thread's beyond the call (t_held): an open compress job, a borrowed working set
+    ~Job()
+    {
+        if (!pool || held) return;
+        if (!settled) {
+            for (hipStream_t st : used)
+                if (st) (void)hipStreamSynchronize(st);
+            (void)hipGetLastError();
+        }
+        unlock_pool(pool);
+    }
+};
+
+// Host threads for a pass over `samples` samples: one below 2^20 of them (starting threads costs more than they gain),
+// else what the variable `env` says (`dflt` where it is not set) within 1 .. hardware_concurrency.
+int host_threads(const char *env, int dflt, size_t samples)
+{
+    if (samples < (1u << 20)) return 1;
+    const char *e = getenv(env);
+    const int want = e && *e ? atoi(e) : dflt, hw = (int)std::thread::hardware_concurrency();
+    return want < 1 || hw < 1 ? 1 : (want < hw ? want : hw);
 }
 
 // Wide integers -> bytes in the pinned staging area, checking 0..255 on the way, and up to the device -- in strips, each
@@ -212,9 +216,7 @@ int ensure_streams(DevicePool *pool, bool image)
 template <typename T>
 int narrow_and_upload(const T *src, ptrdiff_t src_pitch, int H, int W, uint8_t *stage, void *d_dst, ptrdiff_t dst_pitch, hipStream_t st)
 {
-    const unsigned hw = std::thread::hardware_concurrency();
-    static const int want = [] { const char *e = getenv("JPEGX_NARROW_THREADS"); return e && *e ? atoi(e) : 8; }();      // 8 / 16 / 32: 1.26-1.57 / 1.38-1.99 / 1.33-1.94 ms per int64 band (starting the threads costs more than sixteen gain)
-    const int nthreads = ((size_t)H * W < (1u << 20)) ? 1 : ((int)hw >= want ? (want > 0 ? want : 1) : (hw ? (int)hw : 1));
+    const int nthreads = host_threads("JPEGX_NARROW_THREADS", 8, (size_t)H * W);      // 8 / 16 / 32: 1.26-1.57 / 1.38-1.99 / 1.33-1.94 ms per int64 band (starting the threads costs more than sixteen gain)
     const int nstrips = nthreads == 1 ? 1 : 8;
     std::atomic<bool> ok{true};
     std::vector<std::atomic<int>> done(nstrips);
@@ -252,10 +254,7 @@ int narrow_and_upload(const T *src, ptrdiff_t src_pitch, int H, int W, uint8_t *
                 : hipMemcpy2DAsync(static_cast<uint8_t *>(d_dst) + (size_t)r0 * dst_pitch, (size_t)dst_pitch, stage + (size_t)r0 * W, (size_t)W, (size_t)W, (size_t)(r1 - r0), hipMemcpyHostToDevice, st);
     }
     for (auto &t : th) t.join();
-    if (!ok) {
-        (void)hipStreamSynchronize(st);                       // the strips already on their way read the staging area: let them finish
-        return fail(JPEGX_E_UNSUPPORTED, "samples outside 0..255: not an 8-bit band");
-    }
+    if (!ok) return fail(JPEGX_E_UNSUPPORTED, "samples outside 0..255: not an 8-bit band");      // the strips on their way read the staging area: the Job waits for them
     if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
     return JPEGX_OK;
 }
@@ -432,6 +431,32 @@ int head_verdict(const unsigned long long *head, unsigned long long *total)
     return JPEGX_OK;
 }
 
+// the 16-byte head of a band's workspace (byte count, error flag) on its way to pinned memory
+int enqueue_head(unsigned long long *head, const BandSlot &slot, hipStream_t st)
+{
+    if (hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
+    return JPEGX_OK;
+}
+
+// What the compress_begin entries share.  Before anything is enqueued: the job's stream and the head's pinned place.
+int begin_prologue(Job &job, hipStream_t *st, unsigned long long **head)
+{
+    int rc;
+    if ((rc = job.rc) || (rc = job.streams(false)) || (rc = job.pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    *st = job.pool->stream;
+    *head = static_cast<unsigned long long *>(job.pool->h_head.p);
+    return JPEGX_OK;
+}
+
+// With the emitter in the stream: the job stays open, the pool locked (and t_held set), until _finish / _abort.
+int begin_epilogue(Job &job, unsigned long long total, size_t *nbytes)
+{
+    job.pool->open = true;
+    job.pool->out_bytes = (size_t)total;
+    *nbytes = (size_t)total;
+    return job.hold();
+}
+
 }  // namespace
 
 extern "C" {
@@ -449,34 +474,26 @@ static int compress_begin_impl(const void *h_plane, int elem_size, int H, int W,
     if (!nbytes) return fail(JPEGX_E_INVALID, "null pointer");
     int rc = check_compress_shape(h_plane, elem_size, H, W, rows, cols, pitch, bs, ragged);
     if (rc) return rc;
-    DevicePool *pool = nullptr;
-    if ((rc = lock_pool(&pool))) return rc;
-    auto bail = [&](int code) { unlock_pool(pool); return code; };
-    if ((rc = ensure_streams(pool, false))) return bail(rc);
-    if (elem_size != 1 && (rc = pool->h_in.ensure((size_t)H * bs * W * bs))) return bail(rc);
+    Job job;
+    hipStream_t st = nullptr;
+    unsigned long long *head = nullptr, total = 0;
+    if ((rc = begin_prologue(job, &st, &head))) return rc;
+    DevicePool *pool = job.pool;
+    if (elem_size != 1 && (rc = pool->h_in.ensure((size_t)H * bs * W * bs))) return rc;
     BandSlot &slot = pool->slot[0];
-    hipStream_t st = pool->stream;
     // The emitter goes into the stream BEHIND the size read-back without waiting for it: the device does not idle while the
     // host learns the byte count (a 16-byte copy, a wake-up and a launch: ~25 us), and the emitter refuses by itself when
     // the sizes pass flagged an amplitude.  Its destination is therefore sized for the worst case (185 bytes per block).
     const long long nblocks = (long long)(H / 8) * (W / 8);
-    if ((rc = slot.d_out.ensure((size_t)nblocks * 188 + 64)) || (rc = pool->h_head.ensure(16 * MAX_BANDS))) return bail(rc);
-    if ((rc = enqueue_front(pool, slot, static_cast<uint8_t *>(pool->h_in.p), h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, st)))
-        return bail(rc);
-    unsigned long long *head = static_cast<unsigned long long *>(pool->h_head.p);
-    if (hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(pool->ev[0], st) != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return bail(fail(JPEGX_E_HIP, "device to host copy failed"));
-    }
+    if ((rc = slot.d_out.ensure((size_t)nblocks * 188 + 64))) return rc;
+    if ((rc = enqueue_front(pool, slot, static_cast<uint8_t *>(pool->h_in.p), h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, st)) ||
+        (rc = enqueue_head(head, slot, st)))
+        return rc;
+    if (hipEventRecord(pool->ev[0], st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
     rc = enqueue_emit(slot, nblocks, static_cast<uint8_t *>(slot.d_out.p), st);
-    if (hipEventSynchronize(pool->ev[0]) != hipSuccess) { (void)hipStreamSynchronize(st); return bail(fail(JPEGX_E_HIP, "hipEventSynchronize failed")); }
-    if (rc) { (void)hipStreamSynchronize(st); return bail(rc); }
-    unsigned long long total = 0;
-    if ((rc = head_verdict(head, &total))) { (void)hipStreamSynchronize(st); return bail(rc); }
-    pool->open = true;
-    pool->out_bytes = (size_t)total;
-    *nbytes = (size_t)total;
-    return JPEGX_OK;                       // the pool stays locked (and t_held set) until _finish / _abort
+    if (hipEventSynchronize(pool->ev[0]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
+    if (rc || (rc = head_verdict(head, &total))) return rc;
+    return begin_epilogue(job, total, nbytes);
 }
 
 // H, W of the padded plane of a rows x cols band (jpegx_padded_shape), with the checks the ragged entries share
@@ -519,37 +536,27 @@ int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t p
         return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
     const long long nblocks = (long long)(H / N) * (W / N);
     const int len = N * N;
-    DevicePool *pool = nullptr;
+    Job job;
+    hipStream_t st = nullptr;
+    unsigned long long *head = nullptr, total = 0;
     int rc;
-    if ((rc = lock_pool(&pool))) return rc;
-    auto bail = [&](int code) { unlock_pool(pool); return code; };
-    if ((rc = ensure_streams(pool, false))) return bail(rc);
-    BandSlot &slot = pool->slot[0];
-    hipStream_t st = pool->stream;
+    if ((rc = begin_prologue(job, &st, &head))) return rc;
+    BandSlot &slot = job.pool->slot[0];
     if ((rc = slot.d_in.ensure((size_t)H * W * 8)) || (rc = slot.d_zz.ensure((size_t)H * W * 4)) ||
-        (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len))) || (rc = pool->h_head.ensure(16 * MAX_BANDS)))
-        return bail(rc);
-    auto drain = [&](int code) { (void)hipStreamSynchronize(st); return bail(code); };
+        (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len))))
+        return rc;
     hipError_t e = pitch == W ? hipMemcpyAsync(slot.d_in.p, h_plane, (size_t)H * W * 8, hipMemcpyHostToDevice, st)
                               : hipMemcpy2DAsync(slot.d_in.p, (size_t)W * 8, h_plane, (size_t)pitch * 8, (size_t)W * 8, (size_t)H, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { (void)hipGetLastError(); return drain(fail(JPEGX_E_HIP, "host to device copy failed")); }
+    if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
     const int32_t *d_zz = static_cast<const int32_t *>(slot.d_zz.p);
     if ((rc = jpegx_forward_fused_n(static_cast<const double *>(slot.d_in.p), H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
-        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)))
-        return drain(rc);
-    unsigned long long *head = static_cast<unsigned long long *>(pool->h_head.p);
-    if (hipMemcpyAsync(head, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError();
-        return drain(fail(JPEGX_E_HIP, "device to host copy failed"));
-    }
-    unsigned long long total = 0;
-    if ((rc = head_verdict(head, &total))) return bail(rc);          // an amplitude beyond 15 bits: the stream is idle, the context goes back
-    if ((rc = slot.d_out.ensure((size_t)total + 64))) return bail(rc);
-    if ((rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st))) return drain(rc);
-    pool->open = true;
-    pool->out_bytes = (size_t)total;
-    *nbytes = (size_t)total;
-    return JPEGX_OK;                       // the pool stays locked (and t_held set) until _finish / _abort
+        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)) || (rc = enqueue_head(head, slot, st)))
+        return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
+    if ((rc = head_verdict(head, &total)) || (rc = slot.d_out.ensure((size_t)total + 64)) ||
+        (rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st)))
+        return rc;
+    return begin_epilogue(job, total, nbytes);
 }
 
 int jpegx_host_compress_finish(uint8_t *h_out)
@@ -603,16 +610,14 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
         for (int k = 0; k < nbands; ++k)
             if ((rc = check_compress_shape(h_planes[k], elem_size, H, W, rows, cols, pitch, bs, ragged))) return rc;
     }
-    PoolLock lock;
-    if (lock.rc) return lock.rc;
-    DevicePool *pool = lock.pool;
-    if ((rc = ensure_streams(pool, true))) return rc;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(true))) return rc;
+    DevicePool *pool = job.pool;
     const size_t in_bytes = (size_t)H * bs * W * bs;
     const long long nblocks = (long long)(H / 8) * (W / 8);
     if ((rc = pool->h_head.ensure(16 * MAX_BANDS))) return rc;
     if (!h_packed && elem_size != 1 && (rc = pool->h_in.ensure(in_bytes * nbands))) return rc;
     unsigned long long *heads = static_cast<unsigned long long *>(pool->h_head.p);
-    auto drain = [&]() { (void)hipStreamSynchronize(pool->aux[0]); (void)hipStreamSynchronize(pool->aux[1]); };
     const Trace tr;
     tr.mark("compress_image: pool ready");
     if (h_packed) {
@@ -629,45 +634,40 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
         hipError_t e = ((size_t)pitch == row_bytes)
             ? hipMemcpyAsync(pool->d_packed.p, h_packed, (size_t)rows * row_bytes, hipMemcpyHostToDevice, pool->aux[0])
             : hipMemcpy2DAsync(pool->d_packed.p, row_bytes, h_packed, (size_t)pitch, row_bytes, (size_t)rows, hipMemcpyHostToDevice, pool->aux[0]);
-        if (e != hipSuccess) { drain(); return fail(JPEGX_E_HIP, "host to device copy failed"); }
-        if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, (ptrdiff_t)W * bs, pool->aux[0]))) { drain(); return rc; }
-        if (hipEventRecord(pool->ev_x, pool->aux[0]) != hipSuccess || hipStreamWaitEvent(pool->aux[1], pool->ev_x, 0) != hipSuccess) {
-            drain();
+        if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
+        if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, (ptrdiff_t)W * bs, pool->aux[0]))) return rc;
+        if (hipEventRecord(pool->ev_x, pool->aux[0]) != hipSuccess || hipStreamWaitEvent(pool->aux[1], pool->ev_x, 0) != hipSuccess)
             return fail(JPEGX_E_HIP, "event between the image job's streams failed");
-        }
         tr.mark("pixels enqueued");
     }
     for (int k = 0; k < nbands; ++k) {
         hipStream_t st = pool->aux[k & 1];
         uint8_t *stage = (!h_packed && elem_size != 1) ? static_cast<uint8_t *>(pool->h_in.p) + in_bytes * k : nullptr;
         rc = enqueue_front(pool, pool->slot[k], stage, h_packed ? nullptr : h_planes[k], h_packed ? 1 : elem_size, H, W, rows, cols, pitch, bs, mode, param, st);
-        if (!rc && hipMemcpyAsync(heads + 2 * k, pool->slot[k].d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess)
-            rc = fail(JPEGX_E_HIP, "device to host copy failed");
+        if (!rc) rc = enqueue_head(heads + 2 * k, pool->slot[k], st);
         if (!rc && hipEventRecord(pool->ev[k], st) != hipSuccess) rc = fail(JPEGX_E_HIP, "hipEventRecord failed");
-        if (rc) { drain(); return rc; }
+        if (rc) return rc;
         tr.mark("front enqueued", k);
     }
     size_t total_all = prefix_len;
     size_t offset[MAX_BANDS] = {};
     for (int k = 0; k < nbands; ++k) {
-        if (hipEventSynchronize(pool->ev[k]) != hipSuccess) { drain(); return fail(JPEGX_E_HIP, "hipEventSynchronize failed"); }
+        if (hipEventSynchronize(pool->ev[k]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
         unsigned long long total = 0;
-        if ((rc = head_verdict(heads + 2 * k, &total))) { drain(); return rc; }
-        if (length_prefixes && total > 0xFFFFFFFFull) { drain(); return fail(JPEGX_E_INVALID, "a band's stream does not fit the container's 32-bit length field"); }
+        if ((rc = head_verdict(heads + 2 * k, &total))) return rc;
+        if (length_prefixes && total > 0xFFFFFFFFull) return fail(JPEGX_E_INVALID, "a band's stream does not fit the container's 32-bit length field");
         nbytes[k] = (size_t)total;
         offset[k] = total_all + (length_prefixes ? 4 : 0);
         total_all = offset[k] + (size_t)total;
         // the emit kernel needs only the device-side offsets: enqueue it now, the destination comes later
         BandSlot &slot = pool->slot[k];
         if ((rc = slot.d_out.ensure(total ? (size_t)total : 1)) ||
-            (rc = enqueue_emit(slot, nblocks, static_cast<uint8_t *>(slot.d_out.p), pool->aux[k & 1]))) {
-            drain();
+            (rc = enqueue_emit(slot, nblocks, static_cast<uint8_t *>(slot.d_out.p), pool->aux[k & 1])))
             return rc;
-        }
     }
     tr.mark("sizes known, emits enqueued");
     uint8_t *dst = static_cast<uint8_t *>(alloc(user, total_all));
-    if (!dst && total_all) { drain(); return fail(JPEGX_E_INVALID, "the allocator returned no destination"); }
+    if (!dst && total_all) return fail(JPEGX_E_INVALID, "the allocator returned no destination");
     tr.mark("destination allocated");
     prefault(dst, total_all);
     tr.mark("destination touched");
@@ -678,16 +678,14 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
             const uint8_t le[4] = {(uint8_t)n32, (uint8_t)(n32 >> 8), (uint8_t)(n32 >> 16), (uint8_t)(n32 >> 24)};   // struct '<L'
             memcpy(dst + offset[k] - 4, le, 4);
         }
-        if (nbytes[k] && hipMemcpyAsync(dst + offset[k], pool->slot[k].d_out.p, nbytes[k], hipMemcpyDeviceToHost, pool->aux[k & 1]) != hipSuccess) {
-            drain();
+        if (nbytes[k] && hipMemcpyAsync(dst + offset[k], pool->slot[k].d_out.p, nbytes[k], hipMemcpyDeviceToHost, pool->aux[k & 1]) != hipSuccess)
             return fail(JPEGX_E_HIP, "device to host copy failed");
-        }
         tr.mark("download enqueued", k);
     }
-    HP_TRY(hipStreamSynchronize(pool->aux[0]));
-    HP_TRY(hipStreamSynchronize(pool->aux[1]));
+    HIP_TRY(hipStreamSynchronize(pool->aux[0]));
+    HIP_TRY(hipStreamSynchronize(pool->aux[1]));
     tr.mark("compress_image: done");
-    return JPEGX_OK;
+    return job.done();
 }
 
 int jpegx_host_compress_image(const void *const *h_planes, int nbands, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
@@ -737,70 +735,11 @@ int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands,
 }  // extern "C"
 
 namespace {
-// bytes already on the device (slot.d_in, padded) -> int16 stream in slot.d_zz; the caller holds the pool.
-// level 0: the segmented scheme (jpegx_entropy_decode.hip, round 3) -- three launches whose workspace depends on the
-// stream's length only, no host round trip; decode_status afterwards may answer DECODE_RETRY_GENERAL ("next level") for a
-// stream whose densest stretch overflows a segment's tables.  level 1: the same with 256-byte segments.  level 2: the
-// pointer-jumping scheme over the whole stream, which reads the candidate count back in the middle.
+
 constexpr int DECODE_RETRY_GENERAL = jpegx_decode::LADDER_NEXT_LEVEL;
 
-thread_local int t_last_decode_level = -1;      // which scheme took the last stream on this thread (tests)
-}  // namespace
-
-// The ladder itself (jpegx_entropy_decode.h): one rung on any owner's memory.
-int jpegx_decode::ladder_enqueue(Ladder &lad, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int16_t *d_zz, hipStream_t st, int level)
-{
-    int rc;
-    const char *force = getenv("JPEGX_DECODE_GENERAL");    // tests / A-B runs: the general scheme from the start
-    if (force && *force && *force != '0') level = 2;
-    if (level == 1 && seg_plan(nbytes, nblocks, 0).seg == 256) level = 2;      // the first try had the smallest segments already
-    const SegPlan plan = seg_plan(nbytes, nblocks, level, (level == 0 && lad.filter_pause > 0) ? 0 : -1);
-    if (level == 0 && lad.filter_pause > 0) --lad.filter_pause;
-    lad.last_filter = plan.filter;
-    t_last_decode_level = level;
-    if (level < 2 && plan.ok) {
-        void *d_state = nullptr, *d_scratch = nullptr;
-        size_t state_cap = 0;
-        bool fresh = true;
-        int parity = 0;
-        if ((rc = lad.seg_memory(plan, &d_state, &state_cap, &fresh, &parity, &d_scratch))) return rc;
-        lad.seg_parity = parity;
-        lad.status_at = static_cast<const unsigned char *>(d_state) + 64 * parity;
-        enqueue_segmented(d_bytes, nbytes, nblocks, plan, d_state, state_cap, fresh, parity, d_scratch, d_zz, st);
-        HP_TRY(hipGetLastError());
-        return JPEGX_OK;
-    }
-    lad.seg_parity = -1;
-    void *d_ws1 = nullptr, *d_ws2 = nullptr;
-    if ((rc = lad.phase1_memory(phase1_bytes(nbytes), &d_ws1))) return rc;
-    lad.status_at = d_ws1;
-    enqueue_phase1(d_bytes, nbytes, d_ws1, st);
-    unsigned head[4] = {0, 0, 0, 0};
-    HP_TRY(hipMemcpyAsync(head, d_ws1, 16, hipMemcpyDeviceToHost, st));
-    HP_TRY(hipStreamSynchronize(st));
-    const unsigned ncand = head[0];
-    if (ncand == 0 || (long long)ncand < nblocks) return fail(JPEGX_E_INVALID, "entropy stream holds fewer blocks than the plane has");
-    if ((rc = lad.phase2_memory(phase2_bytes(ncand, nblocks), &d_ws2))) return rc;
-    enqueue_phase2(d_bytes, nbytes, nblocks, d_ws1, ncand, d_ws2, d_zz, st);
-    HP_TRY(hipGetLastError());
-    return JPEGX_OK;
-}
-
-int jpegx_decode::ladder_status(Ladder &lad)
-{
-    unsigned head[16] = {0};
-    const bool seg = lad.seg_parity >= 0;
-    HP_TRY(hipMemcpy(head, lad.status_at, 64, hipMemcpyDeviceToHost));
-    if (seg && head[2] != 0) {
-        if ((head[2] & 4u) && lad.last_filter) lad.filter_pause = 64;      // the candidate filter missed a block start: without it for a while
-        return LADDER_NEXT_LEVEL;
-    }
-    if (head[1] != 0) return fail(JPEGX_E_INVALID, "entropy stream is not a sequence of well-formed blocks (device decoder)");
-    return JPEGX_OK;
-}
-
-namespace {
-
+// bytes already on the device (slot.d_in, padded) -> int16 stream in slot.d_zz, one rung of the decoder's ladder
+// (jpegx_decode_ladder.cpp); the caller holds the pool
 int decode_on_device(BandSlot &slot, size_t nbytes, long long nblocks, hipStream_t st, int level)
 {
     int rc;
@@ -814,7 +753,7 @@ int decode_status(BandSlot &slot)
     if (const char *dump = getenv("JPEGX_DECODE_STATS")) {     // a -DJPEGX_DECODE_STATS build leaves per-segment time stamps in its scratch
         if (slot.seg_parity >= 0) {
             std::vector<unsigned char> raw(slot.d_seg.cap);
-            HP_TRY(hipMemcpy(raw.data(), slot.d_seg.p, raw.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(raw.data(), slot.d_seg.p, raw.size(), hipMemcpyDeviceToHost));
             if (FILE *f = fopen(dump, "wb")) { fwrite(raw.data(), 1, raw.size(), f); fclose(f); }
         }
     }
@@ -825,10 +764,32 @@ int check_decompress_shape(const uint8_t *h_bytes, size_t nbytes, int H, int W, 
 {
     if (!h_bytes) return fail(JPEGX_E_INVALID, "null host pointer");
     if (H <= 0 || W <= 0 || (H % 8) || (W % 8)) return fail(JPEGX_E_INVALID, "plane height and width must be positive multiples of 8");
-    if ((long long)(H / 8) * (W / 8) > 0x7FFFFFC0LL) return fail(JPEGX_E_INVALID, "block count must be in 1 .. 2^31-64");
     if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "host_decompress supports block_size 1..255");
-    if (nbytes == 0 || nbytes >= 0xFFFFFFF0ull) return fail(JPEGX_E_INVALID, "entropy stream empty or beyond 4 GiB");
+    return jpegx_decode::check_stream_args(nbytes, (long long)(H / 8) * (W / 8));
+}
+
+// the stream up into slot.d_in as the decoder wants it: dword aligned, zeros behind it
+int upload_stream(BandSlot &slot, const uint8_t *h_bytes, size_t nbytes, hipStream_t st)
+{
+    int rc;
+    if ((rc = slot.d_in.ensure(nbytes + 16))) return rc;
+    HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(slot.d_in.p) + (nbytes & ~(size_t)3), 0, 16 + (nbytes & 3), st));   // zero tail (whole dwords)
+    HIP_TRY(hipMemcpyAsync(slot.d_in.p, h_bytes, nbytes, hipMemcpyHostToDevice, st));
     return JPEGX_OK;
+}
+
+// The stream in slot.d_in through the decoder's levels on one stream (planned segments, 256-byte segments, the
+// whole-stream scheme): the decode and, behind it, what `then` enqueues; wait; ask the rung for its verdict.
+template <typename F>
+int decode_levels(BandSlot &slot, hipStream_t st, size_t nbytes, long long nblocks, F &&then)
+{
+    for (int level = 0; level < 3; ++level) {
+        int rc;
+        if ((rc = decode_on_device(slot, nbytes, nblocks, st, level)) || (rc = then())) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((rc = decode_status(slot)) != DECODE_RETRY_GENERAL) return rc;
+    }
+    return jpegx_decode::ladder_exhausted();
 }
 
 // upload + device entropy decoding + fused inverse (clamp, SubSampling.invert) of one band into slot.d_out
@@ -836,50 +797,50 @@ int check_decompress_shape(const uint8_t *h_bytes, size_t nbytes, int H, int W, 
 int enqueue_back(BandSlot &slot, const uint8_t *h_bytes, size_t nbytes, int H, int W, int bs, int mode, double param,
                  ptrdiff_t dev_pitch, hipStream_t st, int level)
 {
-    const long long nblocks = (long long)(H / 8) * (W / 8);
     int rc;
-    if ((rc = slot.d_in.ensure(nbytes + 16)) || (rc = slot.d_out.ensure((size_t)H * bs * dev_pitch))) return rc;
-    HP_TRY(hipMemsetAsync(static_cast<uint8_t *>(slot.d_in.p) + (nbytes & ~(size_t)3), 0, 16 + (nbytes & 3), st));   // zero tail (whole dwords)
-    HP_TRY(hipMemcpyAsync(slot.d_in.p, h_bytes, nbytes, hipMemcpyHostToDevice, st));
-    if ((rc = decode_on_device(slot, nbytes, nblocks, st, level))) return rc;
+    if ((rc = slot.d_out.ensure((size_t)H * bs * dev_pitch)) || (rc = upload_stream(slot, h_bytes, nbytes, st)) ||
+        (rc = decode_on_device(slot, nbytes, (long long)(H / 8) * (W / 8), st, level)))
+        return rc;
     return jpegx_inverse_fused_u8_inflated(static_cast<const int16_t *>(slot.d_zz.p), H, W, mode, param, 0, bs,
                                            static_cast<uint8_t *>(slot.d_out.p), dev_pitch, st);
 }
-}  // namespace
-
-extern "C" {
 
 // Inverse of jpegx_host_compress_*: the whole decompress_band job for one plane (pipeline/__init__.py:79-88 for
 // transform 'DCT', dct_size 8): bytes up, entropy decoding ON THE DEVICE (jpegx_entropy_decode.hip), fused
 // inverse with clamp and SubSampling.invert (any block_size), uint8 samples down.  h_out: [H*bs][out_pitch] bytes.
-static int decompress_plane_locked(DevicePool *pool, const uint8_t *h_bytes, size_t nbytes, int H, int W, int bs, int mode,
-                                   double param, uint8_t *h_out, ptrdiff_t out_pitch, bool fresh_out)
+int decompress_plane(Job &job, const uint8_t *h_bytes, size_t nbytes, int H, int W, int bs, int mode, double param, uint8_t *h_out,
+                     ptrdiff_t out_pitch, bool fresh_out)
 {
     int rc = check_decompress_shape(h_bytes, nbytes, H, W, bs);
     if (rc) return rc;
     if (!h_out) return fail(JPEGX_E_INVALID, "null host pointer");
     if (out_pitch < (ptrdiff_t)W * bs || (out_pitch % ((bs == 2 || bs == 4) ? 16 : 8)) != 0)
         return fail(JPEGX_E_INVALID, "output pitch too small or misaligned");
-    if ((rc = ensure_streams(pool, false))) return rc;
-    hipStream_t st = pool->stream;
-    BandSlot &slot = pool->slot[0];
+    if ((rc = job.streams(false))) return rc;
+    hipStream_t st = job.pool->stream;
+    BandSlot &slot = job.pool->slot[0];
     BackgroundTouch touch(h_out, fresh_out ? (size_t)H * bs * out_pitch : 0);       // a fresh result array: fault its pages in meanwhile
-    for (int level = 0; level < 3; ++level) {      // planned segments, 256-byte segments, the whole-stream scheme
-        if ((rc = enqueue_back(slot, h_bytes, nbytes, H, W, bs, mode, param, out_pitch, st, level))) return rc;
+    if ((rc = slot.d_out.ensure((size_t)H * bs * out_pitch)) || (rc = upload_stream(slot, h_bytes, nbytes, st))) return rc;
+    rc = decode_levels(slot, st, nbytes, (long long)(H / 8) * (W / 8), [&]() -> int {
+        const int r = jpegx_inverse_fused_u8_inflated(static_cast<const int16_t *>(slot.d_zz.p), H, W, mode, param, 0, bs,
+                                                      static_cast<uint8_t *>(slot.d_out.p), out_pitch, st);
+        if (r) return r;
         touch.wait();
-        HP_TRY(hipMemcpyAsync(h_out, slot.d_out.p, (size_t)H * bs * out_pitch, hipMemcpyDeviceToHost, st));
-        HP_TRY(hipStreamSynchronize(st));
-        if ((rc = decode_status(slot)) != DECODE_RETRY_GENERAL) return rc;
-    }
-    return fail(JPEGX_E_INVALID, "device decoder: no scheme took the stream");
+        HIP_TRY(hipMemcpyAsync(h_out, slot.d_out.p, (size_t)H * bs * out_pitch, hipMemcpyDeviceToHost, st));
+        return JPEGX_OK;
+    });
+    return rc ? rc : job.done();
 }
+}  // namespace
+
+extern "C" {
 
 int jpegx_host_decompress_plane(const uint8_t *h_bytes, size_t nbytes, int H, int W, int bs, int mode, double param,
                                 uint8_t *h_out, ptrdiff_t out_pitch)
 {
-    PoolLock lock;
-    if (lock.rc) return lock.rc;
-    return decompress_plane_locked(lock.pool, h_bytes, nbytes, H, W, bs, mode, param, h_out, out_pitch, true);
+    Job job;
+    if (job.rc) return job.rc;
+    return decompress_plane(job, h_bytes, nbytes, H, W, bs, mode, param, h_out, out_pitch, true);
 }
 
 // The same, handing back what the reference's decompress_band returns: a [rows][cols] int64 array (the band
@@ -892,18 +853,16 @@ int jpegx_host_decompress_plane_i64(const uint8_t *h_bytes, size_t nbytes, int H
         return fail(JPEGX_E_INVALID, "bad output shape");
     const ptrdiff_t pitch = ((ptrdiff_t)W * bs + 15) / 16 * 16;
     const size_t stage_bytes = (size_t)H * bs * pitch;
-    PoolLock lock;                                         // held to the end: the staging span belongs to this job
-    if (lock.rc) return lock.rc;
-    DevicePool *pool = lock.pool;
+    Job job;                                               // held to the end: the staging span belongs to this job
+    if (job.rc) return job.rc;
+    DevicePool *pool = job.pool;
     int rc;
     if ((rc = pool->h_out.ensure(stage_bytes))) return rc;
     uint8_t *stage = static_cast<uint8_t *>(pool->h_out.p);
     BackgroundTouch touch(h_out, (size_t)rows * cols * sizeof(int64_t));   // 128 MiB for a 4096 x 4096 band, usually never touched before
-    if ((rc = decompress_plane_locked(pool, h_bytes, nbytes, H, W, bs, mode, param, stage, pitch, false))) return rc;
+    if ((rc = decompress_plane(job, h_bytes, nbytes, H, W, bs, mode, param, stage, pitch, false))) return rc;
     touch.wait();
-    const unsigned hw = std::thread::hardware_concurrency();
-    static const int want = [] { const char *e = getenv("JPEGX_WIDEN_THREADS"); return e && *e ? atoi(e) : 8; }();      // A/B (8: 1.8-2.4 ms, 16: 1.7-2.6 ms per 4096^2 band: no difference)
-    const int nthreads = ((size_t)rows * cols < (1u << 20)) ? 1 : ((int)hw >= want ? want : (hw ? (int)hw : 1));
+    const int nthreads = host_threads("JPEGX_WIDEN_THREADS", 8, (size_t)rows * cols);      // A/B (8: 1.8-2.4 ms, 16: 1.7-2.6 ms per 4096^2 band: no difference)
     // non-temporal stores: the array is written once, 8 bytes per sample, and is eight times the size of what is read --
     // ordinary stores would first READ every line of it for ownership (twice the memory traffic)
     auto work = [&](int y0, int y1) {
@@ -940,10 +899,9 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
     if (rows <= 0 || cols <= 0 || rows > (long long)H * bs || cols > (long long)W * bs) return fail(JPEGX_E_INVALID, "bad output shape");
     if (out_pitch < (ptrdiff_t)cols * (interleave ? nbands : 1)) return fail(JPEGX_E_INVALID, "output pitch smaller than the row");
     const ptrdiff_t dev_pitch = ((ptrdiff_t)W * bs + 15) / 16 * 16;
-    PoolLock lock;
-    if (lock.rc) return lock.rc;
-    DevicePool *pool = lock.pool;
-    if ((rc = ensure_streams(pool, true))) return rc;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(true))) return rc;
+    DevicePool *pool = job.pool;
     const size_t packed_pitch = (size_t)cols * nbands;
     if (interleave && (rc = pool->d_packed.ensure((size_t)rows * packed_pitch))) return rc;      // before anything is enqueued
     // the result array is usually fresh memory: touch its pages on a helper thread while the bands are uploaded and decoded.
@@ -953,7 +911,6 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
     const size_t row_bytes = (size_t)cols * (interleave ? nbands : 1);
     const size_t out_span = (size_t)out_pitch == row_bytes ? (size_t)rows * (interleave ? 1 : nbands) * row_bytes : 0;
     BackgroundTouch touch(h_out, out_span);
-    auto drain = [&]() { (void)hipStreamSynchronize(pool->aux[0]); (void)hipStreamSynchronize(pool->aux[1]); };
     int level[MAX_BANDS] = {};                              // per band: planned segments, 256-byte segments, the whole-stream scheme
     bool done[MAX_BANDS] = {};
     auto copy_down = [&](int j) -> int {                    // band j's samples to their place in the result, on the band's stream
@@ -967,23 +924,20 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
         for (int k = 0; k < nbands; ++k) {
             hipStream_t st = pool->aux[k & 1];
             if (done[k]) {                                   // this band is done: only the packing below waits for it again
-                if (interleave && hipEventRecord(pool->ev[k], st) != hipSuccess) { drain(); return fail(JPEGX_E_HIP, "hipEventRecord failed"); }
+                if (interleave && hipEventRecord(pool->ev[k], st) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventRecord failed");
                 continue;
             }
-            if ((rc = enqueue_back(pool->slot[k], h_bytes[k], nbytes[k], H, W, bs, mode, param, dev_pitch, st, level[k]))) { drain(); return rc; }
+            if ((rc = enqueue_back(pool->slot[k], h_bytes[k], nbytes[k], H, W, bs, mode, param, dev_pitch, st, level[k]))) return rc;
             if (!interleave) {
                 // No copy may be ENQUEUED while the helper thread still writes its zeros into the result's pages (a copy
                 // that landed first would lose one byte per page).  The first band's copy is therefore held back until
                 // the second band's work is in its own stream: the wait then costs nothing the device could notice.
                 if (k == 0 && nbands > 1 && !done[1]) { held = 0; continue; }
                 touch.wait();
-                if (held >= 0 && (rc = copy_down(held))) { drain(); return rc; }
+                if (held >= 0 && (rc = copy_down(held))) return rc;
                 held = -1;
-                if ((rc = copy_down(k))) { drain(); return rc; }
-            } else if (hipEventRecord(pool->ev[k], st) != hipSuccess) {
-                drain();
-                return fail(JPEGX_E_HIP, "hipEventRecord failed");
-            }
+                if ((rc = copy_down(k))) return rc;
+            } else if (hipEventRecord(pool->ev[k], st) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventRecord failed");
         }
         if (interleave) {
             // the packing kernel runs on stream 0 behind every band
@@ -991,18 +945,16 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
             const void *planes[MAX_BANDS] = {};
             for (int k = 0; k < nbands; ++k) {
                 planes[k] = pool->slot[k].d_out.p;
-                if (k != 0 && hipStreamWaitEvent(st, pool->ev[k], 0) != hipSuccess) { drain(); return fail(JPEGX_E_HIP, "hipStreamWaitEvent failed"); }
+                if (k != 0 && hipStreamWaitEvent(st, pool->ev[k], 0) != hipSuccess) return fail(JPEGX_E_HIP, "hipStreamWaitEvent failed");
             }
             uint8_t *packed = static_cast<uint8_t *>(pool->d_packed.p);
-            if ((rc = jpegx_interleave_u8(planes, nbands, rows, cols, dev_pitch, packed, (ptrdiff_t)packed_pitch, st))) { drain(); return rc; }
+            if ((rc = jpegx_interleave_u8(planes, nbands, rows, cols, dev_pitch, packed, (ptrdiff_t)packed_pitch, st))) return rc;
             touch.wait();                                    // the helper thread's zeros first, then the copy (see above)
-            if (hipMemcpy2DAsync(h_out, (size_t)out_pitch, packed, packed_pitch, packed_pitch, (size_t)rows, hipMemcpyDeviceToHost, st) != hipSuccess) {
-                drain();
+            if (hipMemcpy2DAsync(h_out, (size_t)out_pitch, packed, packed_pitch, packed_pitch, (size_t)rows, hipMemcpyDeviceToHost, st) != hipSuccess)
                 return fail(JPEGX_E_HIP, "device to host copy failed");
-            }
         }
-        HP_TRY(hipStreamSynchronize(pool->aux[0]));
-        HP_TRY(hipStreamSynchronize(pool->aux[1]));
+        HIP_TRY(hipStreamSynchronize(pool->aux[0]));
+        HIP_TRY(hipStreamSynchronize(pool->aux[1]));
         bool again = false;
         for (int k = 0; k < nbands; ++k) {
             if (done[k]) continue;
@@ -1011,110 +963,42 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
             else if (rc) return rc;
             else done[k] = true;
         }
-        if (!again) return JPEGX_OK;
+        if (!again) return job.done();
     }
-    return fail(JPEGX_E_INVALID, "device decoder: no scheme took the stream");
-}
-
-extern "C" int jpegx_internal_last_decode_level(void) { return t_last_decode_level; }
-
-// ---- the device decoder on the caller's device buffers (include/jpegx.h) -------------------------------------------
-// workspace: [state of the larger plan, rounded up to 256 bytes][scratch of the larger plan]; the state is cleared by
-// every call (the pooled jobs above keep theirs clean from call to call instead: one fill launch less)
-namespace {
-size_t decode_state_span(size_t nbytes, long long nblocks)
-{
-    size_t m = 0;
-    for (int level = 0; level < 2; ++level)
-        for (int filter = -1; filter <= 0; ++filter) {
-            const jpegx_decode::SegPlan p = jpegx_decode::seg_plan(nbytes, nblocks, level, filter);
-            if (p.state_bytes > m) m = p.state_bytes;
-        }
-    return (m + 255) & ~(size_t)255;
-}
-}  // namespace
-
-extern "C" size_t jpegx_entropy_decode_workspace_bytes(size_t nbytes, long long nblocks)
-{
-    if (nbytes == 0 || nblocks <= 0) return 0;
-    size_t scratch = 0;
-    for (int level = 0; level < 2; ++level)
-        for (int filter = -1; filter <= 0; ++filter) {
-            const jpegx_decode::SegPlan p = jpegx_decode::seg_plan(nbytes, nblocks, level, filter);
-            if (p.ws_bytes > scratch) scratch = p.ws_bytes;
-        }
-    return decode_state_span(nbytes, nblocks) + scratch + 256;
-}
-
-extern "C" int jpegx_entropy_decode(const uint8_t *d_bytes, size_t nbytes, long long nblocks, void *d_workspace, int16_t *d_zz,
-                                    int level, jpegx_stream_t stream)
-{
-    if (!d_bytes || !d_workspace || !d_zz) return fail(JPEGX_E_INVALID, "null device pointer");
-    if (nblocks <= 0 || nblocks > 0x7FFFFFC0LL) return fail(JPEGX_E_INVALID, "block count must be in 1 .. 2^31-64");
-    if (nbytes == 0 || nbytes >= 0xFFFFFFF0ull) return fail(JPEGX_E_INVALID, "entropy stream empty or beyond 4 GiB");
-    if (level < 0 || level > 1) return fail(JPEGX_E_UNSUPPORTED, "levels 0 and 1 run on caller buffers; the whole-stream scheme is jpegx_host_entropy_decode_gpu's");
-    if ((reinterpret_cast<uintptr_t>(d_workspace) & 255u) != 0) return fail(JPEGX_E_INVALID, "workspace must be 256-byte aligned");
-    const jpegx_decode::SegPlan plan = jpegx_decode::seg_plan(nbytes, nblocks, level);
-    if (!plan.ok) return fail(JPEGX_E_UNSUPPORTED, "stream too long for the segmented decoder");
-    const size_t state_span = decode_state_span(nbytes, nblocks);
-    unsigned char *w = static_cast<unsigned char *>(d_workspace);
-    jpegx_decode::enqueue_segmented(d_bytes, nbytes, nblocks, plan, w, state_span, true, 0, w + state_span, d_zz, (hipStream_t)stream);
-    HP_TRY(hipGetLastError());
-    return JPEGX_OK;
-}
-
-extern "C" int jpegx_entropy_decode_status(const void *d_workspace, jpegx_stream_t stream)
-{
-    if (!d_workspace) return fail(JPEGX_E_INVALID, "null device pointer");
-    unsigned head[16] = {0};
-    HP_TRY(hipMemcpyAsync(head, d_workspace, 64, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    if (head[2] != 0) return 1;
-    if (head[1] != 0) return fail(JPEGX_E_INVALID, "entropy stream is not a sequence of well-formed blocks (device decoder)");
-    return JPEGX_OK;
+    return jpegx_decode::ladder_exhausted();
 }
 
 // bytes -> int16 [nblocks][64] on the device, host arrays in and out (what jpegx_host_entropy_decode does on the CPU)
 int jpegx_host_entropy_decode_gpu(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz)
 {
     if (!h_bytes || !h_zz) return fail(JPEGX_E_INVALID, "null host pointer");
-    if (nblocks <= 0 || nblocks > 0x7FFFFFC0LL) return fail(JPEGX_E_INVALID, "block count must be in 1 .. 2^31-64");
-    if (nbytes == 0 || nbytes >= 0xFFFFFFF0ull) return fail(JPEGX_E_INVALID, "entropy stream empty or beyond 4 GiB");
-    PoolLock lock;
-    if (lock.rc) return lock.rc;
-    DevicePool *pool = lock.pool;
     int rc;
-    if ((rc = ensure_streams(pool, false))) return rc;
-    hipStream_t st = pool->stream;
-    BandSlot &slot = pool->slot[0];
-    if ((rc = slot.d_in.ensure(nbytes + 16))) return rc;
-    HP_TRY(hipMemsetAsync(static_cast<uint8_t *>(slot.d_in.p) + (nbytes & ~(size_t)3), 0, 16 + (nbytes & 3), st));
-    HP_TRY(hipMemcpyAsync(slot.d_in.p, h_bytes, nbytes, hipMemcpyHostToDevice, st));
-    for (int level = 0; level < 3; ++level) {
-        if ((rc = decode_on_device(slot, nbytes, nblocks, st, level))) return rc;
-        HP_TRY(hipMemcpyAsync(h_zz, slot.d_zz.p, (size_t)nblocks * 128, hipMemcpyDeviceToHost, st));
-        HP_TRY(hipStreamSynchronize(st));
-        if ((rc = decode_status(slot)) != DECODE_RETRY_GENERAL) return rc;
-    }
-    return fail(JPEGX_E_INVALID, "device decoder: no scheme took the stream");
+    if ((rc = jpegx_decode::check_stream_args(nbytes, nblocks))) return rc;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(false))) return rc;
+    hipStream_t st = job.pool->stream;
+    BandSlot &slot = job.pool->slot[0];
+    if ((rc = upload_stream(slot, h_bytes, nbytes, st))) return rc;
+    rc = decode_levels(slot, st, nbytes, nblocks, [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(h_zz, slot.d_zz.p, (size_t)nblocks * 128, hipMemcpyDeviceToHost, st));
+        return JPEGX_OK;
+    });
+    return rc ? rc : job.done();
 }
 
 // used by host_roundtrip (jpegx_internal.h): the synchronous host-pointer conveniences borrow the pool's
 // stream and its input / output device spans for the duration of one call; not part of the public ABI
 int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream)
 {
-    DevicePool *pool = nullptr;
-    int rc = lock_pool(&pool);
-    if (rc) return rc;
-    if ((rc = ensure_streams(pool, false)) || (rc = pool->slot[0].d_in.ensure(in_bytes ? in_bytes : 1)) ||
-        (rc = pool->slot[0].d_out.ensure(out_bytes ? out_bytes : 1))) {
-        unlock_pool(pool);
+    Job job;
+    int rc;
+    if ((rc = job.rc) || (rc = job.streams(false)) || (rc = job.pool->slot[0].d_in.ensure(in_bytes ? in_bytes : 1)) ||
+        (rc = job.pool->slot[0].d_out.ensure(out_bytes ? out_bytes : 1)))
         return rc;
-    }
-    *d_in = pool->slot[0].d_in.p;
-    *d_out = pool->slot[0].d_out.p;
-    *stream = pool->stream;
-    return JPEGX_OK;
+    *d_in = job.pool->slot[0].d_in.p;
+    *d_out = job.pool->slot[0].d_out.p;
+    *stream = job.pool->stream;
+    return job.hold();
 }
 
 void jpegx_internal_pool_release(void)
@@ -1126,7 +1010,7 @@ void jpegx_internal_pool_release(void)
 int jpegx_host_pool_release(void)
 {
     int dev = 0;
-    HP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= MAX_DEVICES) return fail(JPEGX_E_UNSUPPORTED, "device index beyond the pool table");
     if (t_held != nullptr)
         return fail(JPEGX_E_INVALID, t_held->open ? "a compress job is open on this thread: finish or abort it first"

@@ -9,6 +9,7 @@
 
 #include "../../include/jpegx.h"
 #include "jpegx_device.h"
+#include "jpegx_shared.h"
 
 namespace jpegx_detail {
 extern thread_local char g_err[512];                    // jpegx_runtime.hip
@@ -18,22 +19,6 @@ extern thread_local unsigned long long *g_counters;     // jpegx_set_debug_count
 namespace {
 using jpegx_detail::g_counters;
 using jpegx_detail::g_err;
-
-int fail(int code, const char *fmt, const char *detail = "")
-{
-    snprintf(g_err, sizeof(g_err), fmt, detail);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
-            snprintf(g_err, sizeof(g_err), "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return JPEGX_E_HIP;                                                          \
-        }                                                                                \
-    } while (0)
 
 int check_plane(const void *in, const void *out, int H, int W, ptrdiff_t pitch, int align_elems)
 {
@@ -146,9 +131,6 @@ int fill_inverse_params(int mode, double param, QuantParams *qp)
         return fail(JPEGX_E_INVALID, "unknown quantiser mode");
     }
 }
-
-extern "C" int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream);
-extern "C" void jpegx_internal_pool_release(void);
 
 // generic "copy in, run, copy out" helper on the device's pooled stream and buffers (jpegx_hostpipe.cpp):
 // no hipMalloc / hipStreamCreate per call once the pool has grown to the working size

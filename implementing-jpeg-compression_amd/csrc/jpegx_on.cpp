@@ -3,12 +3,7 @@
 // on the calling thread, whose own current device is restored afterwards: one host thread can drive all the GPUs
 // of a node (pointers and streams handed in must belong to `device`).  The plain forms keep working on the
 // thread's current device (jpegx_set_device), which is what a one-process-per-GPU job sets once at start.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
-#include "../../include/jpegx.h"
-
-extern "C" void jpegx_internal_set_error(const char *msg);
+#include "jpegx_shared.h"
 
 namespace {
 struct DeviceGuard {

@@ -1,0 +1,58 @@
+// jpegx_shared.h -- what every translation unit of libjpegx.so reports errors with, and the entries they call in each
+// other that are not part of the public ABI (include/jpegx.h): each declared here, once.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/jpegx.h"
+
+extern "C" {
+void jpegx_internal_set_error(const char *msg);      // jpegx_runtime.hip: the thread-local string behind jpegx_last_error
+// jpegx_forward.hip: the fused forward kernels with the entropy stage's block sizes written on the way (*sized = 0: the
+// dispatched tier left none, jpegx_internal_entropy_sizes_half makes them)
+int jpegx_internal_forward_u8_sized(const uint8_t *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode, double param, unsigned flags,
+                                    int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, jpegx_stream_t stream);
+int jpegx_internal_forward_f32_sized(const float *d_in, int H, int W, ptrdiff_t pitch, int mode, double param, unsigned flags,
+                                     int16_t *d_out, unsigned *block_bytes, unsigned *wave_bytes, unsigned *half_info, int *sized,
+                                     jpegx_stream_t stream);
+// jpegx_entropy.hip: the pieces of jpegx_entropy_sizes / _emit for streams whose blocks were sized elsewhere
+void jpegx_internal_entropy_views(void *d_workspace, long long nblocks, unsigned **block_bytes, unsigned **wave_bytes, unsigned **half_info);
+int jpegx_internal_entropy_sizes_half(const int16_t *d_zz, long long nblocks, void *d_workspace, jpegx_stream_t stream);
+int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stream_t stream);
+int jpegx_internal_entropy_emit2(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+int jpegx_internal_entropy_emit2_guarded(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, size_t out_cap,
+                                         jpegx_stream_t stream);
+int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
+                                       jpegx_stream_t stream);
+// jpegx_hostpipe.cpp: a job context of the current device borrowed for one call (host_roundtrip, jpegx_internal.h)
+int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream);
+void jpegx_internal_pool_release(void);
+void jpegx_internal_batch_scratch_release(void);     // jpegx_batch.cpp: goes with jpegx_host_pool_release
+int jpegx_internal_last_decode_level(void);          // jpegx_decode_ladder.cpp: the scheme that took this thread's last stream (tests)
+}
+
+namespace {
+
+// the message as it is, or -- with `detail` -- as a format with one %s
+int fail(int code, const char *msg, const char *detail = nullptr)
+{
+    char buf[512];
+    if (detail) snprintf(buf, sizeof(buf), msg, detail);
+    jpegx_internal_set_error(detail ? buf : msg);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            (void)hipGetLastError(); /* reported here: must not linger as the thread's last error */ \
+            char buf_[512];                                                                  \
+            snprintf(buf_, sizeof(buf_), "%s failed: %s", #expr, hipGetErrorString(e_));     \
+            return fail(JPEGX_E_HIP, buf_);                                                  \
+        }                                                                                    \
+    } while (0)
+
+}  // namespace
