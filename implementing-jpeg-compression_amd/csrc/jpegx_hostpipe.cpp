@@ -986,6 +986,79 @@ int jpegx_host_entropy_decode_gpu(const uint8_t *h_bytes, size_t nbytes, long lo
     return rc ? rc : job.done();
 }
 
+// The run-time block length decoder (csrc/jpegx_entropy_decode_n.hip) on the job's stream: the stream in slot.d_in -> int32
+// coefficients in slot.d_zz, the workspace's head on its way to pinned memory, ev[0] recorded behind it.
+static int enqueue_decode_n(DevicePool *pool, BandSlot &slot, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int len, hipStream_t st)
+{
+    int rc;
+    if ((rc = slot.d_ws.ensure(jpegx_entropy_decode_workspace_bytes_n(nbytes, nblocks, len))) || (rc = slot.d_zz.ensure((size_t)nblocks * len * 4)) ||
+        (rc = upload_stream(slot, h_bytes, nbytes, st)) ||
+        (rc = jpegx_entropy_decode_n(static_cast<const uint8_t *>(slot.d_in.p), nbytes, nblocks, len, slot.d_ws.p, static_cast<int32_t *>(slot.d_zz.p), st)))
+        return rc;
+    if (hipMemcpyAsync(pool->h_head.p, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(pool->ev[0], st) != hipSuccess)
+        return fail(JPEGX_E_HIP, "device to host copy failed");
+    return JPEGX_OK;
+}
+
+// waits for ev[0]: JPEGX_OK or the decoder's refusal
+static int decode_verdict_n(DevicePool *pool)
+{
+    if (hipEventSynchronize(pool->ev[0]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
+    return jpegx_internal_decode_verdict_n(static_cast<const unsigned *>(pool->h_head.p)[1]);
+}
+
+// bytes -> int32 [nblocks][block_len] on the device, host arrays in and out (what jpegx_host_entropy_decode_n does on the CPU)
+int jpegx_host_entropy_decode_n_gpu(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len, int32_t *h_zz)
+{
+    if (!h_bytes || !h_zz) return fail(JPEGX_E_INVALID, "null host pointer");
+    int rc;
+    if ((rc = jpegx_internal_decode_check_n(nbytes, nblocks, block_len))) return rc;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(false)) || (rc = job.pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    hipStream_t st = job.pool->stream;
+    BandSlot &slot = job.pool->slot[0];
+    if ((rc = enqueue_decode_n(job.pool, slot, h_bytes, nbytes, nblocks, block_len, st)) || (rc = decode_verdict_n(job.pool))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_zz, slot.d_zz.p, (size_t)nblocks * block_len * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return job.done();
+}
+
+// The decompress_band job for dct_size N (2..32), steps 8-4 inverted: bytes up, jpegx_entropy_decode_n, jpegx_inverse_fused_n
+// behind it on the same stream (it runs while the host waits for the verdict), the samples down once the stream is known
+// to be good -- a refused stream leaves h_out as it was.
+int jpegx_host_decompress_plane_n(const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode, double param, unsigned flags,
+                                  void *h_out, ptrdiff_t out_pitch)
+{
+    if (!h_bytes || !h_out) return fail(JPEGX_E_INVALID, "null host pointer");
+    if (N < 2 || N > 32) return fail(JPEGX_E_INVALID, "dct_size must be 2 .. 32");
+    if (H <= 0 || W <= 0 || (H % N) != 0 || (W % N) != 0) return fail(JPEGX_E_INVALID, "plane height and width must be positive multiples of dct_size");
+    if (out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than width");
+    if ((long long)H * W > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one plane");
+    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE)
+        return fail(JPEGX_E_INVALID, "dct_size other than 8 takes the quantisers none, discard and divide");
+    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
+        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
+    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
+        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
+    if (flags & ~(unsigned)JPEGX_F_CLAMP_U8) return fail(JPEGX_E_INVALID, "decompress_plane_n: the only flag is JPEGX_F_CLAMP_U8");
+    const long long nblocks = (long long)(H / N) * (W / N);
+    const int len = N * N;
+    int rc;
+    if ((rc = jpegx_internal_decode_check_n(nbytes, nblocks, len))) return rc;
+    const size_t esz = (flags & JPEGX_F_CLAMP_U8) ? 1 : 4, row = (size_t)W * esz;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(false)) || (rc = job.pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    hipStream_t st = job.pool->stream;
+    BandSlot &slot = job.pool->slot[0];
+    if ((rc = slot.d_out.ensure((size_t)H * row)) || (rc = enqueue_decode_n(job.pool, slot, h_bytes, nbytes, nblocks, len, st)) ||
+        (rc = jpegx_inverse_fused_n(static_cast<const int32_t *>(slot.d_zz.p), H, W, N, mode, param, flags, slot.d_out.p, W, st)) ||
+        (rc = decode_verdict_n(job.pool)))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(h_out, (size_t)out_pitch * esz, slot.d_out.p, row, row, (size_t)H, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return job.done();
+}
+
 // used by host_roundtrip (jpegx_internal.h): the synchronous host-pointer conveniences borrow the pool's
 // stream and its input / output device spans for the duration of one call; not part of the public ABI
 int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream)

@@ -105,3 +105,10 @@ JPEGX_ON(jpegx_entropy_emit_n, (int device, const int32_t *d_zz, long long nbloc
          (d_zz, nblocks, block_len, d_workspace, d_out, stream))
 JPEGX_ON(jpegx_host_compress_begin_n, (int device, const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param, size_t *nbytes),
          (h_plane, H, W, pitch, N, mode, param, nbytes))
+JPEGX_ON(jpegx_entropy_decode_n, (int device, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int block_len, void *d_workspace, int32_t *d_zz, jpegx_stream_t stream),
+         (d_bytes, nbytes, nblocks, block_len, d_workspace, d_zz, stream))
+JPEGX_ON(jpegx_entropy_decode_status_n, (int device, const void *d_workspace, jpegx_stream_t stream), (d_workspace, stream))
+JPEGX_ON(jpegx_host_entropy_decode_n_gpu, (int device, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len, int32_t *h_zz),
+         (h_bytes, nbytes, nblocks, block_len, h_zz))
+JPEGX_ON(jpegx_host_decompress_plane_n, (int device, const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode, double param, unsigned flags, void *h_out, ptrdiff_t out_pitch),
+         (h_bytes, nbytes, H, W, N, mode, param, flags, h_out, out_pitch))

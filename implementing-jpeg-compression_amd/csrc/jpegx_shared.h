@@ -30,6 +30,10 @@ int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, 
 int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream);
 void jpegx_internal_pool_release(void);
 void jpegx_internal_batch_scratch_release(void);     // jpegx_batch.cpp: goes with jpegx_host_pool_release
+int jpegx_internal_decode_check_n(size_t nbytes, long long nblocks, int block_len);   // jpegx_entropy_decode_n.hip: the stream's sizes, no device touched
+int jpegx_internal_decode_phase_n(const uint8_t *d_bytes, size_t nbytes, long long nblocks, int block_len, void *d_workspace, int32_t *d_zz,
+                                  int phase, jpegx_stream_t stream);         // one phase of jpegx_entropy_decode_n (microbench/dctn_decode.py)
+int jpegx_internal_decode_verdict_n(unsigned bits);   // jpegx_entropy_decode_n.hip: status word 1 of its workspace -> JPEGX_OK / JPEGX_E_INVALID + message
 int jpegx_internal_last_decode_level(void);          // jpegx_decode_ladder.cpp: the scheme that took this thread's last stream (tests)
 }
 

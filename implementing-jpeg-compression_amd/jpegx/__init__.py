@@ -165,6 +165,11 @@ SIGNATURES = {
     "jpegx_host_idct_f64_n": [_vp, _int, _int, _int, _vp, _int],
     "jpegx_host_entropy_encode_n": [_vp, _c.c_longlong, _int, _vp, _sz, _c.POINTER(_sz)],
     "jpegx_host_entropy_decode_n": [_vp, _sz, _c.c_longlong, _int, _vp],
+    "jpegx_entropy_decode_workspace_bytes_n": [_sz, _c.c_longlong, _int],
+    "jpegx_entropy_decode_n": [_vp, _sz, _c.c_longlong, _int, _vp, _vp, _vp],
+    "jpegx_entropy_decode_status_n": [_vp, _vp],
+    "jpegx_host_entropy_decode_n_gpu": [_vp, _sz, _c.c_longlong, _int, _vp],
+    "jpegx_host_decompress_plane_n": [_vp, _sz, _int, _int, _int, _int, _dbl, _uint, _vp, _pd],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -184,9 +189,11 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_pool_release", "jpegx_comm_create_deadline", "jpegx_pad_edges", "jpegx_host_compress_begin_ragged",
               "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged", "jpegx_forward_fused_n",
               "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n", "jpegx_entropy_sizes_n", "jpegx_entropy_emit_n",
-              "jpegx_host_compress_begin_n"):
+              "jpegx_host_compress_begin_n", "jpegx_entropy_decode_n", "jpegx_entropy_decode_status_n",
+              "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
-RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_batch_workspace_bytes": _sz,
+RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
+            "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
 
 
@@ -1099,6 +1106,41 @@ def entropy_decode_n(blob, nblocks, block_len):
     check(lib().jpegx_host_entropy_decode_n(buf.ctypes.data if buf.size else None, buf.size, int(nblocks), int(block_len),
                                             out.ctypes.data if out.size else None), "jpegx_host_entropy_decode_n")
     return out
+
+
+def entropy_decode_n_gpu(blob, nblocks, block_len):
+    """entropy_decode_n on the device (csrc/jpegx_entropy_decode_n.hip): bytes -> int32 (nblocks, block_len), the same
+    arrays; JpegxError for a stream the device refuses."""
+    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    out = np.empty((max(int(nblocks), 0), max(int(block_len), 0)), dtype=np.int32)
+    check(lib().jpegx_host_entropy_decode_n_gpu(buf.ctypes.data if buf.size else None, buf.size, int(nblocks), int(block_len),
+                                                out.ctypes.data if out.size else None), "jpegx_host_entropy_decode_n_gpu")
+    return out
+
+
+def entropy_decode_n_device(d_bytes, nbytes, nblocks, block_len, d_workspace, d_zz, stream=None):
+    """The run-time block length decoder on the caller's device buffers (jpegx_entropy_decode_n / _status_n).  d_bytes: the
+    stream, dword aligned, with 16 zero bytes behind it; d_workspace: jpegx_entropy_decode_workspace_bytes_n(nbytes,
+    nblocks, block_len) bytes, 16-byte aligned, reusable as it is; d_zz: nblocks * block_len int32, 4-byte aligned.
+    Synchronises the stream; raises JpegxError for a stream that is not nblocks well-formed blocks."""
+    L = lib()
+    check(L.jpegx_entropy_decode_n(d_bytes, int(nbytes), int(nblocks), int(block_len), d_workspace, d_zz, stream), "jpegx_entropy_decode_n")
+    check(L.jpegx_entropy_decode_status_n(d_workspace, stream), "jpegx_entropy_decode_status_n")
+
+
+def decompress_plane_n(blob, height, width, n, mode="none", param=0.0, out="u8"):
+    """Steps 8-4 inverted for dct_size n as one pooled device job (jpegx_host_decompress_plane_n): what
+    inverse_fused_n(entropy_decode_n(blob, ...), n, mode, param, out) returns, without the coefficient stream on the host.
+    (height, width): the plane of whole n x n blocks; out 'u8' (clamped) or 'i32'.  JpegxError for a refused stream."""
+    if out not in ("i32", "u8"):
+        raise JpegxError("decompress_plane_n: out must be 'i32' or 'u8'")
+    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    h, w = int(height), int(width)
+    res = np.empty((max(h, 0), max(w, 0)), dtype=np.int32 if out == "i32" else np.uint8)
+    check(lib().jpegx_host_decompress_plane_n(buf.ctypes.data if buf.size else None, buf.size, h, w, int(n), mode_of(mode), float(param),
+                                              F_CLAMP_U8 if out == "u8" else 0, res.ctypes.data if res.size else None, w),
+          "jpegx_host_decompress_plane_n")
+    return res
 
 
 # ---------------------------------------------------------------------------------------------

@@ -10,7 +10,8 @@ configuration: without libjpegx.so or a GPU the call raises ``jpegx.JpegxError``
 Any other dct_size 2..32 with transform 'DCT' takes the all-float64 kernels of csrc/jpegx_dctn.hip
 (``jpegx_forward_fused_n`` / ``jpegx_inverse_fused_n``, entropy stage by libjpegx's sequential host coder; with
 ``DCTN_ENTROPY_MIN_SAMPLES`` set, compressing runs the entropy stage on the device behind the forward kernel,
-csrc/jpegx_entropy_n.hip) when a
+csrc/jpegx_entropy_n.hip; with ``DCTN_ENTROPY_DECODE_MIN_SAMPLES`` set, decompressing runs the entropy decoder on the
+device in front of the inverse kernel, csrc/jpegx_entropy_decode_n.hip) when a
 device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
 NumPy road runs, exactly as the reference does it.
 """
@@ -114,6 +115,16 @@ DCTN_MIN_SAMPLES = 1024
 # (profiles/dctn_entropy.json): the job road is 5-7x faster on a 3000 x 4000 band and wins from 16384 samples
 # on, loses 13-17 us below, and lost 3 % at one N = 24 size above -- so it is not the default; 16384 is the value to set.
 DCTN_ENTROPY_MIN_SAMPLES = None
+
+# The way back as one device job (jpegx.decompress_plane_n: the run-time block length entropy decoder of
+# csrc/jpegx_entropy_decode_n.hip + the inverse kernel, the coefficient stream never on the host): planes of at least this
+# many samples take it; None: the job road is off and decompress_band keeps the host parser + jpegx_inverse_fused_n.
+# Measured (profiles/dctn_decode.json): on a 3000 x 4000 band at block_size 1 decompress_band_u8 takes 1.5 ms
+# instead of 45-47 ms (30x) and decompress_band 48 instead of 93 ms; from 262 144 samples on the job road was no slower
+# than the parent's at every measured configuration (N = 4, 16: 4-7x faster there; N = 24 with divisor 1000, 16 KB of code:
+# equal within 1 %), below that its launches cost more than the host parser saves -- at N = 24 up to 147 456 samples, at
+# N = 16 up to 36 864, at N = 4 up to 16 384.  Hence the smallest measured size with no miss at or above it.
+DCTN_ENTROPY_DECODE_MIN_SAMPLES = 262144
 
 _device_seen = False
 
@@ -259,6 +270,28 @@ def _decode_stream_n(blob, config):
         return None
     try:
         return jpegx.entropy_decode_n(blob, hb * wb, nn).reshape(hb, wb, nn)
+    except jpegx.JpegxError:
+        return None
+
+
+def _decode_job_n(blob, config, out):
+    """Steps 8-4 inverted for dct_size N as one pooled device job (jpegx.decompress_plane_n): the samples of the plane of
+    whole N x N blocks, uint8 (clamped) for out 'u8' or int32 for 'i32'; or None -- the job road is switched off
+    (DCTN_ENTROPY_DECODE_MIN_SAMPLES), _decode_stream_n's preconditions do not hold, or the device refused the stream: the
+    caller's road of before then ends in the host parser and the host steps naming the fault."""
+    import jpegx
+    rle = run_length_encoding.RunLengthEncoding(config)
+    hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
+    n = config.dct_size
+    args = _dctn_mode(config)
+    if DCTN_ENTROPY_DECODE_MIN_SAMPLES is None or not _stock_registry() or args is None:
+        return None
+    if not isinstance(blob, (bytes, bytearray)) or not len(blob) or hb * wb <= 0:
+        return None
+    if hb * wb * n * n < DCTN_ENTROPY_DECODE_MIN_SAMPLES or not dctn_on_device(config, hb * wb * n * n):
+        return None
+    try:
+        return jpegx.decompress_plane_n(blob, hb * n, wb * n, n, *args, out=out)
     except jpegx.JpegxError:
         return None
 
@@ -432,15 +465,18 @@ def decompress_band_u8(compression_result, config):
             except jpegx.JpegxError:
                 pass
     if not _accelerated(config) and _stock_registry():
-        zz = _decode_stream_n(a, config)
-        if zz is not None:
+        plane = _decode_job_n(a, config, "u8")
+        zz = None if plane is not None else _decode_stream_n(a, config)
+        if plane is not None or zz is not None:
             # inverse with the clamp fused, then the geometry steps on uint8: crop the DCT padding, replicate, crop
             n, bs = config.dct_size, config.block_size
             (rows, cols), _, pooled, _ = geometry.band_geometry(config)
-            try:
-                plane = jpegx.inverse_fused_n(zz, n, *_dctn_mode(config), out="u8")[:pooled[0], :pooled[1]]
-            except jpegx.JpegxError as exc:
-                raise _bad_rle(exc)
+            if plane is None:
+                try:
+                    plane = jpegx.inverse_fused_n(zz, n, *_dctn_mode(config), out="u8")
+                except jpegx.JpegxError as exc:
+                    raise _bad_rle(exc)
+            plane = plane[:pooled[0], :pooled[1]]
             if bs != 1:
                 plane = np.repeat(np.repeat(plane, bs, axis=0), bs, axis=1)
             return np.ascontiguousarray(plane[:rows, :cols])
@@ -477,8 +513,12 @@ def decompress_band(compression_result, config):
                 return band
             todo = todo[2:]
         if not fused and _stock_registry():
-            zz = _decode_stream_n(a, config)
-            band = None if zz is None else _hot_inverse_n(zz, config)
+            band = _decode_job_n(a, config, "i32")
+            if band is not None:
+                band = band.astype(int)
+            else:
+                zz = _decode_stream_n(a, config)
+                band = None if zz is None else _hot_inverse_n(zz, config)
             if band is not None:
                 for cls in todo[5:]:                         # Normalization, DCTPadding, SubSampling, Padding
                     band = cls(config).invert(band)

@@ -322,6 +322,24 @@ size_t jpegx_entropy_decode_workspace_bytes(size_t nbytes, long long nblocks);
 int jpegx_entropy_decode(const uint8_t *d_bytes, size_t nbytes, long long nblocks, void *d_workspace, int16_t *d_zz,
                          int level, jpegx_stream_t stream);
 int jpegx_entropy_decode_status(const void *d_workspace, jpegx_stream_t stream);
+/* The same inverse for blocks of a RUN-TIME length (dct_size 2..32: block_len = N*N; any 1..1024 is taken): bytes -> int32
+ * [nblocks][block_len], the arrays of jpegx_host_entropy_decode_n, i.e. RleBytestream.invert
+ * (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert (pipeline/run_length_encoding.py:66-97).  Block starts
+ * by byte position (csrc/jpegx_entropy_decode_n.hip): one parse per candidate position, radix-4 pointer jumping over
+ * the positions in ceil(log4 nblocks) launches, a lane per block into an LDS tile.  No kernel waits for another workgroup,
+ * every loop is bounded by an argument and every access stays inside the buffers named here whatever the bytes say.
+ * d_bytes: dword aligned, readable and zero for 16 bytes behind the stream; d_zz: 4-byte aligned; d_workspace: 16-byte
+ * aligned, jpegx_entropy_decode_workspace_bytes_n bytes (a function of the three arguments only, 0 for arguments the
+ * decoder refuses, at most 16 * nbytes + 8 * nblocks + 4096), reusable from call to call without clearing; nblocks *
+ * block_len below 2^31; nbytes below 2^32 - 4096.  jpegx_entropy_decode_n only enqueues; jpegx_entropy_decode_status_n
+ * synchronises the stream and answers JPEGX_OK or JPEGX_E_INVALID (not nblocks well-formed blocks that end where the
+ * stream ends: d_zz's content is then unspecified, nothing outside d_zz and the workspace has been written).  There are
+ * no levels.  A stream whose zero padding behind an end marker was damaged is refused here while the host parser,
+ * which skips the padding unread, takes it.                                                                        */
+size_t jpegx_entropy_decode_workspace_bytes_n(size_t nbytes, long long nblocks, int block_len);
+int jpegx_entropy_decode_n(const uint8_t *d_bytes, size_t nbytes, long long nblocks, int block_len, void *d_workspace,
+                           int32_t *d_zz, jpegx_stream_t stream);
+int jpegx_entropy_decode_status_n(const void *d_workspace, jpegx_stream_t stream);
 
 /* ---- batch codec on device buffers: a stack of planes -> one coded byte stream with a plane index, and back ------
  * For every plane what the reference's compress_band makes of it (pipeline/__init__.py:71-76 for transform 'DCT',
@@ -537,6 +555,19 @@ int jpegx_interleave_u8(const void *const *d_planes, int nbands, int rows, int c
                         ptrdiff_t out_pitch, jpegx_stream_t stream);
 /* the entropy decoding alone on the device: bytes -> int16 [nblocks][64] (= jpegx_host_entropy_decode) */
 int jpegx_host_entropy_decode_gpu(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz);
+/* the same for blocks of block_len coefficients: bytes -> int32 [nblocks][block_len] (= jpegx_host_entropy_decode_n;
+ * pipeline/rle_byte_stream.py:61-88, pipeline/run_length_encoding.py:66-97) by jpegx_entropy_decode_n on pooled buffers */
+int jpegx_host_entropy_decode_n_gpu(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len, int32_t *h_zz);
+/* The way back for dct_size N in 2..32 as one pooled job (decompress_band, pipeline/__init__.py:79-88, steps 8-4
+ * inverted): the bytes up into a padded staging span, jpegx_entropy_decode_n (pipeline/rle_byte_stream.py:61-88,
+ * pipeline/run_length_encoding.py:66-97), jpegx_inverse_fused_n with flags 0 (int32 samples) or JPEGX_F_CLAMP_U8 (uint8,
+ * the clamp of pipeline/normalization.py:10-14), the verdict read, the samples down -- the int32 coefficient stream never
+ * on the host.  (H, W): the plane that leaves the inverse, whole N x N blocks; h_out: [H][out_pitch] samples, out_pitch
+ * in samples; sizes and quantisers as for jpegx_host_inverse_fused_n, fewer than 2^31 samples.  Arguments are checked
+ * before any device is touched.  A stream that is not (H/N) * (W/N) well-formed blocks: JPEGX_E_INVALID, h_out is not
+ * written, the job context is given back.                                                                          */
+int jpegx_host_decompress_plane_n(const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode, double param,
+                                  unsigned flags, void *h_out, ptrdiff_t out_pitch);
 /* frees the pooled device / pinned buffers and streams of every job context of the current device (waits for jobs
  * of other threads to finish; JPEGX_E_INVALID while the calling thread itself holds a context) */
 int jpegx_host_pool_release(void);
@@ -624,6 +655,13 @@ int jpegx_entropy_emit_n_on(int device, const int32_t *d_zz, long long nblocks, 
                             uint8_t *d_out, jpegx_stream_t stream);
 int jpegx_host_compress_begin_n_on(int device, const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode,
                                    double param, size_t *nbytes);
+int jpegx_entropy_decode_n_on(int device, const uint8_t *d_bytes, size_t nbytes, long long nblocks, int block_len,
+                              void *d_workspace, int32_t *d_zz, jpegx_stream_t stream);
+int jpegx_entropy_decode_status_n_on(int device, const void *d_workspace, jpegx_stream_t stream);
+int jpegx_host_entropy_decode_n_gpu_on(int device, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int block_len,
+                                       int32_t *h_zz);
+int jpegx_host_decompress_plane_n_on(int device, const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode,
+                                     double param, unsigned flags, void *h_out, ptrdiff_t out_pitch);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
