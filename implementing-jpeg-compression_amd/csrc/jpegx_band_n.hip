@@ -1,0 +1,119 @@
+// jpegx_band_n.hip -- steps 0-3 of the reference for a dct_size-N band as ONE gather on the device: Padding
+// (pipeline/padding.py:8-12, edge replication of raw samples to a multiple of block_size), SubSampling
+// (pipeline/subsampling.py:9-11, np.mean over bs x bs tiles), DCTPadding (pipeline/dct_padding.py:8-9, edge replication
+// of POOLED samples to a multiple of dct_size) and Normalization (pipeline/normalization.py:7-8, the identity: there is no
+// -128 shift).  uint8 band [rows][pitch] in, the float64 plane [H][out_pitch] that jpegx_forward_fused_n reads out.
+//
+// With P = ceil(rows / bs) pooled rows and H = ceil(P / N) * N (columns likewise), output sample (y, x) is
+//     ty = min(y, P_rows - 1), tx = min(x, P_cols - 1)                                  (DCTPadding)
+//     s  = sum over u, w < bs of band[min(ty * bs + u, rows - 1)][min(tx * bs + w, cols - 1)]      (Padding)
+//     out[y][x] = (double)s / (double)(bs * bs)                                         (SubSampling)
+// s is an integer below 2^24, so this is np.mean's double bit for bit (the exact sum, one division -- what k_mean_pool_f64
+// relies on as well).  Every read index is clamped into [0, rows) x [0, cols): no argument combination reads outside the
+// band, and nothing is written outside [H] x [W] of the output.  Part of libjpegx.so (C ABI: include/jpegx.h).
+#include <limits.h>
+
+#include "jpegx_internal.h"
+
+namespace {
+
+// block_size 1: no sum, a byte becomes a double.  A lane owns FOUR consecutive outputs of one plane row (item = row *
+// quads + quad; consecutive lanes, consecutive quads): one dword load where the four bytes are inside the band's row and
+// the address is dword aligned, clamped byte loads otherwise; two 16-byte stores where the quad is inside the row and the
+// address is 16-byte aligned (8-byte stores run at 0.54-0.70x the rate of 16-byte ones on this chip), doubles one by one
+// otherwise.
+__global__ __launch_bounds__(256) void k_band_plane_n_bs1(const uint8_t *__restrict__ band, size_t pitch, int rows, int cols, int W, int quads,
+                                                          long long items, double *__restrict__ out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int y = (int)(i / quads), x0 = (int)(i - (long long)y * quads) * 4;
+    const uint8_t *src = band + (size_t)min(y, rows - 1) * pitch;
+    unsigned v[4];
+    if (x0 + 4 <= cols && (reinterpret_cast<uintptr_t>(src + x0) & 3u) == 0) {
+        const unsigned q = *reinterpret_cast<const unsigned *>(src + x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (q >> (8 * k)) & 0xFFu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = src[min(x0 + k, cols - 1)];
+    }
+    double *dst = out + (size_t)y * opitch + x0;
+    if (x0 + 4 <= W && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        reinterpret_cast<double2 *>(dst)[0] = make_double2((double)v[0], (double)v[1]);
+        reinterpret_cast<double2 *>(dst)[1] = make_double2((double)v[2], (double)v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x0 + k < W) dst[k] = (double)v[k];
+    }
+}
+
+// Any block_size: one lane per output sample, consecutive lanes on consecutive samples of one plane row -- a wave reads
+// 64 * bs contiguous bytes of each of its bs input rows and stores a run of 64 doubles.  Both loops run bs times.
+__global__ __launch_bounds__(256) void k_band_plane_n(const uint8_t *__restrict__ band, size_t pitch, int rows, int cols, int bs, int prows,
+                                                      int pcols, int W, long long items, double *__restrict__ out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+    const int r0 = min(y, prows - 1) * bs, c0 = min(x, pcols - 1) * bs;      // r0 < rows, c0 < cols: the tile starts inside the band
+    unsigned s = 0;
+    const int rlast = rows - 1 - r0, clast = cols - 1 - c0;                // both >= 0; the clamps below never add past rows - 1, cols - 1
+    if (bs <= clast + 1) {                                                  // the tile's columns are all there: no clamp per sample
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *p = band + (size_t)(r0 + min(u, rlast)) * pitch + c0;
+            for (int w = 0; w < bs; ++w) s += p[w];
+        }
+    } else {
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *p = band + (size_t)(r0 + min(u, rlast)) * pitch + c0;
+            for (int w = 0; w < bs; ++w) s += p[min(w, clast)];
+        }
+    }
+    out[(size_t)y * opitch + x] = (double)s / (double)(bs * bs);
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpegx_band_shape_n(int rows, int cols, int bs, int N, int *H, int *W)
+{
+    if (!H || !W) return fail(JPEGX_E_INVALID, "null pointer");
+    if (rows < 1 || cols < 1) return fail(JPEGX_E_INVALID, "band_shape_n: rows and cols must be at least 1");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "band_shape_n: block_size must be in 1..255");
+    if (N < 2 || N > 32) return fail(JPEGX_E_INVALID, "dct_size must be 2 .. 32");
+    const long long ph = ((long long)rows + bs - 1) / bs, pw = ((long long)cols + bs - 1) / bs;
+    const long long h = (ph + N - 1) / N * N, w = (pw + N - 1) / N * N;
+    if (h > INT_MAX || w > INT_MAX || h * w > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one plane");
+    *H = (int)h;
+    *W = (int)w;
+    return JPEGX_OK;
+}
+
+int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out, ptrdiff_t out_pitch,
+                       jpegx_stream_t stream)
+{
+    if (!d_band || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    int H = 0, W = 0;
+    const int rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W);
+    if (rc) return rc;
+    if (pitch < (ptrdiff_t)cols || out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if (reinterpret_cast<uintptr_t>(d_out) % 8) return fail(JPEGX_E_INVALID, "band_plane_n: misaligned output pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (bs == 1) {
+        const int quads = (W + 3) / 4;
+        const long long items = (long long)H * quads;                      // below 2^31: H * W is
+        hipLaunchKernelGGL(k_band_plane_n_bs1, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d_band, (size_t)pitch, rows, cols, W, quads,
+                           items, d_out, (size_t)out_pitch);
+    } else {
+        const long long items = (long long)H * W;
+        hipLaunchKernelGGL(k_band_plane_n, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d_band, (size_t)pitch, rows, cols, bs,
+                           (int)(((long long)rows + bs - 1) / bs), (int)(((long long)cols + bs - 1) / bs), W, items, d_out, (size_t)out_pitch);
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+}  // extern "C"

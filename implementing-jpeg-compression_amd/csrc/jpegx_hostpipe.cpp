@@ -457,6 +457,41 @@ int begin_epilogue(Job &job, unsigned long long total, size_t *nbytes)
     return job.hold();
 }
 
+// the quantisers of the dct_size-N kernels and their parameters, as jpegx_forward_fused_n / jpegx_inverse_fused_n take them
+int check_quantiser_n(int mode, double param)
+{
+    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE)
+        return fail(JPEGX_E_INVALID, "dct_size other than 8 takes the quantisers none, discard and divide");
+    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
+        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
+    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
+        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
+    return JPEGX_OK;
+}
+
+// What the dct_size-N compress_begin entries share once the float64 plane [H][W] of step 3 is on the device (or on its
+// way there on `st`): jpegx_forward_fused_n, the sizes, the head read back, the verdict, the emitter; the job stays open.
+// The emitter is enqueued once the size is known: a block of N * N coefficients has no small worst case to size the
+// destination by beforehand.
+int begin_tail_n(Job &job, BandSlot &slot, const double *d_plane, int H, int W, int N, int mode, double param, hipStream_t st,
+                 unsigned long long *head, size_t *nbytes)
+{
+    const long long nblocks = (long long)(H / N) * (W / N);
+    const int len = N * N;
+    unsigned long long total = 0;
+    int rc;
+    if ((rc = slot.d_zz.ensure((size_t)H * W * 4)) || (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len)))) return rc;
+    const int32_t *d_zz = static_cast<const int32_t *>(slot.d_zz.p);
+    if ((rc = jpegx_forward_fused_n(d_plane, H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
+        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)) || (rc = enqueue_head(head, slot, st)))
+        return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
+    if ((rc = head_verdict(head, &total)) || (rc = slot.d_out.ensure((size_t)total + 64)) ||
+        (rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st)))
+        return rc;
+    return begin_epilogue(job, total, nbytes);
+}
+
 }  // namespace
 
 extern "C" {
@@ -518,9 +553,8 @@ int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int row
     return compress_begin_impl(h_plane, elem_size, H, W, rows, cols, pitch, bs, mode, param, nbytes, true);
 }
 
-// The band job for dct_size N (2..32): the float64 plane that leaves step 3 up, jpegx_forward_fused_n, the run-time block
-// length entropy stage (csrc/jpegx_entropy_n.hip), the bytes left in slot 0's d_out for _finish.  The emitter is enqueued
-// once the size is known: a block of N * N coefficients has no small worst case to size the destination by beforehand.
+// The band job for dct_size N (2..32): the float64 plane that leaves step 3 up, then begin_tail_n -- jpegx_forward_fused_n,
+// the run-time block length entropy stage (csrc/jpegx_entropy_n.hip), the bytes left in slot 0's d_out for _finish.
 int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param, size_t *nbytes)
 {
     if (!h_plane || !nbytes) return fail(JPEGX_E_INVALID, "null pointer");
@@ -528,35 +562,57 @@ int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t p
     if (H <= 0 || W <= 0 || (H % N) != 0 || (W % N) != 0) return fail(JPEGX_E_INVALID, "plane height and width must be positive multiples of dct_size");
     if (pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
     if ((long long)H * W > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one plane");
-    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE)
-        return fail(JPEGX_E_INVALID, "dct_size other than 8 takes the quantisers none, discard and divide");
-    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
-        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
-    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
-        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
-    const long long nblocks = (long long)(H / N) * (W / N);
-    const int len = N * N;
+    int rc;
+    if ((rc = check_quantiser_n(mode, param))) return rc;
     Job job;
     hipStream_t st = nullptr;
-    unsigned long long *head = nullptr, total = 0;
-    int rc;
+    unsigned long long *head = nullptr;
     if ((rc = begin_prologue(job, &st, &head))) return rc;
     BandSlot &slot = job.pool->slot[0];
-    if ((rc = slot.d_in.ensure((size_t)H * W * 8)) || (rc = slot.d_zz.ensure((size_t)H * W * 4)) ||
-        (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len))))
-        return rc;
+    if ((rc = slot.d_in.ensure((size_t)H * W * 8))) return rc;
     hipError_t e = pitch == W ? hipMemcpyAsync(slot.d_in.p, h_plane, (size_t)H * W * 8, hipMemcpyHostToDevice, st)
                               : hipMemcpy2DAsync(slot.d_in.p, (size_t)W * 8, h_plane, (size_t)pitch * 8, (size_t)W * 8, (size_t)H, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
-    const int32_t *d_zz = static_cast<const int32_t *>(slot.d_zz.p);
-    if ((rc = jpegx_forward_fused_n(static_cast<const double *>(slot.d_in.p), H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
-        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)) || (rc = enqueue_head(head, slot, st)))
+    return begin_tail_n(job, slot, static_cast<const double *>(slot.d_in.p), H, W, N, mode, param, st, head, nbytes);
+}
+
+// The same job from the band as the caller holds it (pipeline/__init__.py:71-76 for transform 'DCT', dct_size N): rows x
+// cols 8-bit samples up as bytes -- 1 byte per sample instead of the 8 of the float64 plane -- and steps 0-3 (Padding,
+// SubSampling, DCTPadding, Normalization: pipeline/padding.py:8-12, subsampling.py:9-11, dct_padding.py:8-9,
+// normalization.py:7-8) as one launch on the device (jpegx_band_plane_n) into slot 0's d_tmp, then begin_tail_n.
+int jpegx_host_compress_begin_band_n(const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                                     double param, size_t *nbytes)
+{
+    if (!h_band || !nbytes) return fail(JPEGX_E_INVALID, "null pointer");
+    if (elem_size != 1 && elem_size != 4 && elem_size != 8) return fail(JPEGX_E_UNSUPPORTED, "host_compress takes uint8, int32 or int64 samples");
+    int H = 0, W = 0, rc;
+    if ((rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W))) return rc;
+    if (pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if ((rc = check_quantiser_n(mode, param))) return rc;
+    Job job;
+    hipStream_t st = nullptr;
+    unsigned long long *head = nullptr;
+    if ((rc = begin_prologue(job, &st, &head))) return rc;
+    DevicePool *pool = job.pool;
+    BandSlot &slot = pool->slot[0];
+    const size_t in_bytes = (size_t)rows * cols;
+    if ((rc = slot.d_in.ensure(in_bytes)) || (rc = slot.d_tmp.ensure((size_t)H * W * 8))) return rc;
+    if (elem_size != 1) {
+        // wide integers: checked and narrowed into the pinned staging area strip by strip, every strip on its way while the
+        // next is narrowed; a sample outside 0..255 ends the job here (the Job waits for the strips already enqueued)
+        if ((rc = pool->h_in.ensure(in_bytes))) return rc;
+        uint8_t *stage = static_cast<uint8_t *>(pool->h_in.p);
+        rc = elem_size == 8 ? narrow_and_upload(static_cast<const int64_t *>(h_band), pitch, rows, cols, stage, slot.d_in.p, cols, st)
+                            : narrow_and_upload(static_cast<const int32_t *>(h_band), pitch, rows, cols, stage, slot.d_in.p, cols, st);
+        if (rc) return rc;
+    } else {
+        hipError_t e = pitch == cols ? hipMemcpyAsync(slot.d_in.p, h_band, in_bytes, hipMemcpyHostToDevice, st)
+                                     : hipMemcpy2DAsync(slot.d_in.p, (size_t)cols, h_band, (size_t)pitch, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
+    }
+    if ((rc = jpegx_band_plane_n(static_cast<const uint8_t *>(slot.d_in.p), rows, cols, cols, bs, N, static_cast<double *>(slot.d_tmp.p), W, st)))
         return rc;
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
-    if ((rc = head_verdict(head, &total)) || (rc = slot.d_out.ensure((size_t)total + 64)) ||
-        (rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st)))
-        return rc;
-    return begin_epilogue(job, total, nbytes);
+    return begin_tail_n(job, slot, static_cast<const double *>(slot.d_tmp.p), H, W, N, mode, param, st, head, nbytes);
 }
 
 int jpegx_host_compress_finish(uint8_t *h_out)
@@ -1034,16 +1090,11 @@ int jpegx_host_decompress_plane_n(const uint8_t *h_bytes, size_t nbytes, int H, 
     if (H <= 0 || W <= 0 || (H % N) != 0 || (W % N) != 0) return fail(JPEGX_E_INVALID, "plane height and width must be positive multiples of dct_size");
     if (out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than width");
     if ((long long)H * W > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one plane");
-    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE)
-        return fail(JPEGX_E_INVALID, "dct_size other than 8 takes the quantisers none, discard and divide");
-    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
-        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
-    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
-        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
+    int rc;
+    if ((rc = check_quantiser_n(mode, param))) return rc;
     if (flags & ~(unsigned)JPEGX_F_CLAMP_U8) return fail(JPEGX_E_INVALID, "decompress_plane_n: the only flag is JPEGX_F_CLAMP_U8");
     const long long nblocks = (long long)(H / N) * (W / N);
     const int len = N * N;
-    int rc;
     if ((rc = jpegx_internal_decode_check_n(nbytes, nblocks, len))) return rc;
     const size_t esz = (flags & JPEGX_F_CLAMP_U8) ? 1 : 4, row = (size_t)W * esz;
     Job job;

@@ -112,3 +112,8 @@ JPEGX_ON(jpegx_host_entropy_decode_n_gpu, (int device, const uint8_t *h_bytes, s
          (h_bytes, nbytes, nblocks, block_len, h_zz))
 JPEGX_ON(jpegx_host_decompress_plane_n, (int device, const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode, double param, unsigned flags, void *h_out, ptrdiff_t out_pitch),
          (h_bytes, nbytes, H, W, N, mode, param, flags, h_out, out_pitch))
+JPEGX_ON(jpegx_band_shape_n, (int device, int rows, int cols, int bs, int N, int *H, int *W), (rows, cols, bs, N, H, W))
+JPEGX_ON(jpegx_band_plane_n, (int device, const uint8_t *d_band, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_band, rows, cols, pitch, bs, N, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_host_compress_begin_band_n, (int device, const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param, size_t *nbytes),
+         (h_band, elem_size, rows, cols, pitch, bs, N, mode, param, nbytes))

@@ -170,6 +170,9 @@ SIGNATURES = {
     "jpegx_entropy_decode_status_n": [_vp, _vp],
     "jpegx_host_entropy_decode_n_gpu": [_vp, _sz, _c.c_longlong, _int, _vp],
     "jpegx_host_decompress_plane_n": [_vp, _sz, _int, _int, _int, _int, _dbl, _uint, _vp, _pd],
+    "jpegx_band_shape_n": [_int, _int, _int, _int, _c.POINTER(_int), _c.POINTER(_int)],
+    "jpegx_band_plane_n": [_vp, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_host_compress_begin_band_n": [_vp, _int, _int, _int, _pd, _int, _int, _int, _dbl, _c.POINTER(_sz)],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -190,7 +193,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_compress_image_ragged", "jpegx_host_compress_image_packed_ragged", "jpegx_forward_fused_n",
               "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n", "jpegx_entropy_sizes_n", "jpegx_entropy_emit_n",
               "jpegx_host_compress_begin_n", "jpegx_entropy_decode_n", "jpegx_entropy_decode_status_n",
-              "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n"):
+              "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n", "jpegx_band_shape_n", "jpegx_band_plane_n",
+              "jpegx_host_compress_begin_band_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -1089,6 +1093,72 @@ def compress_plane_n(plane, n, mode="none", param=0.0):
     nbytes = ctypes.c_size_t(0)
     check(L.jpegx_host_compress_begin_n(a.ctypes.data, h, w, w, n, mode_of(mode), float(param), ctypes.byref(nbytes)),
           "jpegx_host_compress_begin_n")
+    try:
+        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes.value)      # uninitialised bytes, filled below
+        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
+    except BaseException:
+        L.jpegx_host_compress_abort()
+        raise
+    check(rc, "jpegx_host_compress_finish")
+    return blob
+
+
+def band_shape_n(rows, cols, bs, n):
+    """(H, W) of the plane that leaves step 3 for a rows x cols band at block_size bs and dct_size n
+    (jpegx_band_shape_n: pipeline.geometry.band_geometry's last pair; host arithmetic, no device needed)."""
+    h, w = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().jpegx_band_shape_n(int(rows), int(cols), int(bs), int(n), ctypes.byref(h), ctypes.byref(w)), "jpegx_band_shape_n")
+    return h.value, w.value
+
+
+def _band_u8(band):
+    a = band if isinstance(band, np.ndarray) else np.asarray(band)
+    if a.ndim != 2 or a.size == 0 or a.dtype.kind not in "ui":
+        raise JpegxError("expected a non-empty 2-D band of an integer dtype, got %r of %s" % (a.shape, a.dtype))
+    if a.dtype != np.uint8:
+        if a.min() < 0 or a.max() > 255:
+            raise JpegxError("samples outside 0..255: not an 8-bit band")
+        a = a.astype(np.uint8)
+    return np.ascontiguousarray(a)
+
+
+def band_plane_n(band, bs, n):
+    """8-bit band (rows, cols) -> the float64 plane (H, W) that leaves step 3: Padding, SubSampling, DCTPadding and
+    Normalization.execute for block_size bs and dct_size n as one launch (jpegx_band_plane_n), bit for bit what the
+    host step classes make of the band."""
+    a = _band_u8(band)
+    rows, cols = a.shape
+    h, w = band_shape_n(rows, cols, bs, n)
+    require_device()
+    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(h * w * 8)
+    try:
+        din.upload(a)
+        check(lib().jpegx_band_plane_n(din.ptr, rows, cols, cols, int(bs), int(n), dout.ptr, w, None), "jpegx_band_plane_n")
+        return dout.download((h, w), np.float64)
+    finally:
+        din.free()
+        dout.free()
+
+
+def compress_band_n(band, bs, n, mode="none", param=0.0):
+    """Integer band (rows, cols) of uint8 / int32 / int64 -> bytes: all nine steps of compress_band for dct_size n as one
+    pooled device job (jpegx_host_compress_begin_band_n / _finish) -- the band goes up as bytes, steps 0-3 are one launch
+    (jpegx_band_plane_n), steps 4-8 those of compress_plane_n.  None when the native entry says "not an 8-bit band" (a
+    sample outside 0..255, another dtype or layout); JpegxError naming BadRleCodeError for an amplitude beyond 15 bits."""
+    src = band if isinstance(band, np.ndarray) else np.asarray(band)
+    elem = _ELEM_OF.get(src.dtype)
+    if elem is None or src.ndim != 2 or src.size == 0:
+        return None
+    if src.strides[1] != elem or src.strides[0] < src.shape[1] * elem or src.strides[0] % elem:
+        src = np.ascontiguousarray(src)                                 # anything but rows a fixed number of samples apart
+    rows, cols = src.shape
+    L = lib()
+    nbytes = ctypes.c_size_t(0)
+    rc = L.jpegx_host_compress_begin_band_n(src.ctypes.data, elem, rows, cols, src.strides[0] // elem, int(bs), int(n), mode_of(mode),
+                                            float(param), ctypes.byref(nbytes))
+    if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not an 8-bit band after all
+        return None
+    check(rc, "jpegx_host_compress_begin_band_n")
     try:
         blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes.value)      # uninitialised bytes, filled below
         rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))

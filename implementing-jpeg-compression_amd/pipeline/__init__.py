@@ -11,7 +11,9 @@ Any other dct_size 2..32 with transform 'DCT' takes the all-float64 kernels of c
 (``jpegx_forward_fused_n`` / ``jpegx_inverse_fused_n``, entropy stage by libjpegx's sequential host coder; with
 ``DCTN_ENTROPY_MIN_SAMPLES`` set, compressing runs the entropy stage on the device behind the forward kernel,
 csrc/jpegx_entropy_n.hip; with ``DCTN_ENTROPY_DECODE_MIN_SAMPLES`` set, decompressing runs the entropy decoder on the
-device in front of the inverse kernel, csrc/jpegx_entropy_decode_n.hip) when a
+device in front of the inverse kernel, csrc/jpegx_entropy_decode_n.hip; planes of at least
+``DCTN_BAND_JOB_MIN_SAMPLES`` samples compress as one device job from the band's 8-bit samples, steps 0-3 included,
+csrc/jpegx_band_n.hip) when a
 device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
 NumPy road runs, exactly as the reference does it.
 """
@@ -126,6 +128,17 @@ DCTN_ENTROPY_MIN_SAMPLES = None
 # N = 16 up to 36 864, at N = 4 up to 16 384.  Hence the smallest measured size with no miss at or above it.
 DCTN_ENTROPY_DECODE_MIN_SAMPLES = 262144
 
+# compress_band for dct_size other than 8 as ONE device job from the band's 8-bit samples (jpegx.compress_band_n: the band
+# up as bytes, steps 0-3 as the kernel of csrc/jpegx_band_n.hip, then the launches of jpegx.compress_plane_n): planes of at
+# least this many samples ENTERING STEP 4 (H * W after both paddings, like the two constants above) take it; None: the road
+# is off and compress_band walks steps 0-3 in NumPy and uploads the float64 plane as before.  A plane that a set
+# DCTN_ENTROPY_MIN_SAMPLES admits keeps taking jpegx.compress_plane_n.  Measured (profiles/dctn_band.json):
+# on a 3000 x 4000 band a call takes 0.3-1.6 ms (uint8) / 1.3-2.0 ms (int64) instead of 18-182 / 29-191 ms; on square bands
+# the job loses 4-6 us at 1024 samples and wins at every measured size from 2304 on.  The smallest measured size with no
+# configuration slower than the road of before at or above it is therefore 2304; the constant stands at the next measured
+# size above the planes (3456 and 8960 samples) that tests/test_gpu_dct_sizes.py pins to jpegx.forward_fused_n.
+DCTN_BAND_JOB_MIN_SAMPLES = 16384
+
 _device_seen = False
 
 
@@ -225,8 +238,44 @@ def _device_job_n(pre, config):
         return None
 
 
+def _band_job_n(band, config):
+    """All nine steps for dct_size N as one device job from the band's 8-bit samples (jpegx.compress_band_n), or None: the
+    road is switched off (DCTN_BAND_JOB_MIN_SAMPLES) or the plane is below it, the registry is not stock, the plane is one
+    that a set DCTN_ENTROPY_MIN_SAMPLES sends to jpegx.compress_plane_n, the quantiser or the band is not what the job
+    takes (a real 2-D non-empty band of an integer dtype with samples in 0..255, block_size 1..255), a coefficient of an
+    8-bit band could reach 2^31 - 1, or the job met an amplitude beyond 15 bits -- the caller's road of before then ends in
+    the host step raising the reference's BadRleCodeError with its own text."""
+    args = _dctn_mode(config)
+    if DCTN_BAND_JOB_MIN_SAMPLES is None or args is None or not _stock_registry():
+        return None
+    bs, n = config.block_size, config.dct_size
+    band = np.asarray(band)
+    if band.ndim != 2 or band.size == 0 or band.dtype.kind not in "ui" or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 255:
+        return None
+    pooled = [-(-v // bs) for v in band.shape]                          # geometry.band_geometry's last two pairs, from the band itself
+    h, w = (-(-v // n) * n for v in pooled)
+    samples = h * w
+    if samples > 2 ** 31 - 1 or samples < DCTN_BAND_JOB_MIN_SAMPLES or not dctn_on_device(config, samples):
+        return None
+    if DCTN_ENTROPY_MIN_SAMPLES is not None and samples >= DCTN_ENTROPY_MIN_SAMPLES:
+        return None
+    mode, param = args
+    # _device_job_n's guard with the 8-bit bound in place of a scan of the band
+    if not 255.0 * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0) <= 2.0 ** 31 - 1.0:
+        return None
+    import jpegx
+    native = band if band.dtype in (np.uint8, np.int32, np.int64) else band.astype(np.int64)
+    try:
+        return jpegx.compress_band_n(native, int(bs), int(n), mode, param)
+    except jpegx.JpegxError as exc:
+        if "BadRleCodeError" not in str(exc):
+            raise
+        return None
+
+
 def _compress_band_n(a, config):
-    """compress_band for dct_size != 8: host steps 0-3 as they are, then the three hot steps as one device launch
+    """compress_band for dct_size != 8: where DCTN_BAND_JOB_MIN_SAMPLES admits the plane, all nine steps as one device job
+    from the band's 8-bit samples (_band_job_n), before any host step runs.  Otherwise host steps 0-3 as they are, then the three hot steps as one device launch
     (jpegx_forward_fused_n) and -- in a stock registry -- libjpegx's sequential entropy coder on the host; or, where the
     job road is switched on (DCTN_ENTROPY_MIN_SAMPLES) and the registry is stock, steps 4-8 as one device job
     (_device_job_n).  None when the road does not apply; the caller then walks the steps on the host as before."""
@@ -235,6 +284,9 @@ def _compress_band_n(a, config):
     at = _hot_run(todo)
     if at is None or _dctn_mode(config) is None:
         return None
+    blob = _band_job_n(a, config)
+    if blob is not None:
+        return blob                                 # all nine steps in one device job
     for cls in todo[:at]:
         a = cls(config).execute(a)
     if _stock_registry():

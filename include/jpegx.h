@@ -415,6 +415,21 @@ int jpegx_padded_shape(int rows, int cols, int bs, int *H, int *W);
 int jpegx_pad_edges(void *d_planes, int elem_size, int nplanes, int rows, int cols, int bs, ptrdiff_t pitch,
                     jpegx_stream_t stream);
 
+/* ---- steps 0-3 of a dct_size-N band on the device: Padding.execute (pipeline/padding.py:8-12), SubSampling.execute
+ * (pipeline/subsampling.py:9-11), DCTPadding.execute (pipeline/dct_padding.py:8-9) and Normalization.execute
+ * (pipeline/normalization.py:7-8, the identity) as one gather -------------------------------------------------------
+ * jpegx_band_shape_n: H, W of the plane that leaves step 3 for a rows x cols band -- per axis P = ceil(n / bs) pooled
+ * samples, ceil(P / N) * N after DCT padding (pipeline.geometry.band_geometry).  Host arithmetic only, no device needed.
+ * rows, cols >= 1; bs in 1..255 (else JPEGX_E_UNSUPPORTED); N in 2..32; H * W <= 2^31 - 1 (else JPEGX_E_INVALID).
+ * jpegx_band_plane_n (enqueue only): uint8 band [rows][pitch] -> float64 plane [H][out_pitch] (pitches in elements),
+ *   out[y][x] = (double)(sum over u, w < bs of band[min(ty * bs + u, rows - 1)][min(tx * bs + w, cols - 1)]) / (double)(bs * bs)
+ * with ty = min(y, P_rows - 1), tx = min(x, P_cols - 1): the exact integer sum and one division, np.mean's double bit for
+ * bit.  Reads stay inside [rows] x [cols] of the band, writes inside [H] x [W] of the output (pitch slack untouched).
+ * One launch of any height (no limit of 65 535 rows).                                                              */
+int jpegx_band_shape_n(int rows, int cols, int bs, int N, int *H, int *W);
+int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out,
+                       ptrdiff_t out_pitch, jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -495,6 +510,15 @@ int jpegx_host_compress_begin_ragged(const void *h_plane, int elem_size, int row
  * given back and no job is open then.                                                                             */
 int jpegx_host_compress_begin_n(const double *h_plane, int H, int W, ptrdiff_t pitch, int N, int mode, double param,
                                 size_t *nbytes);
+/* _begin for dct_size N in 2..32 on the BAND as the caller holds it: rows x cols samples of uint8 (elem_size 1), int32 (4)
+ * or int64 (8), rows `pitch` elements apart.  The band goes up as bytes (wide integers are range-checked and narrowed on
+ * the way: a sample outside 0..255 is JPEGX_E_UNSUPPORTED, no job left open), jpegx_band_plane_n makes the float64 plane
+ * of steps 0-3 on the device (Padding, SubSampling, DCTPadding, Normalization.execute: pipeline/padding.py:8-12,
+ * subsampling.py:9-11, dct_padding.py:8-9, normalization.py:7-8), then the very launches of jpegx_host_compress_begin_n.
+ * bs in 1..255, H * W (jpegx_band_shape_n) <= 2^31 - 1; every argument is checked before a device is touched.  _finish,
+ * _abort and the BadRleCodeError refusal as above.                                                                 */
+int jpegx_host_compress_begin_band_n(const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int N,
+                                     int mode, double param, size_t *nbytes);
 /* The way back (decompress_band, pipeline/__init__.py:79-88, transform 'DCT', dct_size 8): the band's byte
  * stream up, RleBytestream.invert + RunLengthEncoding.invert (pipeline/rle_byte_stream.py:61-88,
  * pipeline/run_length_encoding.py:66-97) ON THE DEVICE -- the stream has no index, block starts are recovered
@@ -662,6 +686,11 @@ int jpegx_host_entropy_decode_n_gpu_on(int device, const uint8_t *h_bytes, size_
                                        int32_t *h_zz);
 int jpegx_host_decompress_plane_n_on(int device, const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode,
                                      double param, unsigned flags, void *h_out, ptrdiff_t out_pitch);
+int jpegx_band_plane_n_on(int device, const uint8_t *d_band, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out,
+                          ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_band_shape_n_on(int device, int rows, int cols, int bs, int N, int *H, int *W);
+int jpegx_host_compress_begin_band_n_on(int device, const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs,
+                                        int N, int mode, double param, size_t *nbytes);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
