@@ -194,6 +194,25 @@ def _hot_forward_n(pre, config):
     return zz
 
 
+def _whole_divisor(args):
+    """False for 'divide' with a divisor that is no integer.  Quantization.invert stores a * divisor into an array of the
+    dtype it was handed, and step 7 hands back integers: the reference then truncates every restored coefficient toward
+    zero (2773.5 -> 2773, -7.5 -> -7), which the device kernels, multiplying in float64, do not."""
+    return args[0] != "divide" or args[1] == np.trunc(args[1])
+
+
+def _restored_stream_n(zz, args):
+    """(stream, mode, param) for jpegx.inverse_fused_n on an INTEGER stream as the reference restores it: as they are with a
+    whole divisor; else the coefficients restored here, truncated like the reference's integer array does it, and handed
+    over under 'none'.  None when such a coefficient leaves the int32 range."""
+    if _whole_divisor(args) or zz.dtype.kind not in "iu":
+        return (zz,) + tuple(args)
+    restored = np.trunc(zz.astype(np.float64) * args[1])
+    if restored.size and not np.abs(restored).max() < 2.0 ** 31:
+        return None
+    return restored.astype(np.int32), "none", 0.0
+
+
 def _hot_inverse_n(zz, config):
     """Steps 6+5+4 inverted for dct_size N in one launch (int samples), or None when the stream stays on the host."""
     n = config.dct_size
@@ -202,12 +221,16 @@ def _hot_inverse_n(zz, config):
     if args is None or zz.ndim != 3 or zz.shape[2] != n * n or zz.dtype.kind not in "fiu" \
             or not dctn_on_device(config, zz.size):
         return None
+    todo = _restored_stream_n(zz, args)
+    if todo is None:
+        return None
+    zz, mode, param = todo
     if zz.dtype != np.int32:
         if np.abs(zz).max() >= 2 ** 31 or not np.array_equal(zz, np.rint(zz)):
             return None
         zz = zz.astype(np.int32)
     import jpegx
-    return jpegx.inverse_fused_n(zz, n, *args).astype(int)
+    return jpegx.inverse_fused_n(zz, n, mode, param).astype(int)
 
 
 def _device_job_n(pre, config):
@@ -329,14 +352,15 @@ def _decode_stream_n(blob, config):
 def _decode_job_n(blob, config, out):
     """Steps 8-4 inverted for dct_size N as one pooled device job (jpegx.decompress_plane_n): the samples of the plane of
     whole N x N blocks, uint8 (clamped) for out 'u8' or int32 for 'i32'; or None -- the job road is switched off
-    (DCTN_ENTROPY_DECODE_MIN_SAMPLES), _decode_stream_n's preconditions do not hold, or the device refused the stream: the
-    caller's road of before then ends in the host parser and the host steps naming the fault."""
+    (DCTN_ENTROPY_DECODE_MIN_SAMPLES), _decode_stream_n's preconditions do not hold, the divisor is no integer (the job
+    restores without the reference's truncation, _whole_divisor), or the device refused the stream: the caller's road of
+    before then ends in the host parser and the host steps naming the fault."""
     import jpegx
     rle = run_length_encoding.RunLengthEncoding(config)
     hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
     n = config.dct_size
     args = _dctn_mode(config)
-    if DCTN_ENTROPY_DECODE_MIN_SAMPLES is None or not _stock_registry() or args is None:
+    if DCTN_ENTROPY_DECODE_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
         return None
     if not isinstance(blob, (bytes, bytearray)) or not len(blob) or hb * wb <= 0:
         return None
@@ -519,13 +543,14 @@ def decompress_band_u8(compression_result, config):
     if not _accelerated(config) and _stock_registry():
         plane = _decode_job_n(a, config, "u8")
         zz = None if plane is not None else _decode_stream_n(a, config)
-        if plane is not None or zz is not None:
+        todo = None if zz is None else _restored_stream_n(zz, _dctn_mode(config))
+        if plane is not None or todo is not None:
             # inverse with the clamp fused, then the geometry steps on uint8: crop the DCT padding, replicate, crop
             n, bs = config.dct_size, config.block_size
             (rows, cols), _, pooled, _ = geometry.band_geometry(config)
             if plane is None:
                 try:
-                    plane = jpegx.inverse_fused_n(zz, n, *_dctn_mode(config), out="u8")
+                    plane = jpegx.inverse_fused_n(todo[0], n, todo[1], todo[2], out="u8")
                 except jpegx.JpegxError as exc:
                     raise _bad_rle(exc)
             plane = plane[:pooled[0], :pooled[1]]
