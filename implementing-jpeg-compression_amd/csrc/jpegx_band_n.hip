@@ -10,7 +10,12 @@
 //     out[y][x] = (double)s / (double)(bs * bs)                                         (SubSampling)
 // s is an integer below 2^24, so this is np.mean's double bit for bit (the exact sum, one division -- what k_mean_pool_f64
 // relies on as well).  Every read index is clamped into [0, rows) x [0, cols): no argument combination reads outside the
-// band, and nothing is written outside [H] x [W] of the output.  Part of libjpegx.so (C ABI: include/jpegx.h).
+// band, and nothing is written outside [H] x [W] of the output.
+//
+// And the way back for the clamped bytes of jpegx_inverse_fused_n as ONE scatter (jpegx_inflate_crop_u8): DCTPadding.invert
+// (pipeline/dct_padding.py:11-21, a crop), SubSampling.invert (pipeline/subsampling.py:13-14, util.inflate: every sample bs x bs
+// times) and Padding.invert (pipeline/padding.py:14-16, a crop): out[y][x] = plane[y / bs][x / bs] for y < rows, x < cols.
+// Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
 #include "jpegx_internal.h"
@@ -74,6 +79,40 @@ __global__ __launch_bounds__(256) void k_band_plane_n(const uint8_t *__restrict_
     out[(size_t)y * opitch + x] = (double)s / (double)(bs * bs);
 }
 
+// The way back, steps 2-0 inverted on clamped bytes: uint8 plane [.][pitch] (what jpegx_inverse_fused_n leaves with
+// JPEGX_F_CLAMP_U8) -> uint8 band [rows][opitch], out[y][x] = plane[y / bs][x / bs].  A lane owns SIXTEEN consecutive output
+// bytes of one output row (item = row * chunks + chunk; consecutive lanes, consecutive chunks): one division for y / bs, one
+// for x0 / bs, then a (quotient, remainder) pair stepped across the chunk -- a source byte is loaded when the pair enters it
+// and only for x < cols, so no read passes column (cols - 1) / bs or row (rows - 1) / bs.  One 16-byte store where the chunk is
+// inside the row and the address is 16-byte aligned, bytes one by one for x < cols otherwise.  items < 2^31 (rows * cols is).
+__global__ __launch_bounds__(256) void k_inflate_crop_u8(const uint8_t *__restrict__ plane, size_t pitch, int cols, unsigned bs, unsigned chunks,
+                                                         unsigned items, uint8_t *__restrict__ out, size_t opitch)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= items) return;
+    const unsigned y = i / chunks, x0 = (i - y * chunks) * 16u;
+    const uint8_t *src = plane + (size_t)(y / bs) * pitch;
+    unsigned q = x0 / bs, r = x0 - q * bs;
+    const int left = cols - (int)x0;                                       // >= 1: bytes of this chunk inside the row
+    unsigned v = 0, w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (k < left) {
+            if (k == 0 || r == 0) v = src[q];
+            w[k >> 2] |= v << (8 * (k & 3));
+            if (++r == bs) { r = 0; ++q; }
+        }
+    }
+    uint8_t *dst = out + (size_t)y * opitch + x0;
+    if (left >= 16 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < left) dst[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,6 +151,22 @@ int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitc
         hipLaunchKernelGGL(k_band_plane_n, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d_band, (size_t)pitch, rows, cols, bs,
                            (int)(((long long)rows + bs - 1) / bs), (int)(((long long)cols + bs - 1) / bs), W, items, d_out, (size_t)out_pitch);
     }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out, ptrdiff_t out_pitch,
+                          jpegx_stream_t stream)
+{
+    if (!d_plane || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (rows < 1 || cols < 1) return fail(JPEGX_E_INVALID, "inflate_crop_u8: rows and cols must be at least 1");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "inflate_crop_u8: block_size must be in 1..255");
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if (pitch < (ptrdiff_t)(((long long)cols + bs - 1) / bs) || out_pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    const unsigned chunks = ((unsigned)cols + 15u) / 16u;
+    const unsigned items = (unsigned)rows * chunks;                         // at most rows * cols: below 2^31
+    hipLaunchKernelGGL(k_inflate_crop_u8, dim3((items + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_plane, (size_t)pitch, cols, (unsigned)bs,
+                       chunks, items, d_out, (size_t)out_pitch);
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

@@ -18,6 +18,7 @@
 
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -887,6 +888,29 @@ int decompress_plane(Job &job, const uint8_t *h_bytes, size_t nbytes, int H, int
     });
     return rc ? rc : job.done();
 }
+
+// uint8 samples [rows][pitch] in staging memory -> the caller's int64 [rows][cols], on a few host threads
+void widen_u8_i64(const uint8_t *stage, ptrdiff_t pitch, int64_t *h_out, int rows, int cols)
+{
+    const int nthreads = host_threads("JPEGX_WIDEN_THREADS", 8, (size_t)rows * cols);      // A/B (8: 1.8-2.4 ms, 16: 1.7-2.6 ms per 4096^2 band: no difference)
+    // non-temporal stores: the array is written once, 8 bytes per sample, and is eight times the size of what is read --
+    // ordinary stores would first READ every line of it for ownership (twice the memory traffic)
+    auto work = [&](int y0, int y1) {
+        for (int y = y0; y < y1; ++y) {
+            const uint8_t *srow = stage + (size_t)y * pitch;
+            int64_t *drow = h_out + (size_t)y * cols;
+            for (int x = 0; x < cols; ++x) __builtin_nontemporal_store((int64_t)srow[x], drow + x);
+        }
+        __builtin_ia32_sfence();
+    };
+    if (nthreads == 1) {
+        work(0, rows);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nthreads; ++t) th.emplace_back(work, (int)((long long)rows * t / nthreads), (int)((long long)rows * (t + 1) / nthreads));
+        for (auto &t : th) t.join();
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -918,24 +942,7 @@ int jpegx_host_decompress_plane_i64(const uint8_t *h_bytes, size_t nbytes, int H
     BackgroundTouch touch(h_out, (size_t)rows * cols * sizeof(int64_t));   // 128 MiB for a 4096 x 4096 band, usually never touched before
     if ((rc = decompress_plane(job, h_bytes, nbytes, H, W, bs, mode, param, stage, pitch, false))) return rc;
     touch.wait();
-    const int nthreads = host_threads("JPEGX_WIDEN_THREADS", 8, (size_t)rows * cols);      // A/B (8: 1.8-2.4 ms, 16: 1.7-2.6 ms per 4096^2 band: no difference)
-    // non-temporal stores: the array is written once, 8 bytes per sample, and is eight times the size of what is read --
-    // ordinary stores would first READ every line of it for ownership (twice the memory traffic)
-    auto work = [&](int y0, int y1) {
-        for (int y = y0; y < y1; ++y) {
-            const uint8_t *srow = stage + (size_t)y * pitch;
-            int64_t *drow = h_out + (size_t)y * cols;
-            for (int x = 0; x < cols; ++x) __builtin_nontemporal_store((int64_t)srow[x], drow + x);
-        }
-        __builtin_ia32_sfence();
-    };
-    if (nthreads == 1) {
-        work(0, rows);
-    } else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthreads; ++t) th.emplace_back(work, (int)((long long)rows * t / nthreads), (int)((long long)rows * (t + 1) / nthreads));
-        for (auto &t : th) t.join();
-    }
+    widen_u8_i64(stage, pitch, h_out, rows, cols);
     return JPEGX_OK;
 }
 
@@ -1108,6 +1115,85 @@ int jpegx_host_decompress_plane_n(const uint8_t *h_bytes, size_t nbytes, int H, 
     HIP_TRY(hipMemcpy2DAsync(h_out, (size_t)out_pitch * esz, slot.d_out.p, row, row, (size_t)H, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return job.done();
+}
+
+// what both band entries check before a device is touched; H, W: the plane that leaves the inverse (jpegx_band_shape_n)
+static int check_decompress_band_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param,
+                                   const void *h_out, int *H, int *W)
+{
+    if (!h_bytes || !h_out) return fail(JPEGX_E_INVALID, "null host pointer");
+    int rc;
+    if ((rc = jpegx_band_shape_n(rows, cols, bs, N, H, W))) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if ((rc = check_quantiser_n(mode, param))) return rc;
+    return jpegx_internal_decode_check_n(nbytes, (long long)(*H / N) * (*W / N), N * N);
+}
+
+// The job of both band entries: jpegx_host_decompress_plane_n's launches with the clamp, then the geometry steps as one
+// scatter into slot.d_tmp, rows back to back, enqueued before the verdict is awaited; the rows x cols samples down to h_dst
+// ([rows][dst_pitch] bytes) once the stream is known to be good, the pages of touch_p (the int64 form's destination) touched
+// in the background while they travel.  Where the band is the plane's own rows (block_size 1 and
+// cols = W) no kernel runs and the copy reads the plane.  The device rows are cols bytes apart, so that a destination with
+// rows back to back -- every caller but one with a pitch of its own -- can come down as ONE contiguous copy (rows that start
+// off a 16-byte boundary cost the kernel its wide stores: 20 us instead of 9 us on a 2999 x 3998 band).
+static int decompress_band_n(Job &job, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int H, int W, int N, int mode,
+                             double param, uint8_t *h_dst, ptrdiff_t dst_pitch, void *touch_p = nullptr, size_t touch_n = 0)
+{
+    int rc;
+    if ((rc = job.streams(false)) || (rc = job.pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    hipStream_t st = job.pool->stream;
+    BandSlot &slot = job.pool->slot[0];
+    const long long nblocks = (long long)(H / N) * (W / N);
+    const bool scatter = bs > 1 || cols != W;
+    if ((rc = slot.d_out.ensure((size_t)H * W)) || (scatter && (rc = slot.d_tmp.ensure((size_t)rows * cols))) ||
+        (rc = enqueue_decode_n(job.pool, slot, h_bytes, nbytes, nblocks, N * N, st)) ||
+        (rc = jpegx_inverse_fused_n(static_cast<const int32_t *>(slot.d_zz.p), H, W, N, mode, param, JPEGX_F_CLAMP_U8, slot.d_out.p, W, st)) ||
+        (scatter && (rc = jpegx_inflate_crop_u8(static_cast<const uint8_t *>(slot.d_out.p), W, rows, cols, bs, static_cast<uint8_t *>(slot.d_tmp.p),
+                                                cols, st))) ||
+        (rc = decode_verdict_n(job.pool)))
+        return rc;
+    // only now, and only for the int64 form: a refused stream has left the caller's pages alone
+    std::unique_ptr<BackgroundTouch> touch(touch_n ? new BackgroundTouch(touch_p, touch_n) : nullptr);
+    const void *d_band = scatter ? slot.d_tmp.p : slot.d_out.p;
+    // Which call brings them down is measured (profiles/dctn_band_decode.json and the runs behind DESIGN.md 4.12): a 2-D copy of
+    // rows 3998 bytes wide takes 20 ms even with both pitches equal to the width, the contiguous copy of the same bytes
+    // 0.3 ms; at widths that are multiples of 8 the 2-D call is the faster one by 0.01-0.04 ms a call.
+    if (dst_pitch == (ptrdiff_t)cols && cols % 8 != 0) HIP_TRY(hipMemcpyAsync(h_dst, d_band, (size_t)rows * cols, hipMemcpyDeviceToHost, st));
+    else HIP_TRY(hipMemcpy2DAsync(h_dst, (size_t)dst_pitch, d_band, (size_t)cols, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return job.done();
+}
+
+// decompress_band for dct_size N (2..32) from the bytes to the band's uint8 samples as one pooled job (pipeline/__init__.py:79-88,
+// all nine steps inverted): jpegx_host_decompress_plane_n's launches, then DCTPadding.invert, SubSampling.invert and
+// Padding.invert as jpegx_inflate_crop_u8 (not launched where they change nothing: block_size 1 and cols a multiple of N).
+// h_out: [rows][out_pitch] bytes; a refused stream leaves it as it was.
+int jpegx_host_decompress_band_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param,
+                                 uint8_t *h_out, ptrdiff_t out_pitch)
+{
+    int H = 0, W = 0, rc;
+    if ((rc = check_decompress_band_n(h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, &H, &W))) return rc;
+    if (out_pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    Job job;
+    if ((rc = job.rc)) return rc;
+    return decompress_band_n(job, h_bytes, nbytes, rows, cols, bs, H, W, N, mode, param, h_out, out_pitch);
+}
+
+// The same, handing back what the reference's decompress_band returns: the [rows][cols] int64 band.  The bytes come down
+// into the pool's pinned staging span and are widened by a few host threads (widen_u8_i64), the destination's pages
+// touched while the samples travel, after the verdict: a refused stream leaves h_out as it was.
+int jpegx_host_decompress_band_i64_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param,
+                                     int64_t *h_out)
+{
+    int H = 0, W = 0, rc;
+    if ((rc = check_decompress_band_n(h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, &H, &W))) return rc;
+    Job job;                                               // held to the end: the staging span belongs to this job
+    if ((rc = job.rc) || (rc = job.pool->h_out.ensure((size_t)rows * cols))) return rc;
+    uint8_t *stage = static_cast<uint8_t *>(job.pool->h_out.p);
+    if ((rc = decompress_band_n(job, h_bytes, nbytes, rows, cols, bs, H, W, N, mode, param, stage, cols, h_out, (size_t)rows * cols * sizeof(int64_t))))
+        return rc;
+    widen_u8_i64(stage, cols, h_out, rows, cols);
+    return JPEGX_OK;
 }
 
 // used by host_roundtrip (jpegx_internal.h): the synchronous host-pointer conveniences borrow the pool's

@@ -117,3 +117,9 @@ JPEGX_ON(jpegx_band_plane_n, (int device, const uint8_t *d_band, int rows, int c
          (d_band, rows, cols, pitch, bs, N, d_out, out_pitch, stream))
 JPEGX_ON(jpegx_host_compress_begin_band_n, (int device, const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param, size_t *nbytes),
          (h_band, elem_size, rows, cols, pitch, bs, N, mode, param, nbytes))
+JPEGX_ON(jpegx_inflate_crop_u8, (int device, const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_plane, pitch, rows, cols, bs, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_host_decompress_band_n, (int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch),
+         (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, out_pitch))
+JPEGX_ON(jpegx_host_decompress_band_i64_n, (int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param, int64_t *h_out),
+         (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out))

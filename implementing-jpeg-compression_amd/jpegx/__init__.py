@@ -173,6 +173,9 @@ SIGNATURES = {
     "jpegx_band_shape_n": [_int, _int, _int, _int, _c.POINTER(_int), _c.POINTER(_int)],
     "jpegx_band_plane_n": [_vp, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
     "jpegx_host_compress_begin_band_n": [_vp, _int, _int, _int, _pd, _int, _int, _int, _dbl, _c.POINTER(_sz)],
+    "jpegx_inflate_crop_u8": [_vp, _pd, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_host_decompress_band_n": [_vp, _sz, _int, _int, _int, _int, _int, _dbl, _vp, _pd],
+    "jpegx_host_decompress_band_i64_n": [_vp, _sz, _int, _int, _int, _int, _int, _dbl, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -194,7 +197,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_inverse_fused_n", "jpegx_dct_f64_n", "jpegx_idct_f64_n", "jpegx_entropy_sizes_n", "jpegx_entropy_emit_n",
               "jpegx_host_compress_begin_n", "jpegx_entropy_decode_n", "jpegx_entropy_decode_status_n",
               "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n", "jpegx_band_shape_n", "jpegx_band_plane_n",
-              "jpegx_host_compress_begin_band_n"):
+              "jpegx_host_compress_begin_band_n", "jpegx_inflate_crop_u8", "jpegx_host_decompress_band_n",
+              "jpegx_host_decompress_band_i64_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -1210,6 +1214,55 @@ def decompress_plane_n(blob, height, width, n, mode="none", param=0.0, out="u8")
     check(lib().jpegx_host_decompress_plane_n(buf.ctypes.data if buf.size else None, buf.size, h, w, int(n), mode_of(mode), float(param),
                                               F_CLAMP_U8 if out == "u8" else 0, res.ctypes.data if res.size else None, w),
           "jpegx_host_decompress_plane_n")
+    return res
+
+
+def inflate_crop_u8(plane, bs, rows, cols):
+    """uint8 plane (the clamped output of inverse_fused_n, at least ceil(rows / bs) x ceil(cols / bs)) -> the uint8 band
+    (rows, cols): DCTPadding.invert, SubSampling.invert and Padding.invert for block_size bs as one launch
+    (jpegx_inflate_crop_u8), out[y][x] = plane[y // bs][x // bs]."""
+    a = plane if isinstance(plane, np.ndarray) else np.asarray(plane)
+    if a.ndim != 2 or a.size == 0 or a.dtype != np.uint8:
+        raise JpegxError("expected a non-empty 2-D uint8 plane, got %r of %s" % (a.shape, a.dtype))
+    a = np.ascontiguousarray(a)
+    rows, cols, bs = int(rows), int(cols), int(bs)
+    if rows < 1 or cols < 1:                        # the entry's refusals, before anything is allocated
+        raise JpegxError("inflate_crop_u8: rows and cols must be at least 1")
+    if not 1 <= bs <= 255:
+        raise JpegxError("inflate_crop_u8: block_size must be in 1..255")
+    if rows * cols > 2 ** 31 - 1:
+        raise JpegxError("inflate_crop_u8: more than 2^31 - 1 samples in one band")
+    if a.shape[0] < -(-rows // bs) or a.shape[1] < -(-cols // bs):
+        raise JpegxError("inflate_crop_u8: a %d x %d plane is smaller than the pooled band" % a.shape)
+    require_device()
+    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(rows * cols)
+    try:
+        din.upload(a)
+        check(lib().jpegx_inflate_crop_u8(din.ptr, a.shape[1], rows, cols, bs, dout.ptr, cols, None), "jpegx_inflate_crop_u8")
+        return dout.download((rows, cols), np.uint8)
+    finally:
+        din.free()
+        dout.free()
+
+
+def decompress_band_n(blob, rows, cols, bs, n, mode="none", param=0.0, out="u8"):
+    """All nine steps of decompress_band for dct_size n as one pooled device job (jpegx_host_decompress_band_n /
+    _band_i64_n): the band (rows, cols) at its configured size, uint8 for out 'u8' or -- what the reference's
+    decompress_band returns -- int64 for 'i64'; the plane of whole blocks never reaches the host.  JpegxError for a refused
+    stream."""
+    if out not in ("u8", "i64"):
+        raise JpegxError("decompress_band_n: out must be 'u8' or 'i64'")
+    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    rows, cols = int(rows), int(cols)
+    if rows * cols > 2 ** 31 - 1:                   # before NumPy is asked for it
+        raise JpegxError("decompress_band_n: more than 2^31 - 1 samples in one band")
+    res = np.empty((max(rows, 0), max(cols, 0)), dtype=np.uint8 if out == "u8" else np.int64)
+    args = (buf.ctypes.data if buf.size else None, buf.size, rows, cols, int(bs), int(n), mode_of(mode), float(param),
+            res.ctypes.data if res.size else None)
+    if out == "u8":
+        check(lib().jpegx_host_decompress_band_n(*args, cols), "jpegx_host_decompress_band_n")
+    else:
+        check(lib().jpegx_host_decompress_band_i64_n(*args), "jpegx_host_decompress_band_i64_n")
     return res
 
 

@@ -13,7 +13,8 @@ Any other dct_size 2..32 with transform 'DCT' takes the all-float64 kernels of c
 csrc/jpegx_entropy_n.hip; with ``DCTN_ENTROPY_DECODE_MIN_SAMPLES`` set, decompressing runs the entropy decoder on the
 device in front of the inverse kernel, csrc/jpegx_entropy_decode_n.hip; planes of at least
 ``DCTN_BAND_JOB_MIN_SAMPLES`` samples compress as one device job from the band's 8-bit samples, steps 0-3 included,
-csrc/jpegx_band_n.hip) when a
+csrc/jpegx_band_n.hip; with ``DCTN_BAND_DECODE_JOB_MIN_SAMPLES`` set, decompressing is one device job down to the band's
+samples, the geometry steps a scatter kernel of the same file) when a
 device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
 NumPy road runs, exactly as the reference does it.
 """
@@ -138,6 +139,19 @@ DCTN_ENTROPY_DECODE_MIN_SAMPLES = 262144
 # configuration slower than the road of before at or above it is therefore 2304; the constant stands at the next measured
 # size above the planes (3456 and 8960 samples) that tests/test_gpu_dct_sizes.py pins to jpegx.forward_fused_n.
 DCTN_BAND_JOB_MIN_SAMPLES = 16384
+
+# decompress_band / decompress_band_u8 for dct_size other than 8 as ONE device job from the bytes to the band's samples
+# (jpegx.decompress_band_n: the launches of jpegx.decompress_plane_n with the clamp, then DCTPadding.invert,
+# SubSampling.invert and Padding.invert as the scatter kernel of csrc/jpegx_band_n.hip, the int64 band widened natively):
+# planes of at least this many samples LEAVING THE INVERSE (H * W with both paddings, like the three constants above) take
+# it; None: the road is off and both entries finish in NumPy as before.  Measured (DESIGN.md 4.12,
+# profiles/dctn_band_decode.json): on a 3000 x 4000 band decompress_band takes 8.01-8.07 ms instead of 50.35-50.41 ms (block_size 1) and
+# 7.15 instead of 12.69 ms (README bs 5 N 24), decompress_band_u8 0.360 instead of 3.26 ms at bs 5 and the same 1.48 ms at block_size 1 (the same
+# launches and copy).  On the ladder of square planes, 262 144 .. 4 194 304 samples at N 4, 16 and 24, no configuration and no entry
+# was slower than the parent's road; planes of exactly 262 144 samples are pinned to jpegx.decompress_plane_n by
+# tests/test_gpu_dctn_roads.py and tests/test_gpu_entropy_decode_n.py, so the constant stands at the smallest measured size
+# above that with no miss at or above it.
+DCTN_BAND_DECODE_JOB_MIN_SAMPLES = 331776
 
 _device_seen = False
 
@@ -372,6 +386,33 @@ def _decode_job_n(blob, config, out):
         return None
 
 
+def _band_decode_job_n(blob, config, out):
+    """All nine steps inverted for dct_size N as one pooled device job (jpegx.decompress_band_n): the band at its configured
+    size, uint8 for out 'u8' or int64 for 'i64'; or None -- the road is switched off (DCTN_BAND_DECODE_JOB_MIN_SAMPLES) or
+    the plane is below it, _decode_job_n's other conditions do not hold (stock registry, a quantiser the kernels take, a
+    whole divisor, non-empty bytes, a usable device), block_size is no integer in 1..255, height or width no integer of at
+    least 1, the band holds more than 2^31 - 1 samples, or the device refused the stream: the caller's road of before
+    then names the fault with the reference's exceptions."""
+    args = _dctn_mode(config)
+    if DCTN_BAND_DECODE_JOB_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
+        return None
+    if not isinstance(blob, (bytes, bytearray)) or not len(blob):
+        return None
+    bs, n, rows, cols = config.block_size, config.dct_size, config.height, config.width
+    if not all(isinstance(v, (int, np.integer)) for v in (bs, rows, cols)) or not 1 <= bs <= 255 or rows < 1 or cols < 1 \
+            or rows * cols > 2 ** 31 - 1:
+        return None
+    pooled = [-(-v // bs) for v in (rows, cols)]                        # geometry.band_geometry's last two pairs
+    h, w = (-(-v // n) * n for v in pooled)
+    if h * w < DCTN_BAND_DECODE_JOB_MIN_SAMPLES or not dctn_on_device(config, h * w):
+        return None
+    import jpegx
+    try:
+        return jpegx.decompress_band_n(blob, int(rows), int(cols), int(bs), int(n), *args, out=out)
+    except jpegx.JpegxError:
+        return None
+
+
 def _accelerated(config):
     return config.transform == "DCT" and config.dct_size == 8 and config.quantization.gpu_mode() is not None
 
@@ -541,6 +582,9 @@ def decompress_band_u8(compression_result, config):
             except jpegx.JpegxError:
                 pass
     if not _accelerated(config) and _stock_registry():
+        band = _band_decode_job_n(a, config, "u8")
+        if band is not None:
+            return band                             # all nine steps inverted in one device job
         plane = _decode_job_n(a, config, "u8")
         zz = None if plane is not None else _decode_stream_n(a, config)
         todo = None if zz is None else _restored_stream_n(zz, _dctn_mode(config))
@@ -590,6 +634,9 @@ def decompress_band(compression_result, config):
                 return band
             todo = todo[2:]
         if not fused and _stock_registry():
+            band = _band_decode_job_n(a, config, "i64")
+            if band is not None:                    # all nine steps inverted in one device job: this is the band
+                return band if band.dtype == np.dtype(int) else band.astype(int)
             band = _decode_job_n(a, config, "i32")
             if band is not None:
                 band = band.astype(int)

@@ -430,6 +430,19 @@ int jpegx_band_shape_n(int rows, int cols, int bs, int N, int *H, int *W);
 int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out,
                        ptrdiff_t out_pitch, jpegx_stream_t stream);
 
+/* ---- steps 2-0 inverted for a dct_size-N band on the device: DCTPadding.invert (pipeline/dct_padding.py:11-21),
+ * SubSampling.invert (pipeline/subsampling.py:13-14, util.inflate) and Padding.invert (pipeline/padding.py:14-16) as one
+ * scatter ----------------------------------------------------------------------------------------------------------
+ * jpegx_inflate_crop_u8 (enqueue only): uint8 plane [.][pitch] -- the clamped output of jpegx_inverse_fused_n -> uint8 band
+ * [rows][out_pitch] (pitches in bytes), out[y][x] = plane[y / bs][x / bs] for y < rows, x < cols: rows x cols is the band's
+ * configured size.  The crop of the DCT padding is implicit (no index reaches pooled row ceil(rows / bs) or pooled column
+ * ceil(cols / bs)), so N is no argument; bs = 1 is a cropping copy.  Reads stay inside [ceil(rows / bs)] x [ceil(cols / bs)]
+ * of the plane, writes inside [rows] x [cols] of the output (pitch slack untouched).  rows, cols >= 1; bs in 1..255 (else
+ * JPEGX_E_UNSUPPORTED); rows * cols <= 2^31 - 1; pitch >= ceil(cols / bs); out_pitch >= cols (else JPEGX_E_INVALID).  One
+ * launch of any height.                                                                                             */
+int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
+                          ptrdiff_t out_pitch, jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -592,6 +605,21 @@ int jpegx_host_entropy_decode_n_gpu(const uint8_t *h_bytes, size_t nbytes, long 
  * written, the job context is given back.                                                                          */
 int jpegx_host_decompress_plane_n(const uint8_t *h_bytes, size_t nbytes, int H, int W, int N, int mode, double param,
                                   unsigned flags, void *h_out, ptrdiff_t out_pitch);
+/* decompress_band for dct_size N in 2..32 as one pooled job from the bytes to the BAND's samples (pipeline/__init__.py:79-88,
+ * all nine steps inverted): the launches of jpegx_host_decompress_plane_n with JPEGX_F_CLAMP_U8 (the clamp of
+ * pipeline/normalization.py:10-14), then -- bs > 1 or cols != W -- jpegx_inflate_crop_u8 (pipeline/dct_padding.py:11-21,
+ * pipeline/subsampling.py:13-14, pipeline/padding.py:14-16) enqueued before the verdict is awaited, and the rows x cols
+ * samples down in one copy (bs = 1 with cols = W: straight from the plane, no launch; the device band's rows are cols bytes
+ * apart, so the copy is a contiguous one unless out_pitch > cols).  rows x cols: the band's configured size; the
+ * plane's H, W are jpegx_band_shape_n's.  h_out: [rows][out_pitch] bytes, out_pitch >= cols; the _i64 form hands back
+ * what decompress_band returns, int64 [rows][cols] with rows back to back (staged in pinned memory and widened by a few
+ * host threads, like jpegx_host_decompress_plane_i64).  bs in 1..255 (else JPEGX_E_UNSUPPORTED), rows * cols <= 2^31 - 1,
+ * quantisers as for jpegx_host_inverse_fused_n; arguments are checked before any device is touched.  A stream that is
+ * not (H/N) * (W/N) well-formed blocks: JPEGX_E_INVALID, h_out is not written, the job context is given back.       */
+int jpegx_host_decompress_band_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode,
+                                 double param, uint8_t *h_out, ptrdiff_t out_pitch);
+int jpegx_host_decompress_band_i64_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode,
+                                     double param, int64_t *h_out);
 /* frees the pooled device / pinned buffers and streams of every job context of the current device (waits for jobs
  * of other threads to finish; JPEGX_E_INVALID while the calling thread itself holds a context) */
 int jpegx_host_pool_release(void);
@@ -691,6 +719,12 @@ int jpegx_band_plane_n_on(int device, const uint8_t *d_band, int rows, int cols,
 int jpegx_band_shape_n_on(int device, int rows, int cols, int bs, int N, int *H, int *W);
 int jpegx_host_compress_begin_band_n_on(int device, const void *h_band, int elem_size, int rows, int cols, ptrdiff_t pitch, int bs,
                                         int N, int mode, double param, size_t *nbytes);
+int jpegx_inflate_crop_u8_on(int device, const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
+                             ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_host_decompress_band_n_on(int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N,
+                                    int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch);
+int jpegx_host_decompress_band_i64_n_on(int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N,
+                                        int mode, double param, int64_t *h_out);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
