@@ -138,7 +138,7 @@ int zigzag_common(const void *d_in, int H, int W, ptrdiff_t pitch, int elem_size
 
 // np.dstack of Jpeg.decompress (pipeline/__init__.py:119-122) on the device: `nb` uint8 planes [rows][pitch] ->
 // pixel-interleaved [rows][cols][nb].  One thread = four pixels of one row: a dword from every plane, 4 * nb
-// bytes out (whole dwords when the packed rows keep them aligned).
+// bytes out (whole dwords when the packed base and rows keep them aligned, single bytes otherwise).
 struct InterleaveArgs { const unsigned char *plane[JPEGX_MAX_IMAGE_BANDS]; };
 
 __global__ __launch_bounds__(256) void k_interleave_u8(InterleaveArgs a, int nb, int rows, int cols, size_t pitch,
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_interleave_u8(InterleaveArgs a, int nb,
         w[k] = k < nb ? *reinterpret_cast<const unsigned *>(a.plane[k] + (size_t)y * pitch + x) : 0u;   // pitch is a multiple of 16
     unsigned char *o = out + (size_t)y * out_pitch + (size_t)x * nb;
     const int npx = min(4, cols - x);
-    if (nb == 3 && npx == 4 && (out_pitch & 3) == 0) {
+    if (nb == 3 && npx == 4 && (out_pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0) {
         const unsigned b0 = w[0], b1 = w[1], b2 = w[2];
         unsigned *o4 = reinterpret_cast<unsigned *>(o);
         o4[0] = (b0 & 0xFFu) | ((b1 & 0xFFu) << 8) | ((b2 & 0xFFu) << 16) | ((b0 & 0xFF00u) << 16);
@@ -202,7 +202,7 @@ int jpegx_deinterleave_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int nbands, i
 {
     if (!d_planes || !d_in) return fail(JPEGX_E_INVALID, "null device pointer");
     if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS || rows <= 0 || cols <= 0 || rows > 65535)
-        return fail(JPEGX_E_INVALID, "deinterleave: 1..JPEGX_MAX_IMAGE_BANDS planes, 1..65535 rows");
+        return fail(JPEGX_E_INVALID, "deinterleave: 1..JPEGX_MAX_IMAGE_BANDS planes, 1..65535 rows, cols >= 1");
     if ((pitch % 4) != 0 || pitch < ((cols + 3) & ~3) || in_pitch < (ptrdiff_t)cols * nbands)
         return fail(JPEGX_E_INVALID, "deinterleave: plane pitch must be a multiple of 4 covering the row rounded up to 4; packed pitch >= cols * nbands");
     DeinterleaveArgs a;
@@ -221,7 +221,7 @@ int jpegx_interleave_u8(const void *const *d_planes, int nbands, int rows, int c
 {
     if (!d_planes || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
     if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS || rows <= 0 || cols <= 0 || rows > 65535)
-        return fail(JPEGX_E_INVALID, "interleave: 1..JPEGX_MAX_IMAGE_BANDS planes, 1..65535 rows");
+        return fail(JPEGX_E_INVALID, "interleave: 1..JPEGX_MAX_IMAGE_BANDS planes, 1..65535 rows, cols >= 1");
     if ((pitch % 4) != 0 || pitch < ((cols + 3) & ~3) || out_pitch < (ptrdiff_t)cols * nbands)
         return fail(JPEGX_E_INVALID, "interleave: plane pitch must be a multiple of 4 covering the row rounded up to 4; packed pitch >= cols * nbands");
     InterleaveArgs a;

@@ -151,7 +151,9 @@ int jpegx_forward_fused_f64(const double *d_in, int H, int W, ptrdiff_t pitch, i
 
 /* SubSampling.execute for ANY block_size (pipeline/subsampling.py:9-11, np.mean of bs x bs tiles): d_in is
  * [H*bs][pitch] of uint8 (elem_size 1) or integer-valued fp32 (elem_size 4); d_out [H][out_pitch] float64:
- * the exact tile sum divided once, which is what np.mean returns for integer bands.             */
+ * the exact tile sum divided once, which is what np.mean returns for integer bands.  fp32 samples are integers in
+ * 0..255.  bs in 1..4096 (anything else: JPEGX_E_INVALID), H <= 65535 output rows in one launch (more:
+ * JPEGX_E_UNSUPPORTED); pitch >= W*bs and out_pitch >= W, in elements, otherwise free.          */
 int jpegx_mean_pool_f64(const void *d_in, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
                         double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
 
@@ -584,10 +586,17 @@ int jpegx_host_compress_image_ragged(const void *const *h_planes, int nbands, in
 int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch,
                                             int bs, int mode, double param, const void *prefix, size_t prefix_len,
                                             int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes);
-/* pixel-interleaved [rows][cols][nbands] (rows in_pitch bytes apart) -> device planes [rows][pitch] (uint8, pitch a multiple of 4) */
+/* The two entries between packed pixels and planes: nbands in 1..JPEGX_MAX_IMAGE_BANDS, rows in 1..65535, cols >= 1.
+ * d_planes is a HOST array of nbands device pointers, each 4-byte aligned; the planes' pitch is a multiple of 4 and at
+ * least cols rounded up to 4.  The packed pointer (d_in / d_out) needs NO alignment and its pitch is any number of bytes
+ * >= cols * nbands: whole dwords are moved where base and pitch keep them aligned, single bytes otherwise.
+ * pixel-interleaved [rows][cols][nbands] (rows in_pitch bytes apart) -> device planes [rows][pitch] (uint8, pitch a multiple of 4).
+ * Every plane row is written in whole dwords: when cols is no multiple of 4, the up to three bytes behind a row, up to
+ * the next multiple of 4, are overwritten with unspecified values; nothing from there to the pitch is touched. */
 int jpegx_deinterleave_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int nbands, int rows, int cols, void *const *d_planes,
                           ptrdiff_t pitch, jpegx_stream_t stream);
-/* device planes [rows][pitch] (uint8, pitch a multiple of 4) -> pixel-interleaved [rows][cols][nbands] */
+/* device planes [rows][pitch] (uint8, pitch a multiple of 4) -> pixel-interleaved [rows][cols][nbands]: exactly
+ * cols * nbands bytes of every packed row are written.  A plane row is read up to cols rounded up to 4. */
 int jpegx_interleave_u8(const void *const *d_planes, int nbands, int rows, int cols, ptrdiff_t pitch, uint8_t *d_out,
                         ptrdiff_t out_pitch, jpegx_stream_t stream);
 /* the entropy decoding alone on the device: bytes -> int16 [nblocks][64] (= jpegx_host_entropy_decode) */

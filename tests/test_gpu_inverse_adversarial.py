@@ -9,6 +9,7 @@ import adversarial_zz as az
 import emul_lib
 import oracle
 from codec_oracle import decompress_reference
+from fenced import device_inverse
 
 pytestmark = pytest.mark.gpu
 
@@ -22,31 +23,6 @@ I16 = (-32768, 32767)
 
 def stream(cls, shape, mode, param):
     return az.plane(az.make(cls, shape[0] * shape[1], mode, param), shape[0])
-
-
-def device_inverse(gpu, zz, mode, param, out, flags=0, inflate=None, pitch_extra=0):
-    """jpegx_inverse_fused (inflate None) or jpegx_inverse_fused_u8_inflated on device buffers, the output prefilled
-    with 0xA5; the bytes between the rows must still hold it.  pitch_extra: elements on top of the aligned row."""
-    dtype = np.dtype({"f32": np.float32, "i16": np.int16, "u8": np.uint8}[out])
-    esz, bs = dtype.itemsize, (inflate or 1)
-    h, w = zz.shape[0] * 8, zz.shape[1] * 8
-    pitch = (w * bs * esz + 15) // 16 * 16 // esz + pitch_extra
-    dzz, dout = gpu.DeviceBuffer(zz.nbytes), gpu.DeviceBuffer(h * bs * pitch * esz)
-    try:
-        dzz.upload(np.ascontiguousarray(zz, np.int16))
-        gpu.check(gpu.lib().jpegx_memset(dout.ptr, 0xA5, dout.nbytes, None))
-        if inflate is None:
-            gpu.inverse_fused_device(dzz.ptr, h, w, dout.ptr, mode, param, flags, out_type={"f32": gpu.OUT_F32, "i16": gpu.OUT_I16, "u8": gpu.OUT_U8}[out], out_pitch=pitch)
-        else:
-            gpu.check(gpu.lib().jpegx_inverse_fused_u8_inflated(dzz.ptr, h, w, gpu.mode_of(mode), float(param), flags, bs, dout.ptr, pitch, None),
-                      "jpegx_inverse_fused_u8_inflated")
-        gpu.check(gpu.lib().jpegx_device_synchronize())
-        res = dout.download((h * bs, pitch), dtype)
-    finally:
-        dzz.free()
-        dout.free()
-    assert np.all(res[:, w * bs:].view(np.uint8) == 0xA5), "bytes between the rows were written"
-    return res[:, :w * bs]
 
 
 def same(got, want, what):
