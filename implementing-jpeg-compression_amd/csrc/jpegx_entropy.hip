@@ -136,7 +136,8 @@ __global__ __launch_bounds__(64) void k_rle_sizes_half(const int16_t *__restrict
     unsigned sum = bytes;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-    if (lane == 0) W.wave_bytes[blockIdx.x] = sum | (__any(bad) ? 0x80000000u : 0u);
+    const bool anybad = __any(bad);                       // by the whole wave: inside the lane-0 branch the vote would see lane 0 alone
+    if (lane == 0) W.wave_bytes[blockIdx.x] = sum | (anybad ? 0x80000000u : 0u);
 }
 
 // Plane index of a batch (nplanes planes of nb blocks each, one stream): byte offset of every plane's first block b =
@@ -230,7 +231,8 @@ __global__ __launch_bounds__(1024) void k_scan_one_chunk(int nwaves, void *ws, i
         if (lane >= d) incl += u;
     }
     if (lane == 63) carry[wv] = incl;
-    if (lane == 0) bad_s[wv] = __any(bad) ? 1u : 0u;
+    const bool wavebad = __any(bad);                      // all 64 lanes vote: each holds four waves' totals
+    if (lane == 0) bad_s[wv] = wavebad ? 1u : 0u;
     __syncthreads();
     unsigned base = 0, anybad = 0;
 #pragma unroll

@@ -418,7 +418,8 @@ __device__ __forceinline__ void forward_strip_body(unsigned char *lds, int wg, c
         unsigned sum = bytes;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-        if (lane == 0) wave_bytes[wg] = sum | (__any(bad) ? 0x80000000u : 0u);
+        const bool anybad = __any(bad);                   // by the whole wave: inside the lane-0 branch the vote would see lane 0 alone
+        if (lane == 0) wave_bytes[wg] = sum | (anybad ? 0x80000000u : 0u);
     }
 
     // the strip is dead: reuse its first 8 KiB as the swizzled output tile
@@ -1207,7 +1208,8 @@ __global__ __launch_bounds__(64) JPEGX_U8_OCC void k_forward_fused_u8(const unsi
         unsigned sum = bytes;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-        if (lane == 0) wave_bytes[blockIdx.x] = sum | (__any(bad) ? 0x80000000u : 0u);
+        const bool anybad = __any(bad);                   // by the whole wave: inside the lane-0 branch the vote would see lane 0 alone
+        if (lane == 0) wave_bytes[blockIdx.x] = sum | (anybad ? 0x80000000u : 0u);
     }
     if (prm.tune & 4) {
         // A/B (JPEGX_F_TUNE_DIRECT_STORE): every lane stores its own 128 bytes, eight 16-byte pieces at a 128-byte
