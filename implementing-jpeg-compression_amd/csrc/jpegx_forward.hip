@@ -1366,6 +1366,18 @@ struct SizeViews {
     bool sized;     // out: the launched kernel wrote them (the whole-block strip tier; every other tier leaves them to k_rle_sizes_half)
 };
 
+// The LDS-staged pooled loader (forward_fused_body, STAGED != 0) addresses a wave's input as "first block + 32-bit byte
+// offset per lane".  A wave's 64 blocks reach at most ceil(64 / wb) block rows below its first one, each 8 * bs input rows
+// of `pitch` floats: with a narrow plane and a long pitch that offset no longer fits 32 bits and the DMA would read 4 GiB
+// short, from another row of the same buffer.  Such planes go through the per-lane loader (STAGED == 0, 64-bit addresses).
+bool pooled_offsets_exceed_32_bits(int H, int W, ptrdiff_t pitch, int bs)
+{
+    if (pitch >= ((ptrdiff_t)1 << 40)) return true;                // keeps the product below in 64 bits
+    const int wb = W / 8, hb = H / 8;
+    const long long rows = (64 + wb - 1) / wb < hb ? (64 + wb - 1) / wb : hb;
+    return rows * 8 * bs * (long long)pitch * 4 + (long long)W * bs * 4 >= (1LL << 32);
+}
+
 template <int BS, bool NT, int STAGED = 0>
 int launch_forward(const float *d_in, int H, int W, ptrdiff_t pitch, const QuantParams &qp, unsigned flags,
                    int16_t *d_out, hipStream_t st, SizeViews *sv = nullptr)
@@ -1466,8 +1478,9 @@ static int forward_f32_common(const float *d_in, int H, int W, ptrdiff_t pitch, 
     // Pooled input: staged through LDS by default (whole-line nontemporal DMA).  The per-lane
     // variant reads partial lines per instruction (16 B at a 32*bs-byte lane stride); nontemporal
     // loads then refetch every line and lose 30-60 % (profiles/r01_ab_pooled.txt), so that variant
-    // always uses the default cache policy.
-    if (bs > 1 && !(flags & JPEGX_F_TUNE_NO_STRIP)) {
+    // always uses the default cache policy.  It also serves the planes whose rows lie too far apart for the
+    // staged loader's 32-bit lane offsets.
+    if (bs > 1 && !(flags & JPEGX_F_TUNE_NO_STRIP) && !pooled_offsets_exceed_32_bits(H, W, pitch, bs)) {
         const bool nt = !(flags & JPEGX_F_TUNE_NO_NT);
         const int rpp = (flags & JPEGX_F_TUNE_POOL_ROWS_LO) ? 1 : ((flags & JPEGX_F_TUNE_POOL_ROWS_HI) ? 4 : 2);   // experiment: rows per phase
 #define JPEGX_LF(BSV, RPPV) (nt ? launch_forward<BSV, true, RPPV>(d_in, H, W, pitch, qp, flags, d_out, st) \
@@ -1521,13 +1534,21 @@ int jpegx_forward_fused_planes(const jpegx_plane_desc *planes, int nplanes, int 
     PlaneTable tab;
     memset(&tab, 0, sizeof(tab));
     long long wg = 0;
+    // pooled planes beyond the staged loader's 32-bit lane offsets (pooled_offsets_exceed_32_bits) stay out of the
+    // shared grid: each gets a launch of its own through the per-lane loader, on the same stream and in front of the
+    // shared grid -- such a call enqueues several kernels, and a failure of a later launch leaves the earlier ones queued
+    int far_planes[MAX_PLANES], nfar = 0, ntab = 0;
     for (int k = 0; k < nplanes; ++k) {
         const jpegx_plane_desc &d = planes[order[k]];
         rc = check_plane(d.d_in, d.d_out, d.H, d.W, d.pitch / d.bs, 1);
         if (rc) return rc;
         if (d.pitch < (ptrdiff_t)d.W * d.bs || (d.pitch % 4) != 0 || !aligned16(d.d_in) || !aligned16(d.d_out))
             return fail(JPEGX_E_INVALID, "forward_planes: pitch must be a multiple of 4 floats and >= W*bs; pointers 16-byte aligned");
-        PlaneArgs &a = tab.p[k];
+        if (d.bs > 1 && pooled_offsets_exceed_32_bits(d.H, d.W, d.pitch, d.bs)) {
+            far_planes[nfar++] = order[k];
+            continue;
+        }
+        PlaneArgs &a = tab.p[ntab++];
         a.in = d.d_in;
         a.out = d.d_out;
         a.pitch = (size_t)d.pitch;
@@ -1538,7 +1559,13 @@ int jpegx_forward_fused_planes(const jpegx_plane_desc *planes, int nplanes, int 
         wg += (a.nblk + 63) / 64;
         if (wg > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "forward_planes: more than 2^31 workgroups in one launch");
     }
-    tab.n = nplanes;
+    tab.n = ntab;
+    for (int k = 0; k < nfar; ++k) {
+        const jpegx_plane_desc &d = planes[far_planes[k]];
+        rc = forward_f32_common(d.d_in, d.H, d.W, d.pitch, d.bs, mode, param, flags, d.d_out, nullptr, stream);
+        if (rc) return rc;
+    }
+    if (ntab == 0) return JPEGX_OK;
     const bool pixel = (flags & JPEGX_F_PIXEL_INPUT) != 0 && max_abs_multiplier(qp) <= 2.0f;
     const bool dc_exact = pixel && is_pow2_float(qp.rq32[0]) && (qp.mode != JPEGX_Q_DIVIDE || (double)qp.rq32[0] * qp.param == 1.0);
     const bool nt = !(flags & JPEGX_F_TUNE_NO_NT);

@@ -139,7 +139,13 @@ int jpegx_forward_fused(const float *d_in, int H, int W, ptrdiff_t pitch, int mo
                         unsigned flags, int16_t *d_out, jpegx_stream_t stream);
 
 /* Same with the SubSampling mean-pool prologue fused (pipeline/subsampling.py:9-11): the
- * input plane is [H*bs][W*bs] and is averaged over bs x bs tiles (bs in {1,2,4}) on load.    */
+ * input plane is [H*bs][W*bs] and is averaged over bs x bs tiles (bs in {1,2,4}) on load.
+ * pitch (in floats, a multiple of 4, >= W*bs) is otherwise free: where 64 consecutive blocks
+ * span 2^32 bytes of input or more (narrow planes with a long pitch) the entry, and
+ * jpegx_forward_fused_planes for such a descriptor, uses the loader with 64-bit lane addresses
+ * instead of the LDS-staged one; the result is the same.  jpegx_forward_fused_planes gives
+ * every such descriptor a kernel launch of its own, in front of the shared grid and on the
+ * same stream: one call may then enqueue several kernels (graph capture, profiles).          */
 int jpegx_forward_fused_pooled(const float *d_in, int H, int W, ptrdiff_t pitch, int bs, int mode,
                                double param, unsigned flags, int16_t *d_out, jpegx_stream_t stream);
 
