@@ -15,6 +15,11 @@
 // And the way back for the clamped bytes of jpegx_inverse_fused_n as ONE scatter (jpegx_inflate_crop_u8): DCTPadding.invert
 // (pipeline/dct_padding.py:11-21, a crop), SubSampling.invert (pipeline/subsampling.py:13-14, util.inflate: every sample bs x bs
 // times) and Padding.invert (pipeline/padding.py:14-16, a crop): out[y][x] = plane[y / bs][x / bs] for y < rows, x < cols.
+//
+// Both once more for a whole pixel-interleaved picture (Jpeg.compress / Jpeg.decompress, pipeline/__init__.py:98-124):
+// jpegx_band_planes_packed_n reads [rows][cols][nbands] pixels and writes every band's plane in one launch -- plane k is what
+// jpegx_band_plane_n makes of pixels[:, :, k], no uint8 planes in between, every input byte read once; and
+// jpegx_inflate_crop_pack_u8 writes out[y][x * nbands + k] = plane k[y / bs][x / bs], the np.dstack included.
 // Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
@@ -113,6 +118,160 @@ __global__ __launch_bounds__(256) void k_inflate_crop_u8(const uint8_t *__restri
     }
 }
 
+// ---- the same two steps for a whole pixel-interleaved picture: every band in one launch ------------------------------
+// The planes of one picture, handed to the kernels by value (a host array of device pointers at the C ABI).
+struct PlanesF64 { double *p[JPEGX_MAX_IMAGE_BANDS]; };
+struct PlanesU8 { const uint8_t *p[JPEGX_MAX_IMAGE_BANDS]; };
+
+// block_size 1 from [rows][cols][NB] pixels: k_band_plane_n_bs1's lane -- FOUR consecutive pixels of one plane row -- for all NB
+// bands at once.  The quad's 4 * NB bytes are contiguous: NB dword loads where the four pixels are inside the picture's row
+// and their address is dword aligned, clamped byte loads otherwise; per plane two 16-byte stores where the quad is inside
+// the plane's row and the address is 16-byte aligned, doubles one by one otherwise.  Every input byte is read once.
+template <int NB>
+__global__ __launch_bounds__(256) void k_band_planes_packed_n_bs1(const uint8_t *__restrict__ px, size_t pitch, int rows, int cols, int W, int quads,
+                                                                  long long items, PlanesF64 out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int y = (int)(i / quads), x0 = (int)(i - (long long)y * quads) * 4;
+    const uint8_t *src = px + (size_t)min(y, rows - 1) * pitch;
+    unsigned v[NB][4];
+    const uint8_t *quad = src + (size_t)x0 * NB;
+    if (x0 + 4 <= cols && (reinterpret_cast<uintptr_t>(quad) & 3u) == 0) {
+        unsigned q[NB];
+#pragma unroll
+        for (int d = 0; d < NB; ++d) q[d] = reinterpret_cast<const unsigned *>(quad)[d];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int k = 0; k < NB; ++k) v[k][p] = (q[(p * NB + k) >> 2] >> (8 * ((p * NB + k) & 3))) & 0xFFu;
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const uint8_t *one = src + (size_t)min(x0 + p, cols - 1) * NB;
+#pragma unroll
+            for (int k = 0; k < NB; ++k) v[k][p] = one[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        double *dst = out.p[k] + (size_t)y * opitch + x0;
+        if (x0 + 4 <= W && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+            reinterpret_cast<double2 *>(dst)[0] = make_double2((double)v[k][0], (double)v[k][1]);
+            reinterpret_cast<double2 *>(dst)[1] = make_double2((double)v[k][2], (double)v[k][3]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (x0 + p < W) dst[p] = (double)v[k][p];
+        }
+    }
+}
+
+// Any block_size from [rows][cols][NB] pixels: k_band_plane_n's lane -- one pooled sample -- summing all NB bands in one walk
+// over its bs rows of bs * NB contiguous bytes; a wave reads 64 * bs * NB contiguous bytes of each of its bs input rows and
+// stores a run of 64 doubles per plane.  Both loops run bs times; every sum is below 2^24.
+template <int NB>
+__global__ __launch_bounds__(256) void k_band_planes_packed_n(const uint8_t *__restrict__ px, size_t pitch, int rows, int cols, int bs, int prows,
+                                                              int pcols, int W, long long items, PlanesF64 out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+    const int r0 = min(y, prows - 1) * bs, c0 = min(x, pcols - 1) * bs;      // r0 < rows, c0 < cols: the tile starts inside the picture
+    unsigned s[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) s[k] = 0;
+    const int rlast = rows - 1 - r0, clast = cols - 1 - c0;                // both >= 0; the clamps below never add past rows - 1, cols - 1
+    if (bs <= clast + 1) {                                                  // the tile's columns are all there: no clamp per pixel
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *p = px + (size_t)(r0 + min(u, rlast)) * pitch + (size_t)c0 * NB;
+            for (int w = 0; w < bs; ++w)
+#pragma unroll
+                for (int k = 0; k < NB; ++k) s[k] += p[w * NB + k];
+        }
+    } else {
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *p = px + (size_t)(r0 + min(u, rlast)) * pitch + (size_t)c0 * NB;
+            for (int w = 0; w < bs; ++w)
+#pragma unroll
+                for (int k = 0; k < NB; ++k) s[k] += p[min(w, clast) * NB + k];
+        }
+    }
+    const double area = (double)(bs * bs);
+#pragma unroll
+    for (int k = 0; k < NB; ++k) out.p[k][(size_t)y * opitch + x] = (double)s[k] / area;
+}
+
+// The way back for a whole picture: NB clamped uint8 planes [.][pitch] -> pixel-interleaved [rows][cols][NB] with rows opitch
+// bytes apart, out[y][x * NB + k] = plane k[y / bs][x / bs].  A lane owns PIX consecutive pixels of one output row -- the
+// fewest whose bytes are whole 16-byte units: 16, 8, 16, 4 pixels = 16, 16, 48, 16 bytes for 1, 2, 3, 4 bands -- so every
+// byte's band is known at compile time.  One division for y / bs, one for x0 / bs, then a (quotient, remainder) pair stepped
+// across the pixels: the NB source bytes are loaded when the pair enters a source column and only for x < cols, so no read
+// passes column (cols - 1) / bs or row (rows - 1) / bs of a plane.  16-byte stores where the lane's pixels are all inside the
+// row and the address is 16-byte aligned, bytes one by one for x < cols otherwise.  items < 2^31 (rows * cols is).
+template <int NB>
+__global__ __launch_bounds__(256) void k_inflate_crop_pack_u8(PlanesU8 in, size_t pitch, int cols, unsigned bs, unsigned chunks, unsigned items,
+                                                              uint8_t *__restrict__ out, size_t opitch)
+{
+    constexpr int UNIT = NB == 3 ? 48 : 16, PIX = UNIT / NB;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= items) return;
+    const unsigned y = i / chunks, x0 = (i - y * chunks) * (unsigned)PIX;
+    const size_t row = (size_t)(y / bs) * pitch;
+    unsigned q = x0 / bs, r = x0 - q * bs;
+    const int left = cols - (int)x0;                                       // >= 1: pixels of this lane inside the row
+    unsigned v[NB], w[UNIT / 4];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) v[k] = 0;
+#pragma unroll
+    for (int d = 0; d < UNIT / 4; ++d) w[d] = 0;
+#pragma unroll
+    for (int p = 0; p < PIX; ++p) {
+        if (p < left) {
+            if (p == 0 || r == 0) {
+#pragma unroll
+                for (int k = 0; k < NB; ++k) v[k] = in.p[k][row + q];
+            }
+#pragma unroll
+            for (int k = 0; k < NB; ++k) w[(p * NB + k) >> 2] |= v[k] << (8 * ((p * NB + k) & 3));
+            if (++r == bs) { r = 0; ++q; }
+        }
+    }
+    uint8_t *dst = out + (size_t)y * opitch + (size_t)x0 * NB;
+    if (left >= PIX && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+#pragma unroll
+        for (int d = 0; d < UNIT / 16; ++d) reinterpret_cast<uint4 *>(dst)[d] = make_uint4(w[4 * d], w[4 * d + 1], w[4 * d + 2], w[4 * d + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < UNIT; ++j)
+            if (j / NB < left) dst[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+    }
+}
+
+template <int NB>
+void launch_band_planes_packed_n(const uint8_t *px, size_t pitch, int rows, int cols, int bs, int H, int W, const PlanesF64 &out, size_t opitch, hipStream_t st)
+{
+    if (bs == 1) {
+        const int quads = (W + 3) / 4;
+        const long long items = (long long)H * quads;                      // below 2^31: H * W is
+        hipLaunchKernelGGL(k_band_planes_packed_n_bs1<NB>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, px, pitch, rows, cols, W, quads, items,
+                           out, opitch);
+    } else {
+        const long long items = (long long)H * W;
+        hipLaunchKernelGGL(k_band_planes_packed_n<NB>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, px, pitch, rows, cols, bs,
+                           (int)(((long long)rows + bs - 1) / bs), (int)(((long long)cols + bs - 1) / bs), W, items, out, opitch);
+    }
+}
+
+template <int NB>
+void launch_inflate_crop_pack_u8(const PlanesU8 &in, size_t pitch, int rows, int cols, int bs, uint8_t *out, size_t opitch, hipStream_t st)
+{
+    constexpr unsigned PIX = (NB == 3 ? 48 : 16) / NB;
+    const unsigned chunks = ((unsigned)cols + PIX - 1u) / PIX;
+    const unsigned items = (unsigned)rows * chunks;                         // at most rows * cols: below 2^31
+    hipLaunchKernelGGL(k_inflate_crop_pack_u8<NB>, dim3((items + 255u) / 256u), dim3(256), 0, st, in, pitch, cols, (unsigned)bs, chunks, items, out, opitch);
+}
+
 }  // namespace
 
 extern "C" {
@@ -167,6 +326,58 @@ int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int
     const unsigned items = (unsigned)rows * chunks;                         // at most rows * cols: below 2^31
     hipLaunchKernelGGL(k_inflate_crop_u8, dim3((items + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_plane, (size_t)pitch, cols, (unsigned)bs,
                        chunks, items, d_out, (size_t)out_pitch);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_band_planes_packed_n(const uint8_t *d_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *const *d_planes,
+                               ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_pixels || !d_planes) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) return fail(JPEGX_E_INVALID, "band_planes_packed_n takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    int H = 0, W = 0;
+    const int rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W);
+    if (rc) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if (pitch < (ptrdiff_t)cols * nbands || out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    PlanesF64 out = {};
+    for (int k = 0; k < nbands; ++k) {
+        if (!d_planes[k]) return fail(JPEGX_E_INVALID, "null device pointer");
+        if (reinterpret_cast<uintptr_t>(d_planes[k]) % 8) return fail(JPEGX_E_INVALID, "band_planes_packed_n: misaligned output pointer");
+        out.p[k] = d_planes[k];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    switch (nbands) {
+    case 1: launch_band_planes_packed_n<1>(d_pixels, (size_t)pitch, rows, cols, bs, H, W, out, (size_t)out_pitch, st); break;
+    case 2: launch_band_planes_packed_n<2>(d_pixels, (size_t)pitch, rows, cols, bs, H, W, out, (size_t)out_pitch, st); break;
+    case 3: launch_band_planes_packed_n<3>(d_pixels, (size_t)pitch, rows, cols, bs, H, W, out, (size_t)out_pitch, st); break;
+    default: launch_band_planes_packed_n<4>(d_pixels, (size_t)pitch, rows, cols, bs, H, W, out, (size_t)out_pitch, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_inflate_crop_pack_u8(const uint8_t *const *d_planes, int nbands, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
+                               ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_planes || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) return fail(JPEGX_E_INVALID, "inflate_crop_pack_u8 takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    if (rows < 1 || cols < 1) return fail(JPEGX_E_INVALID, "inflate_crop_pack_u8: rows and cols must be at least 1");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "inflate_crop_pack_u8: block_size must be in 1..255");
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if (pitch < (ptrdiff_t)(((long long)cols + bs - 1) / bs) || out_pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    PlanesU8 in = {};
+    for (int k = 0; k < nbands; ++k) {
+        if (!d_planes[k]) return fail(JPEGX_E_INVALID, "null device pointer");
+        in.p[k] = d_planes[k];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    switch (nbands) {
+    case 1: launch_inflate_crop_pack_u8<1>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
+    case 2: launch_inflate_crop_pack_u8<2>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
+    case 3: launch_inflate_crop_pack_u8<3>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
+    default: launch_inflate_crop_pack_u8<4>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
+    }
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

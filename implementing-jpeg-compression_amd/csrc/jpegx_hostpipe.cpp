@@ -474,23 +474,104 @@ int check_quantiser_n(int mode, double param)
 // way there on `st`): jpegx_forward_fused_n, the sizes, the head read back, the verdict, the emitter; the job stays open.
 // The emitter is enqueued once the size is known: a block of N * N coefficients has no small worst case to size the
 // destination by beforehand.
+// The two halves of that tail, shared with the picture job (jpegx_host_compress_image_packed_n), which runs them per band.
+// Up to the size: the forward kernel on the float64 plane [H][W], the sizes, the workspace's head on its way to `head`.
+int enqueue_sizes_n(BandSlot &slot, const double *d_plane, int H, int W, int N, int mode, double param, hipStream_t st, unsigned long long *head)
+{
+    const long long nblocks = (long long)(H / N) * (W / N);
+    int rc;
+    if ((rc = slot.d_zz.ensure((size_t)H * W * 4)) || (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, N * N)))) return rc;
+    if ((rc = jpegx_forward_fused_n(d_plane, H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
+        (rc = jpegx_entropy_sizes_n(static_cast<const int32_t *>(slot.d_zz.p), nblocks, N * N, slot.d_ws.p, st)))
+        return rc;
+    return enqueue_head(head, slot, st);
+}
+
+// With the size known: the destination grown to it, the emitter behind the sizes on the same stream.
+int enqueue_emit_n(BandSlot &slot, int H, int W, int N, unsigned long long total, hipStream_t st)
+{
+    int rc;
+    if ((rc = slot.d_out.ensure((size_t)total + 64))) return rc;
+    return jpegx_entropy_emit_n(static_cast<const int32_t *>(slot.d_zz.p), (long long)(H / N) * (W / N), N * N, slot.d_ws.p,
+                                static_cast<uint8_t *>(slot.d_out.p), st);
+}
+
 int begin_tail_n(Job &job, BandSlot &slot, const double *d_plane, int H, int W, int N, int mode, double param, hipStream_t st,
                  unsigned long long *head, size_t *nbytes)
 {
-    const long long nblocks = (long long)(H / N) * (W / N);
-    const int len = N * N;
     unsigned long long total = 0;
     int rc;
-    if ((rc = slot.d_zz.ensure((size_t)H * W * 4)) || (rc = slot.d_ws.ensure(jpegx_entropy_workspace_bytes_n(nblocks, len)))) return rc;
-    const int32_t *d_zz = static_cast<const int32_t *>(slot.d_zz.p);
-    if ((rc = jpegx_forward_fused_n(d_plane, H, W, W, N, mode, param, static_cast<int32_t *>(slot.d_zz.p), st)) ||
-        (rc = jpegx_entropy_sizes_n(d_zz, nblocks, len, slot.d_ws.p, st)) || (rc = enqueue_head(head, slot, st)))
-        return rc;
+    if ((rc = enqueue_sizes_n(slot, d_plane, H, W, N, mode, param, st, head))) return rc;
     if (hipStreamSynchronize(st) != hipSuccess) return fail(JPEGX_E_HIP, "device to host copy failed");
-    if ((rc = head_verdict(head, &total)) || (rc = slot.d_out.ensure((size_t)total + 64)) ||
-        (rc = jpegx_entropy_emit_n(d_zz, nblocks, len, slot.d_ws.p, static_cast<uint8_t *>(slot.d_out.p), st)))
-        return rc;
+    if ((rc = head_verdict(head, &total)) || (rc = enqueue_emit_n(slot, H, W, N, total, st))) return rc;
     return begin_epilogue(job, total, nbytes);
+}
+
+// [rows][cols][nbands] pixels, rows `pitch` bytes apart, up into pool->d_packed with rows back to back, on aux[0]
+int upload_packed(DevicePool *pool, const uint8_t *h_packed, int rows, size_t row_bytes, ptrdiff_t pitch)
+{
+    int rc;
+    if ((rc = pool->d_packed.ensure((size_t)rows * row_bytes))) return rc;
+    hipError_t e = ((size_t)pitch == row_bytes)
+        ? hipMemcpyAsync(pool->d_packed.p, h_packed, (size_t)rows * row_bytes, hipMemcpyHostToDevice, pool->aux[0])
+        : hipMemcpy2DAsync(pool->d_packed.p, row_bytes, h_packed, (size_t)pitch, row_bytes, (size_t)rows, hipMemcpyHostToDevice, pool->aux[0]);
+    if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
+    return JPEGX_OK;
+}
+
+// aux[1] goes on behind what aux[0] holds so far (the planes made from the packed pixels)
+int planes_ready(DevicePool *pool)
+{
+    if (hipEventRecord(pool->ev_x, pool->aux[0]) != hipSuccess || hipStreamWaitEvent(pool->aux[1], pool->ev_x, 0) != hipSuccess)
+        return fail(JPEGX_E_HIP, "event between the image job's streams failed");
+    return JPEGX_OK;
+}
+
+// What the picture jobs share from the point where band k's 16-byte head is on its way to heads[2 * k] on aux[k & 1] with
+// ev[k] behind it: per band the wait, the verdict, the 32-bit length check and `emit(k, total)` (the emitter on the band's
+// stream, its destination slot[k].d_out); then ONE call of `alloc` for [prefix][u32 LE length][band 0]..., its pages
+// touched, and every band copied from the device to its place.
+template <typename Emit>
+int finish_container(Job &job, int nbands, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user,
+                     size_t *nbytes, const Trace &tr, Emit &&emit)
+{
+    DevicePool *pool = job.pool;
+    const unsigned long long *heads = static_cast<const unsigned long long *>(pool->h_head.p);
+    size_t total_all = prefix_len;
+    size_t offset[MAX_BANDS] = {};
+    int rc;
+    for (int k = 0; k < nbands; ++k) {
+        if (hipEventSynchronize(pool->ev[k]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
+        unsigned long long total = 0;
+        if ((rc = head_verdict(heads + 2 * k, &total))) return rc;
+        if (length_prefixes && total > 0xFFFFFFFFull) return fail(JPEGX_E_INVALID, "a band's stream does not fit the container's 32-bit length field");
+        nbytes[k] = (size_t)total;
+        offset[k] = total_all + (length_prefixes ? 4 : 0);
+        total_all = offset[k] + (size_t)total;
+        // the emit kernel needs only the device-side offsets: enqueue it now, the destination comes later
+        if ((rc = emit(k, total))) return rc;
+    }
+    tr.mark("sizes known, emits enqueued");
+    uint8_t *dst = static_cast<uint8_t *>(alloc(user, total_all));
+    if (!dst && total_all) return fail(JPEGX_E_INVALID, "the allocator returned no destination");
+    tr.mark("destination allocated");
+    prefault(dst, total_all);
+    tr.mark("destination touched");
+    if (prefix_len) memcpy(dst, prefix, prefix_len);
+    for (int k = 0; k < nbands; ++k) {
+        if (length_prefixes) {
+            const uint32_t n32 = (uint32_t)nbytes[k];
+            const uint8_t le[4] = {(uint8_t)n32, (uint8_t)(n32 >> 8), (uint8_t)(n32 >> 16), (uint8_t)(n32 >> 24)};   // struct '<L'
+            memcpy(dst + offset[k] - 4, le, 4);
+        }
+        if (nbytes[k] && hipMemcpyAsync(dst + offset[k], pool->slot[k].d_out.p, nbytes[k], hipMemcpyDeviceToHost, pool->aux[k & 1]) != hipSuccess)
+            return fail(JPEGX_E_HIP, "device to host copy failed");
+        tr.mark("download enqueued", k);
+    }
+    HIP_TRY(hipStreamSynchronize(pool->aux[0]));
+    HIP_TRY(hipStreamSynchronize(pool->aux[1]));
+    tr.mark("compress_image: done");
+    return job.done();
 }
 
 }  // namespace
@@ -682,19 +763,14 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
         // band): one upload, the planes made on the device (rows of the padded pitch; enqueue_front fills the margins),
         // then the bands as below without their own uploads
         const size_t row_bytes = (size_t)cols * nbands;
-        if ((rc = pool->d_packed.ensure((size_t)rows * row_bytes))) return rc;
         void *planes[MAX_BANDS] = {};
         for (int k = 0; k < nbands; ++k) {
             if ((rc = pool->slot[k].d_in.ensure(in_bytes))) return rc;
             planes[k] = pool->slot[k].d_in.p;
         }
-        hipError_t e = ((size_t)pitch == row_bytes)
-            ? hipMemcpyAsync(pool->d_packed.p, h_packed, (size_t)rows * row_bytes, hipMemcpyHostToDevice, pool->aux[0])
-            : hipMemcpy2DAsync(pool->d_packed.p, row_bytes, h_packed, (size_t)pitch, row_bytes, (size_t)rows, hipMemcpyHostToDevice, pool->aux[0]);
-        if (e != hipSuccess) return fail(JPEGX_E_HIP, "host to device copy failed");
+        if ((rc = upload_packed(pool, h_packed, rows, row_bytes, pitch))) return rc;
         if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, (ptrdiff_t)W * bs, pool->aux[0]))) return rc;
-        if (hipEventRecord(pool->ev_x, pool->aux[0]) != hipSuccess || hipStreamWaitEvent(pool->aux[1], pool->ev_x, 0) != hipSuccess)
-            return fail(JPEGX_E_HIP, "event between the image job's streams failed");
+        if ((rc = planes_ready(pool))) return rc;
         tr.mark("pixels enqueued");
     }
     for (int k = 0; k < nbands; ++k) {
@@ -706,43 +782,11 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
         if (rc) return rc;
         tr.mark("front enqueued", k);
     }
-    size_t total_all = prefix_len;
-    size_t offset[MAX_BANDS] = {};
-    for (int k = 0; k < nbands; ++k) {
-        if (hipEventSynchronize(pool->ev[k]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
-        unsigned long long total = 0;
-        if ((rc = head_verdict(heads + 2 * k, &total))) return rc;
-        if (length_prefixes && total > 0xFFFFFFFFull) return fail(JPEGX_E_INVALID, "a band's stream does not fit the container's 32-bit length field");
-        nbytes[k] = (size_t)total;
-        offset[k] = total_all + (length_prefixes ? 4 : 0);
-        total_all = offset[k] + (size_t)total;
-        // the emit kernel needs only the device-side offsets: enqueue it now, the destination comes later
+    return finish_container(job, nbands, prefix, prefix_len, length_prefixes, alloc, user, nbytes, tr, [&](int k, unsigned long long total) -> int {
         BandSlot &slot = pool->slot[k];
-        if ((rc = slot.d_out.ensure(total ? (size_t)total : 1)) ||
-            (rc = enqueue_emit(slot, nblocks, static_cast<uint8_t *>(slot.d_out.p), pool->aux[k & 1])))
-            return rc;
-    }
-    tr.mark("sizes known, emits enqueued");
-    uint8_t *dst = static_cast<uint8_t *>(alloc(user, total_all));
-    if (!dst && total_all) return fail(JPEGX_E_INVALID, "the allocator returned no destination");
-    tr.mark("destination allocated");
-    prefault(dst, total_all);
-    tr.mark("destination touched");
-    if (prefix_len) memcpy(dst, prefix, prefix_len);
-    for (int k = 0; k < nbands; ++k) {
-        if (length_prefixes) {
-            const uint32_t n32 = (uint32_t)nbytes[k];
-            const uint8_t le[4] = {(uint8_t)n32, (uint8_t)(n32 >> 8), (uint8_t)(n32 >> 16), (uint8_t)(n32 >> 24)};   // struct '<L'
-            memcpy(dst + offset[k] - 4, le, 4);
-        }
-        if (nbytes[k] && hipMemcpyAsync(dst + offset[k], pool->slot[k].d_out.p, nbytes[k], hipMemcpyDeviceToHost, pool->aux[k & 1]) != hipSuccess)
-            return fail(JPEGX_E_HIP, "device to host copy failed");
-        tr.mark("download enqueued", k);
-    }
-    HIP_TRY(hipStreamSynchronize(pool->aux[0]));
-    HIP_TRY(hipStreamSynchronize(pool->aux[1]));
-    tr.mark("compress_image: done");
-    return job.done();
+        const int r = slot.d_out.ensure(total ? (size_t)total : 1);
+        return r ? r : enqueue_emit(slot, nblocks, static_cast<uint8_t *>(slot.d_out.p), pool->aux[k & 1]);
+    });
 }
 
 int jpegx_host_compress_image(const void *const *h_planes, int nbands, int elem_size, int H, int W, ptrdiff_t pitch, int bs,
@@ -787,6 +831,50 @@ int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands,
     if (rc) return rc;
     return compress_image_impl(nullptr, h_pixels, nbands, 1, H, W, rows, cols, true, pitch, bs, mode, param, prefix, prefix_len,
                                length_prefixes, alloc, user, nbytes);
+}
+
+// The picture job for dct_size N (2..32): Jpeg.compress (pipeline/__init__.py:98-110 + file_format.generate_data,
+// file_format.py:86-93) from [rows][cols][nbands] pixels.  One upload into d_packed and ONE launch for steps 0-3 of every
+// band (jpegx_band_planes_packed_n into the slots' d_tmp) on aux[0]; then band k on aux[k & 1] with slot[k] -- forward
+// kernel, sizes, head, ev[k] -- and, once a band's size is known, its emitter; the container as compress_image_impl writes it.
+int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                                       double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc,
+                                       void *user, size_t *nbytes)
+{
+    if (!h_pixels || !alloc || !nbytes || (prefix_len && !prefix)) return fail(JPEGX_E_INVALID, "null pointer");
+    if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "compress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    int H = 0, W = 0, rc;
+    if ((rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W))) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "packed pitch smaller than a row of pixels");
+    if ((rc = check_quantiser_n(mode, param))) return rc;
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(true))) return rc;
+    DevicePool *pool = job.pool;
+    if ((rc = pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    unsigned long long *heads = static_cast<unsigned long long *>(pool->h_head.p);
+    const Trace tr;
+    tr.mark("compress_image_n: pool ready");
+    double *planes[MAX_BANDS] = {};
+    for (int k = 0; k < nbands; ++k) {
+        if ((rc = pool->slot[k].d_tmp.ensure((size_t)H * W * 8))) return rc;
+        planes[k] = static_cast<double *>(pool->slot[k].d_tmp.p);
+    }
+    const size_t row_bytes = (size_t)cols * nbands;
+    if ((rc = upload_packed(pool, h_pixels, rows, row_bytes, pitch)) ||
+        (rc = jpegx_band_planes_packed_n(static_cast<const uint8_t *>(pool->d_packed.p), nbands, rows, cols, (ptrdiff_t)row_bytes, bs, N, planes, W, pool->aux[0])) ||
+        (rc = planes_ready(pool)))
+        return rc;
+    tr.mark("pixels enqueued");
+    for (int k = 0; k < nbands; ++k) {
+        hipStream_t st = pool->aux[k & 1];
+        if ((rc = enqueue_sizes_n(pool->slot[k], planes[k], H, W, N, mode, param, st, heads + 2 * k))) return rc;
+        if (hipEventRecord(pool->ev[k], st) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventRecord failed");
+        tr.mark("front enqueued", k);
+    }
+    return finish_container(job, nbands, prefix, prefix_len, length_prefixes, alloc, user, nbytes, tr, [&](int k, unsigned long long total) -> int {
+        return enqueue_emit_n(pool->slot[k], H, W, N, total, pool->aux[k & 1]);
+    });
 }
 
 }  // extern "C"
@@ -1050,24 +1138,27 @@ int jpegx_host_entropy_decode_gpu(const uint8_t *h_bytes, size_t nbytes, long lo
 }
 
 // The run-time block length decoder (csrc/jpegx_entropy_decode_n.hip) on the job's stream: the stream in slot.d_in -> int32
-// coefficients in slot.d_zz, the workspace's head on its way to pinned memory, ev[0] recorded behind it.
-static int enqueue_decode_n(DevicePool *pool, BandSlot &slot, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int len, hipStream_t st)
+// coefficients in slot.d_zz, the workspace's head on its way to place `k` of the pinned heads, ev[k] recorded behind it
+// (k = 0 for the jobs of one band; the picture job's band index).
+static int enqueue_decode_n(DevicePool *pool, BandSlot &slot, const uint8_t *h_bytes, size_t nbytes, long long nblocks, int len, hipStream_t st,
+                            int k = 0)
 {
     int rc;
     if ((rc = slot.d_ws.ensure(jpegx_entropy_decode_workspace_bytes_n(nbytes, nblocks, len))) || (rc = slot.d_zz.ensure((size_t)nblocks * len * 4)) ||
         (rc = upload_stream(slot, h_bytes, nbytes, st)) ||
         (rc = jpegx_entropy_decode_n(static_cast<const uint8_t *>(slot.d_in.p), nbytes, nblocks, len, slot.d_ws.p, static_cast<int32_t *>(slot.d_zz.p), st)))
         return rc;
-    if (hipMemcpyAsync(pool->h_head.p, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(pool->ev[0], st) != hipSuccess)
+    if (hipMemcpyAsync(static_cast<uint8_t *>(pool->h_head.p) + 16 * k, slot.d_ws.p, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipEventRecord(pool->ev[k], st) != hipSuccess)
         return fail(JPEGX_E_HIP, "device to host copy failed");
     return JPEGX_OK;
 }
 
-// waits for ev[0]: JPEGX_OK or the decoder's refusal
-static int decode_verdict_n(DevicePool *pool)
+// waits for ev[k]: JPEGX_OK or the decoder's refusal of band k
+static int decode_verdict_n(DevicePool *pool, int k = 0)
 {
-    if (hipEventSynchronize(pool->ev[0]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
-    return jpegx_internal_decode_verdict_n(static_cast<const unsigned *>(pool->h_head.p)[1]);
+    if (hipEventSynchronize(pool->ev[k]) != hipSuccess) return fail(JPEGX_E_HIP, "hipEventSynchronize failed");
+    return jpegx_internal_decode_verdict_n(static_cast<const unsigned *>(pool->h_head.p)[4 * k + 1]);
 }
 
 // bytes -> int32 [nblocks][block_len] on the device, host arrays in and out (what jpegx_host_entropy_decode_n does on the CPU)
@@ -1129,6 +1220,17 @@ static int check_decompress_band_n(const uint8_t *h_bytes, size_t nbytes, int ro
     return jpegx_internal_decode_check_n(nbytes, (long long)(*H / N) * (*W / N), N * N);
 }
 
+// `rows` device rows of `width` bytes, back to back, down to [rows][dst_pitch] on the host.  Which call brings them down is
+// measured (profiles/dctn_band_decode.json and the runs behind DESIGN.md 4.12): a 2-D copy of rows 3998 bytes wide takes 20 ms
+// even with both pitches equal to the width, the contiguous copy of the same bytes 0.3 ms; at widths that are multiples of 8
+// the 2-D call is the faster one by 0.01-0.04 ms a call.
+static int copy_rows_down(uint8_t *h_dst, ptrdiff_t dst_pitch, const void *d_src, size_t width, int rows, hipStream_t st)
+{
+    if ((size_t)dst_pitch == width && width % 8 != 0) HIP_TRY(hipMemcpyAsync(h_dst, d_src, (size_t)rows * width, hipMemcpyDeviceToHost, st));
+    else HIP_TRY(hipMemcpy2DAsync(h_dst, (size_t)dst_pitch, d_src, width, width, (size_t)rows, hipMemcpyDeviceToHost, st));
+    return JPEGX_OK;
+}
+
 // The job of both band entries: jpegx_host_decompress_plane_n's launches with the clamp, then the geometry steps as one
 // scatter into slot.d_tmp, rows back to back, enqueued before the verdict is awaited; the rows x cols samples down to h_dst
 // ([rows][dst_pitch] bytes) once the stream is known to be good, the pages of touch_p (the int64 form's destination) touched
@@ -1155,11 +1257,7 @@ static int decompress_band_n(Job &job, const uint8_t *h_bytes, size_t nbytes, in
     // only now, and only for the int64 form: a refused stream has left the caller's pages alone
     std::unique_ptr<BackgroundTouch> touch(touch_n ? new BackgroundTouch(touch_p, touch_n) : nullptr);
     const void *d_band = scatter ? slot.d_tmp.p : slot.d_out.p;
-    // Which call brings them down is measured (profiles/dctn_band_decode.json and the runs behind DESIGN.md 4.12): a 2-D copy of
-    // rows 3998 bytes wide takes 20 ms even with both pitches equal to the width, the contiguous copy of the same bytes
-    // 0.3 ms; at widths that are multiples of 8 the 2-D call is the faster one by 0.01-0.04 ms a call.
-    if (dst_pitch == (ptrdiff_t)cols && cols % 8 != 0) HIP_TRY(hipMemcpyAsync(h_dst, d_band, (size_t)rows * cols, hipMemcpyDeviceToHost, st));
-    else HIP_TRY(hipMemcpy2DAsync(h_dst, (size_t)dst_pitch, d_band, (size_t)cols, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, st));
+    if ((rc = copy_rows_down(h_dst, dst_pitch, d_band, (size_t)cols, rows, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return job.done();
 }
@@ -1194,6 +1292,65 @@ int jpegx_host_decompress_band_i64_n(const uint8_t *h_bytes, size_t nbytes, int 
         return rc;
     widen_u8_i64(stage, cols, h_out, rows, cols);
     return JPEGX_OK;
+}
+
+// Jpeg.decompress for dct_size N (2..32) as one pooled job (pipeline/__init__.py:112-124: three decompress_band calls and the
+// np.dstack): band k on aux[k & 1] with slot[k] -- bytes up, jpegx_entropy_decode_n, its head and ev[k], jpegx_inverse_fused_n
+// with the clamp -- then either ONE scatter of all bands into d_packed on aux[0] behind both streams (interleave:
+// jpegx_inflate_crop_pack_u8, [rows][cols][nbands]) or per band jpegx_inflate_crop_u8 where it changes anything (planes stacked,
+// [band][rows][out_pitch]).  Nothing is copied to h_out before EVERY band's verdict is good: a refused band leaves it as it was.
+int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode,
+                                  double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave)
+{
+    if (!h_bytes || !nbytes || !h_out) return fail(JPEGX_E_INVALID, "null pointer");
+    if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "decompress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    int H = 0, W = 0, rc;
+    for (int k = 0; k < nbands; ++k)
+        if ((rc = check_decompress_band_n(h_bytes[k], nbytes[k], rows, cols, bs, N, mode, param, h_out, &H, &W))) return rc;
+    const size_t row_bytes = (size_t)cols * (interleave ? nbands : 1);
+    if (out_pitch < (ptrdiff_t)row_bytes) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    Job job;
+    if ((rc = job.rc) || (rc = job.streams(true)) || (rc = job.pool->h_head.ensure(16 * MAX_BANDS))) return rc;
+    DevicePool *pool = job.pool;
+    const long long nblocks = (long long)(H / N) * (W / N);
+    const bool scatter = !interleave && (bs > 1 || cols != W);             // planes stacked: the band's own kernel, or nothing
+    if (interleave && (rc = pool->d_packed.ensure((size_t)rows * row_bytes))) return rc;
+    const uint8_t *planes[MAX_BANDS] = {};
+    for (int k = 0; k < nbands; ++k) {
+        hipStream_t st = pool->aux[k & 1];
+        BandSlot &slot = pool->slot[k];
+        if ((rc = slot.d_out.ensure((size_t)H * W)) || (scatter && (rc = slot.d_tmp.ensure((size_t)rows * cols))) ||
+            (rc = enqueue_decode_n(pool, slot, h_bytes[k], nbytes[k], nblocks, N * N, st, k)) ||
+            (rc = jpegx_inverse_fused_n(static_cast<const int32_t *>(slot.d_zz.p), H, W, N, mode, param, JPEGX_F_CLAMP_U8, slot.d_out.p, W, st)) ||
+            (scatter && (rc = jpegx_inflate_crop_u8(static_cast<const uint8_t *>(slot.d_out.p), W, rows, cols, bs, static_cast<uint8_t *>(slot.d_tmp.p),
+                                                    cols, st))))
+            return rc;
+        planes[k] = static_cast<const uint8_t *>(slot.d_out.p);
+    }
+    if (interleave) {
+        // the packing scatter runs on aux[0] behind every band: aux[1]'s bands are all in front of ev_x
+        if (nbands > 1 && (hipEventRecord(pool->ev_x, pool->aux[1]) != hipSuccess || hipStreamWaitEvent(pool->aux[0], pool->ev_x, 0) != hipSuccess))
+            return fail(JPEGX_E_HIP, "event between the image job's streams failed");
+        if ((rc = jpegx_inflate_crop_pack_u8(planes, nbands, W, rows, cols, bs, static_cast<uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, pool->aux[0])))
+            return rc;
+    }
+    for (int k = 0; k < nbands; ++k)
+        if ((rc = decode_verdict_n(pool, k))) return rc;                    // the Job waits for what is still running
+    // Every stream is good.  A destination whose rows lie back to back is usually a fresh array: its pages are touched here,
+    // while the device finishes (every byte of it is one the copies overwrite; a wider out_pitch leaves the caller's bytes
+    // between the rows alone, so nothing is touched then).
+    if ((size_t)out_pitch == row_bytes) prefault(h_out, (size_t)rows * row_bytes * (interleave ? 1 : nbands));
+    if (interleave) {
+        if ((rc = copy_rows_down(h_out, out_pitch, pool->d_packed.p, row_bytes, rows, pool->aux[0]))) return rc;
+    } else {
+        for (int k = 0; k < nbands; ++k)
+            if ((rc = copy_rows_down(h_out + (size_t)k * rows * out_pitch, out_pitch, scatter ? pool->slot[k].d_tmp.p : pool->slot[k].d_out.p, (size_t)cols, rows,
+                                     pool->aux[k & 1])))
+                return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(pool->aux[0]));
+    HIP_TRY(hipStreamSynchronize(pool->aux[1]));
+    return job.done();
 }
 
 // used by host_roundtrip (jpegx_internal.h): the synchronous host-pointer conveniences borrow the pool's

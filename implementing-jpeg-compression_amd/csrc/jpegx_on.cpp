@@ -123,3 +123,11 @@ JPEGX_ON(jpegx_host_decompress_band_n, (int device, const uint8_t *h_bytes, size
          (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, out_pitch))
 JPEGX_ON(jpegx_host_decompress_band_i64_n, (int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode, double param, int64_t *h_out),
          (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out))
+JPEGX_ON(jpegx_band_planes_packed_n, (int device, const uint8_t *d_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *const *d_planes, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_pixels, nbands, rows, cols, pitch, bs, N, d_planes, out_pitch, stream))
+JPEGX_ON(jpegx_inflate_crop_pack_u8, (int device, const uint8_t *const *d_planes, int nbands, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_planes, nbands, pitch, rows, cols, bs, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_host_compress_image_packed_n, (int device, const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
+         (h_pixels, nbands, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
+JPEGX_ON(jpegx_host_decompress_image_n, (int device, const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave),
+         (h_bytes, nbytes, nbands, rows, cols, bs, N, mode, param, h_out, out_pitch, interleave))

@@ -176,6 +176,10 @@ SIGNATURES = {
     "jpegx_inflate_crop_u8": [_vp, _pd, _int, _int, _int, _vp, _pd, _vp],
     "jpegx_host_decompress_band_n": [_vp, _sz, _int, _int, _int, _int, _int, _dbl, _vp, _pd],
     "jpegx_host_decompress_band_i64_n": [_vp, _sz, _int, _int, _int, _int, _int, _dbl, _vp],
+    "jpegx_band_planes_packed_n": [_vp, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_inflate_crop_pack_u8": [_vp, _int, _pd, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_host_compress_image_packed_n": [_vp, _int, _int, _int, _pd, _int, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
+    "jpegx_host_decompress_image_n": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _int, _int, _dbl, _vp, _pd, _int],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -198,7 +202,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_compress_begin_n", "jpegx_entropy_decode_n", "jpegx_entropy_decode_status_n",
               "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n", "jpegx_band_shape_n", "jpegx_band_plane_n",
               "jpegx_host_compress_begin_band_n", "jpegx_inflate_crop_u8", "jpegx_host_decompress_band_n",
-              "jpegx_host_decompress_band_i64_n"):
+              "jpegx_host_decompress_band_i64_n", "jpegx_band_planes_packed_n", "jpegx_inflate_crop_pack_u8",
+              "jpegx_host_compress_image_packed_n", "jpegx_host_decompress_image_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -1264,6 +1269,131 @@ def decompress_band_n(blob, rows, cols, bs, n, mode="none", param=0.0, out="u8")
     else:
         check(lib().jpegx_host_decompress_band_i64_n(*args), "jpegx_host_decompress_band_i64_n")
     return res
+
+
+def _pixels_u8(pixels):
+    a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if a.ndim != 3 or a.size == 0 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4:
+        raise JpegxError("expected non-empty uint8 pixels (rows, cols, 1..4), got %r of %s" % (a.shape, a.dtype))
+    return np.ascontiguousarray(a)
+
+
+def band_planes_packed_n(pixels, bs, n, pitch=None, out_pitch=None):
+    """uint8 pixels (rows, cols, nb) -> the list of nb float64 planes (H, W) that leave step 3, every band in one launch
+    (jpegx_band_planes_packed_n): plane k is bit for bit band_plane_n(pixels[:, :, k], bs, n).  ``pitch``: bytes between the
+    rows of the packed picture on the device (default cols * nb); ``out_pitch``: doubles between the planes' rows (default W)."""
+    a = _pixels_u8(pixels)
+    rows, cols, nb = a.shape
+    h, w = band_shape_n(rows, cols, bs, n)
+    pitch = cols * nb if pitch is None else int(pitch)
+    opitch = w if out_pitch is None else int(out_pitch)
+    if pitch < cols * nb or opitch < w:
+        raise JpegxError("band_planes_packed_n: pitch smaller than the row")
+    require_device()
+    din = DeviceBuffer(rows * pitch)
+    douts = [DeviceBuffer(h * opitch * 8) for _ in range(nb)]
+    try:
+        staged = np.zeros((rows, pitch), np.uint8)
+        staged[:, :cols * nb] = a.reshape(rows, cols * nb)
+        din.upload(staged)
+        ptrs = (ctypes.c_void_p * nb)(*[d.ptr for d in douts])
+        check(lib().jpegx_band_planes_packed_n(din.ptr, nb, rows, cols, pitch, int(bs), int(n), ptrs, opitch, None), "jpegx_band_planes_packed_n")
+        return [np.ascontiguousarray(d.download((h, opitch), np.float64)[:, :w]) for d in douts]
+    finally:
+        din.free()
+        for d in douts:
+            d.free()
+
+
+def inflate_crop_pack_u8(planes, rows, cols, bs, pitch=None, out_pitch=None):
+    """nb uint8 planes of one shape (the clamped outputs of inverse_fused_n, at least ceil(rows / bs) x ceil(cols / bs)) ->
+    uint8 pixels (rows, cols, nb): DCTPadding.invert, SubSampling.invert, Padding.invert and the np.dstack of Jpeg.decompress
+    as one launch (jpegx_inflate_crop_pack_u8), out[y][x][k] = planes[k][y // bs][x // bs].  ``pitch``: bytes between the
+    planes' rows on the device (default their width); ``out_pitch``: bytes between the picture's rows (default cols * nb)."""
+    arrs = [np.ascontiguousarray(p) for p in planes]
+    nb = len(arrs)
+    if not 1 <= nb <= 4 or any(a.ndim != 2 or a.size == 0 or a.dtype != np.uint8 or a.shape != arrs[0].shape for a in arrs):
+        raise JpegxError("expected 1..4 non-empty 2-D uint8 planes of one shape")
+    rows, cols, bs = int(rows), int(cols), int(bs)
+    if rows < 1 or cols < 1:                        # the entry's refusals, before anything is allocated
+        raise JpegxError("inflate_crop_pack_u8: rows and cols must be at least 1")
+    if not 1 <= bs <= 255:
+        raise JpegxError("inflate_crop_pack_u8: block_size must be in 1..255")
+    if rows * cols > 2 ** 31 - 1:
+        raise JpegxError("inflate_crop_pack_u8: more than 2^31 - 1 samples in one band")
+    ph, pw = arrs[0].shape
+    if ph < -(-rows // bs) or pw < -(-cols // bs):
+        raise JpegxError("inflate_crop_pack_u8: a %d x %d plane is smaller than the pooled band" % (ph, pw))
+    pitch = pw if pitch is None else int(pitch)
+    opitch = cols * nb if out_pitch is None else int(out_pitch)
+    if pitch < pw or opitch < cols * nb:
+        raise JpegxError("inflate_crop_pack_u8: pitch smaller than the row")
+    require_device()
+    dins, dout = [DeviceBuffer(ph * pitch) for _ in range(nb)], DeviceBuffer(rows * opitch)
+    try:
+        for d, a in zip(dins, arrs):
+            staged = np.zeros((ph, pitch), np.uint8)
+            staged[:, :pw] = a
+            d.upload(staged)
+        ptrs = (ctypes.c_void_p * nb)(*[d.ptr for d in dins])
+        check(lib().jpegx_inflate_crop_pack_u8(ptrs, nb, pitch, rows, cols, bs, dout.ptr, opitch, None), "jpegx_inflate_crop_pack_u8")
+        return np.ascontiguousarray(dout.download((rows, opitch), np.uint8)[:, :cols * nb]).reshape(rows, cols, nb)
+    finally:
+        dout.free()
+        for d in dins:
+            d.free()
+
+
+def compress_image_packed_n(pixels, bs, n, mode="none", param=0.0, prefix=None):
+    """compress_image_packed for dct_size n: ``pixels`` is the C-contiguous (rows, cols, 1..4) uint8 array np.asarray(image)
+    gives; all bands through ONE pooled device job (jpegx_host_compress_image_packed_n).  With ``prefix`` (the container
+    header) the finished file -- prefix, then every band behind its '<L' byte count; without it the list of the bands' byte
+    strings, each what compress_band_n returns for its band.  None when the pixels are not in that layout; JpegxError
+    naming BadRleCodeError for an amplitude beyond 15 bits."""
+    a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if a.ndim != 3 or a.size == 0 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
+        return None
+    rows, cols, nb = a.shape
+    box = []
+
+    def alloc(_user, nbytes):
+        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)       # uninitialised bytes, filled by the device copies
+        box.append(blob)
+        return _pyapi.PyBytes_AsString(blob)
+    cb = ALLOC_FN(alloc)
+    sizes = (ctypes.c_size_t * nb)()
+    head = bytes(prefix) if prefix is not None else b""
+    check(lib().jpegx_host_compress_image_packed_n(a.ctypes.data, nb, rows, cols, cols * nb, int(bs), int(n), mode_of(mode), float(param),
+                                                   head, len(head), 1 if prefix is not None else 0, cb, None, sizes),
+          "jpegx_host_compress_image_packed_n")
+    whole = box[0]
+    if prefix is not None:
+        return whole
+    out, at = [], 0
+    for size in sizes:
+        out.append(whole[at:at + size])
+        at += size
+    return out
+
+
+def decompress_image_n(blobs, rows, cols, bs, n, mode="none", param=0.0, interleave=True):
+    """All bands of one picture back at dct_size n in ONE pooled device job (jpegx_host_decompress_image_n): uint8
+    (rows, cols, nbands) when ``interleave`` (what PIL's Image.fromarray takes), else (nbands, rows, cols); every band is
+    what decompress_band_n returns for its bytes.  JpegxError when the device refuses a band's stream."""
+    bufs = [np.frombuffer(b if isinstance(b, bytes) else bytes(b), dtype=np.uint8) for b in blobs]
+    nb = len(bufs)
+    rows, cols = int(rows), int(cols)
+    if not 1 <= nb <= 4:
+        raise JpegxError("decompress_image_n takes 1..4 bands")
+    if rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:      # before NumPy is asked for it
+        raise JpegxError("decompress_image_n: rows and cols must be at least 1 and hold at most 2^31 - 1 samples")
+    ptrs = (ctypes.c_void_p * nb)(*[b.ctypes.data if b.size else None for b in bufs])
+    sizes = (ctypes.c_size_t * nb)(*[b.size for b in bufs])
+    out = np.empty((rows, cols, nb) if interleave else (nb, rows, cols), dtype=np.uint8)
+    check(lib().jpegx_host_decompress_image_n(ptrs, sizes, nb, rows, cols, int(bs), int(n), mode_of(mode), float(param), out.ctypes.data,
+                                              cols * nb if interleave else cols, 1 if interleave else 0),
+          "jpegx_host_decompress_image_n")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -14,7 +14,8 @@ csrc/jpegx_entropy_n.hip; with ``DCTN_ENTROPY_DECODE_MIN_SAMPLES`` set, decompre
 device in front of the inverse kernel, csrc/jpegx_entropy_decode_n.hip; planes of at least
 ``DCTN_BAND_JOB_MIN_SAMPLES`` samples compress as one device job from the band's 8-bit samples, steps 0-3 included,
 csrc/jpegx_band_n.hip; with ``DCTN_BAND_DECODE_JOB_MIN_SAMPLES`` set, decompressing is one device job down to the band's
-samples, the geometry steps a scatter kernel of the same file) when a
+samples, the geometry steps a scatter kernel of the same file; Jpeg.compress / Jpeg.decompress on three-band 8-bit pictures
+are one device job each from ``DCTN_IMAGE_JOB_MIN_SAMPLES`` / ``DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES`` samples per plane on) when a
 device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; otherwise -- unlike dct_size 8 -- the host
 NumPy road runs, exactly as the reference does it.
 """
@@ -152,6 +153,32 @@ DCTN_BAND_JOB_MIN_SAMPLES = 16384
 # tests/test_gpu_dctn_roads.py and tests/test_gpu_entropy_decode_n.py, so the constant stands at the smallest measured size
 # above that with no miss at or above it.
 DCTN_BAND_DECODE_JOB_MIN_SAMPLES = 331776
+
+# Jpeg.compress for dct_size other than 8 as ONE device job from the picture's interleaved pixels to the finished container
+# (jpegx.compress_image_packed_n: one upload, steps 0-3 of all three bands as one launch of csrc/jpegx_band_n.hip, the bands'
+# forward and entropy stages on two streams, one allocation for the container): pictures whose planes hold at least this
+# many samples ENTERING STEP 4 (H * W of one band, like the four constants above) take it; None: the road is off and
+# Jpeg.compress splits the image and calls compress_band three times as before.  Independent of DCTN_BAND_JOB_MIN_SAMPLES.
+# Measured (profiles/dctn_image.json): on a 3000 x 4000 x 3 picture Jpeg.compress takes 19.1 instead of
+# 27.1 ms (README bs 5 N 24), 23.5 instead of 59.9 ms (bs 1 N 4) and 21.4 instead of 67.8 ms (bs 1 N 16); on the ladder of
+# square pictures, 16 384 .. 1 048 576 samples per plane at N 4, 16 and 24, no configuration was slower than the parent's
+# road (1.15-6.0x faster).  The smallest measured size with no miss at or above it is the smallest measured, 16 384, which is
+# also the lowest this constant may take: the pictures of 36 x 48 and 80 x 112 planes that tests/test_gpu_dctn_roads.py and
+# tests/test_gpu_dct_sizes.py pin to jpegx.forward_fused_n lie below it.
+DCTN_IMAGE_JOB_MIN_SAMPLES = 16384
+
+# Jpeg.decompress for dct_size other than 8 as ONE device job from the container's three streams to the interleaved pixels
+# (jpegx.decompress_image_n: the bands' decoders and inverse kernels on two streams, then DCTPadding.invert,
+# SubSampling.invert, Padding.invert and the np.dstack as one scatter of csrc/jpegx_band_n.hip and one copy down): planes of
+# at least this many samples LEAVING THE INVERSE take it; None: the road is off and Jpeg.decompress calls decompress_band_u8
+# three times and stacks on the host as before.  Independent of DCTN_BAND_DECODE_JOB_MIN_SAMPLES.
+# Measured (profiles/dctn_image.json): on a 3000 x 4000 x 3 picture Jpeg.decompress takes 18.2 instead of
+# 30.9 ms (README bs 5 N 24), 33.7 instead of 46.9 ms (bs 1 N 4) and 34.8 instead of 39.6 ms (bs 1 N 16).  On the ladder the
+# job lost once, at 16 384 samples and N 16 (0.424 against 0.373 ms: three device decoders cost more there than the host
+# parser), and was 1.2-6.2x faster at every configuration from 36 864 samples on: the smallest measured size with no miss
+# at or above it.  Never to stand below 16 384 (the 36 x 48 planes that tests/test_gpu_band_decode_job_n.py pins to
+# jpegx.decompress_band_n with that gate at 0).
+DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES = 36864
 
 _device_seen = False
 
@@ -681,6 +708,9 @@ class Jpeg:
         whole = _compress_pixels(image, self.config)         # the picture's pixels as ONE array, the bands made on the device
         if whole is not None:
             return whole
+        whole = _compress_pixels_n(image, self.config)       # the same for dct_size other than 8
+        if whole is not None:
+            return whole
         arrays = [band_to_array(band) for band in image.split()]
         whole = _compress_image(arrays, self.config)        # the finished container, written band by band from the device
         if whole is not None:
@@ -694,6 +724,8 @@ class Jpeg:
         config, data = file_format.read_data(bytestream)
         size = (config.height, config.width)
         packed = _decompress_image((data.y, data.cb, data.cr), config)
+        if packed is None:
+            packed = _decompress_image_n((data.y, data.cb, data.cr), config)      # dct_size other than 8: one device job
         if packed is None:
             packed = np.dstack([decompress_band_u8(b, config).reshape(size) for b in (data.y, data.cb, data.cr)])
         return Image.fromarray(packed, mode="YCbCr")
@@ -762,5 +794,80 @@ def _decompress_image(blobs, config):
     hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
     try:
         return jpegx.decompress_image_native(blobs, hb * 8, wb * 8, config.block_size, mode, param, config.height, config.width)
+    except jpegx.JpegxError:
+        return None
+
+
+def _plane_samples_n(rows, cols, bs, n):
+    """H * W of the plane of whole n x n blocks for a rows x cols band (geometry.band_geometry's last pair)."""
+    h, w = (-(-(-(-v // bs)) // n) * n for v in (rows, cols))
+    return h * w
+
+
+def _compress_pixels_n(image, config):
+    """_compress_pixels for dct_size other than 8: the picture's interleaved pixels through ONE device job that writes the
+    finished container (jpegx.compress_image_packed_n) -- no `image.split()`, one upload instead of three, one wait per band
+    for its size instead of a whole job -- with the bytes of file_format.generate_data over three compress_band calls.  None:
+    the road is switched off (DCTN_IMAGE_JOB_MIN_SAMPLES) or the plane is below it; _compress_pixels' conditions do not
+    hold (three bands, mode YCbCr / RGB / LAB / HSV, the image of the configured size, uint8 pixels) or _band_job_n's do not
+    (stock registry, a quantiser the kernels take, a usable device, no coefficient of an 8-bit band that could reach
+    2^31 - 1, no DCTN_ENTROPY_MIN_SAMPLES admitting the plane); or the job met an amplitude beyond 15 bits -- the per-band
+    road then raises the reference's BadRleCodeError with its own text."""
+    args = _dctn_mode(config)
+    if DCTN_IMAGE_JOB_MIN_SAMPLES is None or args is None or not _stock_registry() or not _dctn_config(config):
+        return None
+    bs, n = config.block_size, config.dct_size
+    try:
+        bands = image.getbands()
+    except Exception:
+        return None
+    if not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 255 or len(bands) != 3 or image.mode not in ("YCbCr", "RGB", "LAB", "HSV"):
+        return None
+    if (config.height, config.width) != (image.height, image.width) or image.height < 1 or image.width < 1:
+        return None
+    samples = _plane_samples_n(image.height, image.width, bs, n)
+    if samples > 2 ** 31 - 1 or image.height * image.width > 2 ** 31 - 1 or samples < DCTN_IMAGE_JOB_MIN_SAMPLES \
+            or not dctn_on_device(config, samples):
+        return None
+    if DCTN_ENTROPY_MIN_SAMPLES is not None and samples >= DCTN_ENTROPY_MIN_SAMPLES:
+        return None
+    mode, param = args
+    if not 255.0 * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0) <= 2.0 ** 31 - 1.0:      # _band_job_n's guard
+        return None
+    pixels = np.asarray(image)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3:
+        return None
+    import jpegx
+    try:
+        return jpegx.compress_image_packed_n(np.ascontiguousarray(pixels), int(bs), int(n), mode, param,
+                                             prefix=file_format.create_header(config))
+    except jpegx.JpegxError as exc:
+        if "BadRleCodeError" not in str(exc):
+            raise
+        return None
+
+
+def _decompress_image_n(blobs, config):
+    """_decompress_image for dct_size other than 8: three decompress_band_u8 calls and the np.dstack as ONE device job
+    (jpegx.decompress_image_n); (height, width, 3) uint8.  None: the road is switched off
+    (DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES) or the plane is below it, _band_decode_job_n's conditions do not hold (stock
+    registry, a quantiser the kernels take, a whole divisor, non-empty bytes, block_size an integer in 1..255, height and
+    width integers of at least 1 holding at most 2^31 - 1 samples, a usable device), or the device refused a band's
+    stream: the per-band road then names the fault."""
+    args = _dctn_mode(config) if _dctn_config(config) else None
+    if DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
+        return None
+    if any(not isinstance(b, (bytes, bytearray)) or not len(b) for b in blobs):
+        return None
+    bs, n, rows, cols = config.block_size, config.dct_size, config.height, config.width
+    if not all(isinstance(v, (int, np.integer)) for v in (bs, rows, cols)) or not 1 <= bs <= 255 or rows < 1 or cols < 1 \
+            or rows * cols > 2 ** 31 - 1:
+        return None
+    samples = _plane_samples_n(rows, cols, bs, n)
+    if samples < DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES or not dctn_on_device(config, samples):
+        return None
+    import jpegx
+    try:
+        return jpegx.decompress_image_n(blobs, int(rows), int(cols), int(bs), int(n), *args)
     except jpegx.JpegxError:
         return None

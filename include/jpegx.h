@@ -451,6 +451,26 @@ int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitc
 int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
                           ptrdiff_t out_pitch, jpegx_stream_t stream);
 
+/* ---- both for a whole pixel-interleaved picture, every band in one launch (Jpeg.compress / Jpeg.decompress,
+ * pipeline/__init__.py:98-124: `image.split()` and three bands one after another, np.dstack on the way back) ----------
+ * jpegx_band_planes_packed_n (enqueue only): [rows][cols][nbands] uint8 pixels, rows `pitch` BYTES apart (np.asarray(image))
+ * -> nbands float64 planes [H][out_pitch]; d_planes is a HOST array of nbands device pointers, each 8-byte aligned.  Plane k
+ * is bit for bit what jpegx_band_plane_n makes of pixels[:, :, k] (pipeline/padding.py:8-12, subsampling.py:9-11,
+ * dct_padding.py:8-9, normalization.py:7-8): the same clamped gather, the exact integer tile sum, one division -- without
+ * uint8 planes in between, every input byte read once for all bands.  The packed pointer needs NO alignment; pitch is any
+ * value >= cols * nbands.  Reads stay inside [rows] x [cols * nbands] bytes, writes inside [H] x [W] of every plane.
+ * jpegx_inflate_crop_pack_u8 (enqueue only): nbands uint8 planes [.][pitch] -- the clamped output of jpegx_inverse_fused_n
+ * -> [rows][cols][nbands] pixels, rows out_pitch bytes apart: out[y][x * nbands + k] = plane k[y / bs][x / bs] for y < rows,
+ * x < cols (pipeline/dct_padding.py:11-21, subsampling.py:13-14, padding.py:14-16 and the np.dstack of
+ * pipeline/__init__.py:121 as one scatter).  Exactly cols * nbands bytes of every output row are written; no read passes
+ * column (cols - 1) / bs or row (rows - 1) / bs of a plane; d_out needs NO alignment.
+ * Both: nbands in 1..JPEGX_MAX_IMAGE_BANDS, rows, cols >= 1, rows * cols <= 2^31 - 1, bs in 1..255 (else
+ * JPEGX_E_UNSUPPORTED), N in 2..32, pitches at least the row (else JPEGX_E_INVALID); one launch of any height.        */
+int jpegx_band_planes_packed_n(const uint8_t *d_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N,
+                               double *const *d_planes, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_inflate_crop_pack_u8(const uint8_t *const *d_planes, int nbands, ptrdiff_t pitch, int rows, int cols, int bs,
+                               uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -635,6 +655,31 @@ int jpegx_host_decompress_band_n(const uint8_t *h_bytes, size_t nbytes, int rows
                                  double param, uint8_t *h_out, ptrdiff_t out_pitch);
 int jpegx_host_decompress_band_i64_n(const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N, int mode,
                                      double param, int64_t *h_out);
+/* ---- a whole picture at dct_size N in 2..32 as one pooled job each way (Jpeg.compress / Jpeg.decompress,
+ * pipeline/__init__.py:98-124, with the container of file_format.py:86-111) -------------------------------------------
+ * compress_image_packed_n: [rows][cols][nbands] uint8 pixels, rows `pitch` bytes apart, go up in one piece; steps 0-3 of
+ * every band are ONE launch (jpegx_band_planes_packed_n: pipeline/padding.py:8-12, subsampling.py:9-11, dct_padding.py:8-9,
+ * normalization.py:7-8); band k then runs jpegx_forward_fused_n and jpegx_entropy_sizes_n on stream k % 2 and, once its
+ * size is known, jpegx_entropy_emit_n (pipeline/basis_change.py:11-18, quantization.py:8-18, zigzag_order.py:85-99,
+ * run_length_encoding.py:47-64, rle_byte_stream.py:48-59); `alloc` is asked ONCE for [prefix][u32 LE count][band 0]... as
+ * for jpegx_host_compress_image, and every band is copied from the device to its place.  The bytes are those of
+ * jpegx_host_compress_begin_band_n per band.  An amplitude beyond 15 bits in any band: JPEGX_E_INVALID with
+ * "BadRleCodeError" in the message; a band above 2^32 - 1 bytes with length_prefixes: JPEGX_E_INVALID.
+ * decompress_image_n: band k on stream k % 2 -- bytes up, jpegx_entropy_decode_n, jpegx_inverse_fused_n with
+ * JPEGX_F_CLAMP_U8 (pipeline/rle_byte_stream.py:61-88, run_length_encoding.py:66-97, normalization.py:10-14) -- then
+ * interleave = 1: jpegx_inflate_crop_pack_u8 behind all bands and ONE copy down, h_out [rows][cols][nbands] with rows
+ * out_pitch bytes apart; interleave = 0: per band jpegx_inflate_crop_u8 (not launched where it changes nothing), h_out
+ * [band][rows][out_pitch].  The copies to h_out are enqueued only after EVERY band's verdict is good: one refused band is
+ * JPEGX_E_INVALID and leaves h_out exactly as it was; the job context is given back.
+ * Both: nbands in 1..JPEGX_MAX_IMAGE_BANDS, bs in 1..255 (else JPEGX_E_UNSUPPORTED), rows * cols <= 2^31 - 1 and H * W
+ * (jpegx_band_shape_n) <= 2^31 - 1 per band, the quantisers none, discard and divide; every argument is checked before a
+ * device is touched.                                                                                               */
+int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs,
+                                       int N, int mode, double param, const void *prefix, size_t prefix_len,
+                                       int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols,
+                                  int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch,
+                                  int interleave);
 /* frees the pooled device / pinned buffers and streams of every job context of the current device (waits for jobs
  * of other threads to finish; JPEGX_E_INVALID while the calling thread itself holds a context) */
 int jpegx_host_pool_release(void);
@@ -740,6 +785,16 @@ int jpegx_host_decompress_band_n_on(int device, const uint8_t *h_bytes, size_t n
                                     int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch);
 int jpegx_host_decompress_band_i64_n_on(int device, const uint8_t *h_bytes, size_t nbytes, int rows, int cols, int bs, int N,
                                         int mode, double param, int64_t *h_out);
+int jpegx_band_planes_packed_n_on(int device, const uint8_t *d_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs,
+                                  int N, double *const *d_planes, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_inflate_crop_pack_u8_on(int device, const uint8_t *const *d_planes, int nbands, ptrdiff_t pitch, int rows, int cols,
+                                  int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_host_compress_image_packed_n_on(int device, const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                          int bs, int N, int mode, double param, const void *prefix, size_t prefix_len,
+                                          int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+int jpegx_host_decompress_image_n_on(int device, const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows,
+                                     int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch,
+                                     int interleave);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
