@@ -379,6 +379,30 @@ def inverse_fused_device(in_ptr, height, width, out_ptr, mode="qtable", param=0.
 # ---------------------------------------------------------------------------------------------
 # NumPy-in / NumPy-out conveniences (synchronous; H2D + kernel + D2H inside the library)
 # ---------------------------------------------------------------------------------------------
+class _Buffers:
+    """``with _Buffers() as dev:`` -- every ``dev(nbytes)`` inside is a DeviceBuffer that is freed when the block ends,
+    however it ends; one allocated late, once a size is known, included."""
+
+    def __enter__(self):
+        self._held = []
+        return self
+
+    def __call__(self, nbytes):
+        self._held.append(DeviceBuffer(nbytes))
+        return self._held[-1]
+
+    def __exit__(self, *exc):
+        for b in self._held:
+            b.free()
+
+
+def _coded(blob):
+    """Coded bytes for a native decoder: (pointer, or None for an empty string; size; the array that keeps the pointer
+    alive for as long as the caller holds it)."""
+    buf = np.frombuffer(bytes(blob), dtype=np.uint8)                    # bytes(b) of an exact bytes object is b itself
+    return (buf.ctypes.data if buf.size else None), buf.size, buf
+
+
 def _plane(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
     if a.ndim != 2:
@@ -422,14 +446,11 @@ def mean_pool_f64(plane, block_size):
     if hh % bs or ww % bs:
         raise JpegxError("plane must be a multiple of block_size in both dimensions")
     h, w = hh // bs, ww // bs
-    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(h * w * 8)
-    try:
+    with _Buffers() as dev:
+        din, dout = dev(a.nbytes), dev(h * w * 8)
         din.upload(a)
         check(lib().jpegx_mean_pool_f64(din.ptr, a.dtype.itemsize, h, w, ww, bs, dout.ptr, w, None), "jpegx_mean_pool_f64")
         return dout.download((h, w), np.float64)
-    finally:
-        din.free()
-        dout.free()
 
 
 def forward_fused_f64(plane, mode="qtable", param=0.0, flags_extra=0):
@@ -454,15 +475,12 @@ def forward_fused_pooled(plane, block_size, mode="qtable", param=0.0, pixel_inpu
     if pixel_input is None:
         pixel_input = is_pixel_like(a, bs)
     out = np.empty((h // 8, w // 8, 64), dtype=np.int16)
-    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(out.nbytes)
-    try:
+    with _Buffers() as dev:
+        din, dout = dev(a.nbytes), dev(out.nbytes)
         din.upload(a)
         forward_fused_device(din.ptr, h, w, dout.ptr, mode, param, F_PIXEL_INPUT if pixel_input else 0,
                              pitch=ww, pool=bs)
         return dout.download(out.shape, np.int16)
-    finally:
-        din.free()
-        dout.free()
 
 
 def forward_fused_u8(plane, block_size=1, mode="qtable", param=0.0, flags_extra=0):
@@ -474,14 +492,11 @@ def forward_fused_u8(plane, block_size=1, mode="qtable", param=0.0, flags_extra=
         raise JpegxError("plane must be a multiple of 8*block_size in both dimensions")
     h, w = hh // bs, ww // bs
     out = np.empty((h // 8, w // 8, 64), dtype=np.int16)
-    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(out.nbytes)
-    try:
+    with _Buffers() as dev:
+        din, dout = dev(a.nbytes), dev(out.nbytes)
         din.upload(a)
         forward_fused_u8_device(din.ptr, h, w, dout.ptr, mode, param, flags_extra, pitch=ww, pool=bs)
         return dout.download(out.shape, np.int16)
-    finally:
-        din.free()
-        dout.free()
 
 
 def inverse_fused(zz, mode="qtable", param=0.0, out="f32", clamp=False):
@@ -602,16 +617,13 @@ def entropy_block_sizes(zz):
         raise JpegxError("expected a (..., 64) coefficient stream, got %r" % (z.shape,))
     nblocks = z.size // 64
     L = lib()
-    dzz, dws = DeviceBuffer(z.nbytes), DeviceBuffer(L.jpegx_entropy_workspace_bytes(nblocks))
-    try:
+    with _Buffers() as dev:
+        dzz, dws = dev(z.nbytes), dev(L.jpegx_entropy_workspace_bytes(nblocks))
         dzz.upload(z)
         check(L.jpegx_entropy_sizes(dzz.ptr, nblocks, dws.ptr, None), "jpegx_entropy_sizes")
         out = np.empty(nblocks, dtype=np.uint32)
         check(L.jpegx_entropy_block_sizes(dws.ptr, nblocks, out.ctypes.data, None), "jpegx_entropy_block_sizes")
         return out
-    finally:
-        dzz.free()
-        dws.free()
 
 
 def last_decode_level():
@@ -640,8 +652,8 @@ def forward_u8_block_sizes(plane, block_size=1, mode="qtable", param=0.0):
     L.jpegx_internal_forward_u8_sized.restype = ctypes.c_int
     L.jpegx_internal_entropy_scan.argtypes = [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]
     L.jpegx_internal_entropy_scan.restype = ctypes.c_int
-    din, dzz, dws = DeviceBuffer(a.nbytes), DeviceBuffer(nblocks * 128), DeviceBuffer(L.jpegx_entropy_workspace_bytes(nblocks))
-    try:
+    with _Buffers() as dev:
+        din, dzz, dws = dev(a.nbytes), dev(nblocks * 128), dev(L.jpegx_entropy_workspace_bytes(nblocks))
         din.upload(a)
         bb, wb, hb = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         L.jpegx_internal_entropy_views(dws.ptr, nblocks, ctypes.byref(bb), ctypes.byref(wb), ctypes.byref(hb))
@@ -652,10 +664,6 @@ def forward_u8_block_sizes(plane, block_size=1, mode="qtable", param=0.0):
         sizes = np.empty(nblocks, dtype=np.uint32)
         check(L.jpegx_entropy_block_sizes(dws.ptr, nblocks, sizes.ctypes.data, None), "jpegx_entropy_block_sizes")
         return dzz.download((H // 8, W // 8, 64), np.int16), sizes, int(tot.value), rc
-    finally:
-        din.free()
-        dzz.free()
-        dws.free()
 
 
 def padded_shape(rows, cols, block_size=1):
@@ -691,14 +699,12 @@ def pad_edges(planes, rows, cols, block_size=1, pitch=None):
     if a.shape[0] == 0 or a.shape[0] % (h * bs):
         raise JpegxError("the buffer's rows must be a whole number of padded planes")
     require_device()
-    buf = DeviceBuffer(a.nbytes)
-    try:
+    with _Buffers() as dev:
+        buf = dev(a.nbytes)
         buf.upload(a)
         check(lib().jpegx_pad_edges(buf.ptr, a.dtype.itemsize, a.shape[0] // (h * bs), int(rows), int(cols), bs,
                                     a.shape[1] if pitch is None else int(pitch), None), "jpegx_pad_edges")
         return buf.download(a.shape, a.dtype)
-    finally:
-        buf.free()
 
 
 _ELEM_OF = {np.dtype(np.uint8): 1, np.dtype(np.int32): 4, np.dtype(np.int64): 8}
@@ -715,6 +721,59 @@ def _ragged_refused(hh, ww, bs, mode, param):
     if hh == 0 or ww == 0 or not 1 <= bs <= 255:
         return True
     return bs in (1, 2, 4) and not u8_path_ok(16, bs, 16, mode, param)
+
+
+def _tiles_refused(hh, ww, bs, mode, param):
+    """What the native entries for planes of whole tiles do not take: an empty plane, one that is not whole
+    8 * block_size tiles, a block_size beyond 1..255 and, at block sizes 1, 2, 4, rows that are no multiple of 16 samples
+    or a quantiser the uint8 kernels refuse (u8_path_ok)."""
+    if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
+        return True
+    return bs in (1, 2, 4) and bool(ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param))
+
+
+def _finish_compress(nbytes):
+    """The end of an open compress job (a jpegx_host_compress_begin* that succeeded and reported ``nbytes``): the bytes
+    object the job's stream is copied into from the device; the job is aborted if making it fails."""
+    L = lib()
+    try:
+        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)          # uninitialised bytes, filled below
+        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
+    except BaseException:
+        L.jpegx_host_compress_abort()
+        raise
+    check(rc, "jpegx_host_compress_finish")
+    return blob
+
+
+ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)   # jpegx_alloc_fn
+
+
+def _container(nbands, prefix):
+    """The end that the picture jobs share: (tail, result).  ``tail`` holds the trailing arguments of a
+    jpegx_host_compress_image* entry -- prefix, its length, length_prefixes, the allocator callback through which libjpegx
+    asks for ONE bytes object once all byte counts are known, its user pointer, the array of the bands' sizes -- and must
+    stay referenced across the native call, since it alone keeps the callback alive.  ``result()`` after a successful call:
+    the whole file when there is a ``prefix``, else the list of the bands' byte strings."""
+    box = []
+
+    def alloc(_user, nbytes):
+        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)       # uninitialised bytes, filled by the device copies
+        box.append(blob)
+        return _pyapi.PyBytes_AsString(blob)
+    sizes = (ctypes.c_size_t * nbands)()
+    head = bytes(prefix) if prefix is not None else b""
+
+    def result():
+        whole = box[0]
+        if prefix is not None:
+            return whole
+        out, at = [], 0
+        for n in sizes:
+            out.append(whole[at:at + n])
+            at += n
+        return out
+    return (head, len(head), 1 if prefix is not None else 0, ALLOC_FN(alloc), None, sizes), result
 
 
 def compress_plane_native(plane, block_size=1, mode="qtable", param=0.0, ragged=False):
@@ -738,26 +797,14 @@ def compress_plane_native(plane, block_size=1, mode="qtable", param=0.0, ragged=
             return None
         rc = L.jpegx_host_compress_begin_ragged(src.ctypes.data, elem, hh, ww, ww, bs, mode_of(mode), float(param), ctypes.byref(n))
     else:
-        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
-            return None
-        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
+        if _tiles_refused(hh, ww, bs, mode, param):
             return None
         rc = L.jpegx_host_compress_begin(src.ctypes.data, elem, hh // bs, ww // bs, ww, bs, mode_of(mode), float(param),
                                          ctypes.byref(n))
     if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not an 8-bit band after all
         return None
     check(rc, "jpegx_host_compress_begin")
-    try:
-        blob = _pyapi.PyBytes_FromStringAndSize(None, n.value)      # uninitialised bytes, filled below
-        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
-    except BaseException:
-        L.jpegx_host_compress_abort()
-        raise
-    check(rc, "jpegx_host_compress_finish")
-    return blob
-
-
-ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)   # jpegx_alloc_fn
+    return _finish_compress(n.value)
 
 
 def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
@@ -780,26 +827,12 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     if any(a.shape != a0.shape or a.dtype != a0.dtype or not a.flags.c_contiguous for a in arrs):
         return None
     hh, ww = a0.shape
-    if ragged:
-        if _ragged_refused(hh, ww, bs, mode, param):
-            return None
-    else:
-        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
-            return None
-        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
-            return None
+    if (_ragged_refused if ragged else _tiles_refused)(hh, ww, bs, mode, param):
+        return None
     L = lib()
-    box = []
-
-    def alloc(_user, nbytes):
-        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)       # uninitialised bytes, filled by the device copies
-        box.append(blob)
-        return _pyapi.PyBytes_AsString(blob)
-    cb = ALLOC_FN(alloc)
     ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    sizes = (ctypes.c_size_t * len(arrs))()
-    head = bytes(prefix) if prefix is not None else b""
-    tail = (ww, bs, mode_of(mode), float(param), head, len(head), 1 if prefix is not None else 0, cb, None, sizes)
+    tail, result = _container(len(arrs), prefix)
+    tail = (ww, bs, mode_of(mode), float(param)) + tail
     if ragged:
         rc = L.jpegx_host_compress_image_ragged(ptrs, len(arrs), elem, hh, ww, *tail)
     else:
@@ -807,14 +840,7 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not 8-bit bands after all
         return None
     check(rc, "jpegx_host_compress_image")
-    whole = box[0]
-    if prefix is not None:
-        return whole
-    out, at = [], 0
-    for n in sizes:
-        out.append(whole[at:at + n])
-        at += n
-    return out
+    return result()
 
 
 def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
@@ -830,47 +856,26 @@ def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix
     hh, ww, nb = a.shape
     if hh > 65535:
         return None
-    if ragged:
-        if _ragged_refused(hh, ww, bs, mode, param):
-            return None
-    else:
-        if hh == 0 or hh % (8 * bs) or ww % (8 * bs) or not 1 <= bs <= 255:
-            return None
-        if bs in (1, 2, 4) and (ww % 16 or not u8_path_ok(ww // bs, bs, ww, mode, param)):
-            return None
+    if (_ragged_refused if ragged else _tiles_refused)(hh, ww, bs, mode, param):
+        return None
     L = lib()
-    box = []
-
-    def alloc(_user, nbytes):
-        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)       # uninitialised bytes, filled by the device copies
-        box.append(blob)
-        return _pyapi.PyBytes_AsString(blob)
-    cb = ALLOC_FN(alloc)
-    sizes = (ctypes.c_size_t * nb)()
-    head = bytes(prefix) if prefix is not None else b""
-    tail = (ww * nb, bs, mode_of(mode), float(param), head, len(head), 1 if prefix is not None else 0, cb, None, sizes)
+    tail, result = _container(nb, prefix)
+    tail = (ww * nb, bs, mode_of(mode), float(param)) + tail
     if ragged:
         check(L.jpegx_host_compress_image_packed_ragged(a.ctypes.data, nb, hh, ww, *tail), "jpegx_host_compress_image_packed_ragged")
     else:
         check(L.jpegx_host_compress_image_packed(a.ctypes.data, nb, hh // bs, ww // bs, *tail), "jpegx_host_compress_image_packed")
-    whole = box[0]
-    if prefix is not None:
-        return whole
-    out, at = [], 0
-    for n in sizes:
-        out.append(whole[at:at + n])
-        at += n
-    return out
+    return result()
 
 
 def decompress_image_native(blobs, height, width, block_size, mode, param, rows, cols, interleave=True):
     """All bands of one picture back in ONE native job (jpegx_host_decompress_image).  (height, width): a band after
     pooling (multiples of 8); the result is cropped to (rows, cols): uint8 (rows, cols, nbands) when ``interleave``
     (what PIL's Image.fromarray takes), else (nbands, rows, cols)."""
-    bufs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blobs]
-    n = len(bufs)
-    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data if b.size else None for b in bufs])
-    sizes = (ctypes.c_size_t * n)(*[b.size for b in bufs])
+    coded = [_coded(b) for b in blobs]
+    n = len(coded)
+    ptrs = (ctypes.c_void_p * n)(*[c[0] for c in coded])
+    sizes = (ctypes.c_size_t * n)(*[c[1] for c in coded])
     out = np.empty((rows, cols, n) if interleave else (n, rows, cols), dtype=np.uint8)
     check(lib().jpegx_host_decompress_image(ptrs, sizes, n, int(height), int(width), int(block_size), mode_of(mode), float(param),
                                             out.ctypes.data, cols * n if interleave else cols, int(rows), int(cols), 1 if interleave else 0),
@@ -897,10 +902,9 @@ def compress_plane(plane, block_size=1, mode="qtable", param=0.0):
         and u8_path_ok(w, bs, ww, mode, param)
     a = np.ascontiguousarray(src, dtype=np.uint8 if as_u8 else np.float32)
     L = lib()
-    din, dzz = DeviceBuffer(a.nbytes), DeviceBuffer(h * w * 2)
-    dws = DeviceBuffer(L.jpegx_entropy_workspace_bytes(nblocks))
-    dout = None
-    try:
+    with _Buffers() as dev:
+        din, dzz = dev(a.nbytes), dev(h * w * 2)
+        dws = dev(L.jpegx_entropy_workspace_bytes(nblocks))
         din.upload(a)
         if as_u8:
             forward_fused_u8_device(din.ptr, h, w, dzz.ptr, mode, param, 0, pitch=ww, pool=bs)
@@ -910,21 +914,16 @@ def compress_plane(plane, block_size=1, mode="qtable", param=0.0):
         check(L.jpegx_entropy_sizes(dzz.ptr, nblocks, dws.ptr, None), "jpegx_entropy_sizes")
         total = ctypes.c_ulonglong(0)
         check(L.jpegx_entropy_total(dws.ptr, ctypes.byref(total), None), "jpegx_entropy_total")
-        dout = DeviceBuffer(max(1, total.value))
+        dout = dev(max(1, total.value))
         check(L.jpegx_entropy_emit(dzz.ptr, nblocks, dws.ptr, dout.ptr, None), "jpegx_entropy_emit")
         return dout.download((total.value,), np.uint8).tobytes()
-    finally:
-        for b in (din, dzz, dws, dout):
-            if b is not None:
-                b.free()
 
 
 def entropy_decode_gpu(blob, nblocks):
     """bytes -> int16 (nblocks, 64) with the parallel decoder on the device (jpegx_entropy_decode.hip)."""
-    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     out = np.empty((int(nblocks), 64), dtype=np.int16)
-    check(lib().jpegx_host_entropy_decode_gpu(buf.ctypes.data if buf.size else None, buf.size, int(nblocks),
-                                              out.ctypes.data), "jpegx_host_entropy_decode_gpu")
+    check(lib().jpegx_host_entropy_decode_gpu(ptr, size, int(nblocks), out.ctypes.data), "jpegx_host_entropy_decode_gpu")
     return out
 
 
@@ -932,20 +931,20 @@ def decompress_plane(blob, height, width, block_size=1, mode="qtable", param=0.0
     """Steps 8-1 inverted for one plane, everything on the device: entropy decoding, un-zigzag, dequantise, IDCT,
     round, clamp, replicate block_size x block_size.  (height, width) = the plane AFTER pooling, multiples of 8.
     Returns uint8 (height * block_size, width * block_size)."""
-    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     bs = int(block_size)
     pitch = (width * bs + 15) // 16 * 16
     out = np.empty((height * bs, pitch), dtype=np.uint8)
-    check(lib().jpegx_host_decompress_plane(buf.ctypes.data if buf.size else None, buf.size, int(height), int(width), bs,
+    check(lib().jpegx_host_decompress_plane(ptr, size, int(height), int(width), bs,
                                             mode_of(mode), float(param), out.ctypes.data, pitch), "jpegx_host_decompress_plane")
     return out[:, :width * bs]
 
 
 def decompress_plane_i64(blob, height, width, block_size, mode, param, rows, cols):
     """decompress_plane as the (rows, cols) int64 band the reference's decompress_band returns."""
-    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     out = np.empty((int(rows), int(cols)), dtype=np.int64)
-    check(lib().jpegx_host_decompress_plane_i64(buf.ctypes.data if buf.size else None, buf.size, int(height), int(width),
+    check(lib().jpegx_host_decompress_plane_i64(ptr, size, int(height), int(width),
                                                 int(block_size), mode_of(mode), float(param), out.ctypes.data, int(rows), int(cols)),
           "jpegx_host_decompress_plane_i64")
     return out
@@ -969,10 +968,9 @@ def entropy_decode_device(d_bytes, nbytes, nblocks, d_workspace, d_zz, stream=No
 
 def entropy_decode(blob, nblocks):
     """bytes -> int16 (nblocks, 64): RleBytestream.invert + RunLengthEncoding.invert (host, sequential)."""
-    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     out = np.empty((int(nblocks), 64), dtype=np.int16)
-    check(lib().jpegx_host_entropy_decode(buf.ctypes.data if buf.size else None, buf.size, int(nblocks),
-                                          out.ctypes.data), "jpegx_host_entropy_decode")
+    check(lib().jpegx_host_entropy_decode(ptr, size, int(nblocks), out.ctypes.data), "jpegx_host_entropy_decode")
     return out
 
 
@@ -1076,20 +1074,15 @@ def entropy_encode_n_gpu(zz, block_len=None):
     ws_bytes = L.jpegx_entropy_workspace_bytes_n(nblocks, block_len)
     if ws_bytes == 0:
         raise JpegxError("the device coder takes blocks of 1 .. 1024 coefficients and streams below 2^31 coefficients, got %r" % (z.shape,))
-    dzz, dws, dout = DeviceBuffer(z.nbytes), DeviceBuffer(ws_bytes), None
-    try:
+    with _Buffers() as dev:
+        dzz, dws = dev(z.nbytes), dev(ws_bytes)
         dzz.upload(z)
         check(L.jpegx_entropy_sizes_n(dzz.ptr, nblocks, block_len, dws.ptr, None), "jpegx_entropy_sizes_n")
         total = ctypes.c_ulonglong(0)
         check(L.jpegx_entropy_total(dws.ptr, ctypes.byref(total), None), "jpegx_entropy_total")
-        dout = DeviceBuffer(max(total.value, 1))
+        dout = dev(max(total.value, 1))
         check(L.jpegx_entropy_emit_n(dzz.ptr, nblocks, block_len, dws.ptr, dout.ptr, None), "jpegx_entropy_emit_n")
         return dout.download((total.value,), np.uint8).tobytes()
-    finally:
-        dzz.free()
-        dws.free()
-        if dout is not None:
-            dout.free()
 
 
 def compress_plane_n(plane, n, mode="none", param=0.0):
@@ -1102,14 +1095,7 @@ def compress_plane_n(plane, n, mode="none", param=0.0):
     nbytes = ctypes.c_size_t(0)
     check(L.jpegx_host_compress_begin_n(a.ctypes.data, h, w, w, n, mode_of(mode), float(param), ctypes.byref(nbytes)),
           "jpegx_host_compress_begin_n")
-    try:
-        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes.value)      # uninitialised bytes, filled below
-        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
-    except BaseException:
-        L.jpegx_host_compress_abort()
-        raise
-    check(rc, "jpegx_host_compress_finish")
-    return blob
+    return _finish_compress(nbytes.value)
 
 
 def band_shape_n(rows, cols, bs, n):
@@ -1139,14 +1125,11 @@ def band_plane_n(band, bs, n):
     rows, cols = a.shape
     h, w = band_shape_n(rows, cols, bs, n)
     require_device()
-    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(h * w * 8)
-    try:
+    with _Buffers() as dev:
+        din, dout = dev(a.nbytes), dev(h * w * 8)
         din.upload(a)
         check(lib().jpegx_band_plane_n(din.ptr, rows, cols, cols, int(bs), int(n), dout.ptr, w, None), "jpegx_band_plane_n")
         return dout.download((h, w), np.float64)
-    finally:
-        din.free()
-        dout.free()
 
 
 def compress_band_n(band, bs, n, mode="none", param=0.0):
@@ -1168,21 +1151,14 @@ def compress_band_n(band, bs, n, mode="none", param=0.0):
     if rc == -4:                                        # JPEGX_E_UNSUPPORTED: not an 8-bit band after all
         return None
     check(rc, "jpegx_host_compress_begin_band_n")
-    try:
-        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes.value)      # uninitialised bytes, filled below
-        rc = L.jpegx_host_compress_finish(_pyapi.PyBytes_AsString(blob))
-    except BaseException:
-        L.jpegx_host_compress_abort()
-        raise
-    check(rc, "jpegx_host_compress_finish")
-    return blob
+    return _finish_compress(nbytes.value)
 
 
 def entropy_decode_n(blob, nblocks, block_len):
     """bytes -> int32 (nblocks, block_len): RleBytestream.invert + RunLengthEncoding.invert (host, sequential)."""
-    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     out = np.empty((max(int(nblocks), 0), max(int(block_len), 0)), dtype=np.int32)
-    check(lib().jpegx_host_entropy_decode_n(buf.ctypes.data if buf.size else None, buf.size, int(nblocks), int(block_len),
+    check(lib().jpegx_host_entropy_decode_n(ptr, size, int(nblocks), int(block_len),
                                             out.ctypes.data if out.size else None), "jpegx_host_entropy_decode_n")
     return out
 
@@ -1190,9 +1166,9 @@ def entropy_decode_n(blob, nblocks, block_len):
 def entropy_decode_n_gpu(blob, nblocks, block_len):
     """entropy_decode_n on the device (csrc/jpegx_entropy_decode_n.hip): bytes -> int32 (nblocks, block_len), the same
     arrays; JpegxError for a stream the device refuses."""
-    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     out = np.empty((max(int(nblocks), 0), max(int(block_len), 0)), dtype=np.int32)
-    check(lib().jpegx_host_entropy_decode_n_gpu(buf.ctypes.data if buf.size else None, buf.size, int(nblocks), int(block_len),
+    check(lib().jpegx_host_entropy_decode_n_gpu(ptr, size, int(nblocks), int(block_len),
                                                 out.ctypes.data if out.size else None), "jpegx_host_entropy_decode_n_gpu")
     return out
 
@@ -1213,10 +1189,10 @@ def decompress_plane_n(blob, height, width, n, mode="none", param=0.0, out="u8")
     (height, width): the plane of whole n x n blocks; out 'u8' (clamped) or 'i32'.  JpegxError for a refused stream."""
     if out not in ("i32", "u8"):
         raise JpegxError("decompress_plane_n: out must be 'i32' or 'u8'")
-    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     h, w = int(height), int(width)
     res = np.empty((max(h, 0), max(w, 0)), dtype=np.int32 if out == "i32" else np.uint8)
-    check(lib().jpegx_host_decompress_plane_n(buf.ctypes.data if buf.size else None, buf.size, h, w, int(n), mode_of(mode), float(param),
+    check(lib().jpegx_host_decompress_plane_n(ptr, size, h, w, int(n), mode_of(mode), float(param),
                                               F_CLAMP_U8 if out == "u8" else 0, res.ctypes.data if res.size else None, w),
           "jpegx_host_decompress_plane_n")
     return res
@@ -1240,14 +1216,11 @@ def inflate_crop_u8(plane, bs, rows, cols):
     if a.shape[0] < -(-rows // bs) or a.shape[1] < -(-cols // bs):
         raise JpegxError("inflate_crop_u8: a %d x %d plane is smaller than the pooled band" % a.shape)
     require_device()
-    din, dout = DeviceBuffer(a.nbytes), DeviceBuffer(rows * cols)
-    try:
+    with _Buffers() as dev:
+        din, dout = dev(a.nbytes), dev(rows * cols)
         din.upload(a)
         check(lib().jpegx_inflate_crop_u8(din.ptr, a.shape[1], rows, cols, bs, dout.ptr, cols, None), "jpegx_inflate_crop_u8")
         return dout.download((rows, cols), np.uint8)
-    finally:
-        din.free()
-        dout.free()
 
 
 def decompress_band_n(blob, rows, cols, bs, n, mode="none", param=0.0, out="u8"):
@@ -1257,13 +1230,12 @@ def decompress_band_n(blob, rows, cols, bs, n, mode="none", param=0.0, out="u8")
     stream."""
     if out not in ("u8", "i64"):
         raise JpegxError("decompress_band_n: out must be 'u8' or 'i64'")
-    buf = np.frombuffer(blob if isinstance(blob, bytes) else bytes(blob), dtype=np.uint8)
+    ptr, size, _keep = _coded(blob)
     rows, cols = int(rows), int(cols)
     if rows * cols > 2 ** 31 - 1:                   # before NumPy is asked for it
         raise JpegxError("decompress_band_n: more than 2^31 - 1 samples in one band")
     res = np.empty((max(rows, 0), max(cols, 0)), dtype=np.uint8 if out == "u8" else np.int64)
-    args = (buf.ctypes.data if buf.size else None, buf.size, rows, cols, int(bs), int(n), mode_of(mode), float(param),
-            res.ctypes.data if res.size else None)
+    args = (ptr, size, rows, cols, int(bs), int(n), mode_of(mode), float(param), res.ctypes.data if res.size else None)
     if out == "u8":
         check(lib().jpegx_host_decompress_band_n(*args, cols), "jpegx_host_decompress_band_n")
     else:
@@ -1290,19 +1262,15 @@ def band_planes_packed_n(pixels, bs, n, pitch=None, out_pitch=None):
     if pitch < cols * nb or opitch < w:
         raise JpegxError("band_planes_packed_n: pitch smaller than the row")
     require_device()
-    din = DeviceBuffer(rows * pitch)
-    douts = [DeviceBuffer(h * opitch * 8) for _ in range(nb)]
-    try:
+    with _Buffers() as dev:
+        din = dev(rows * pitch)
+        douts = [dev(h * opitch * 8) for _ in range(nb)]
         staged = np.zeros((rows, pitch), np.uint8)
         staged[:, :cols * nb] = a.reshape(rows, cols * nb)
         din.upload(staged)
         ptrs = (ctypes.c_void_p * nb)(*[d.ptr for d in douts])
         check(lib().jpegx_band_planes_packed_n(din.ptr, nb, rows, cols, pitch, int(bs), int(n), ptrs, opitch, None), "jpegx_band_planes_packed_n")
         return [np.ascontiguousarray(d.download((h, opitch), np.float64)[:, :w]) for d in douts]
-    finally:
-        din.free()
-        for d in douts:
-            d.free()
 
 
 def inflate_crop_pack_u8(planes, rows, cols, bs, pitch=None, out_pitch=None):
@@ -1329,8 +1297,8 @@ def inflate_crop_pack_u8(planes, rows, cols, bs, pitch=None, out_pitch=None):
     if pitch < pw or opitch < cols * nb:
         raise JpegxError("inflate_crop_pack_u8: pitch smaller than the row")
     require_device()
-    dins, dout = [DeviceBuffer(ph * pitch) for _ in range(nb)], DeviceBuffer(rows * opitch)
-    try:
+    with _Buffers() as dev:
+        dins, dout = [dev(ph * pitch) for _ in range(nb)], dev(rows * opitch)
         for d, a in zip(dins, arrs):
             staged = np.zeros((ph, pitch), np.uint8)
             staged[:, :pw] = a
@@ -1338,10 +1306,6 @@ def inflate_crop_pack_u8(planes, rows, cols, bs, pitch=None, out_pitch=None):
         ptrs = (ctypes.c_void_p * nb)(*[d.ptr for d in dins])
         check(lib().jpegx_inflate_crop_pack_u8(ptrs, nb, pitch, rows, cols, bs, dout.ptr, opitch, None), "jpegx_inflate_crop_pack_u8")
         return np.ascontiguousarray(dout.download((rows, opitch), np.uint8)[:, :cols * nb]).reshape(rows, cols, nb)
-    finally:
-        dout.free()
-        for d in dins:
-            d.free()
 
 
 def compress_image_packed_n(pixels, bs, n, mode="none", param=0.0, prefix=None):
@@ -1354,41 +1318,25 @@ def compress_image_packed_n(pixels, bs, n, mode="none", param=0.0, prefix=None):
     if a.ndim != 3 or a.size == 0 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
         return None
     rows, cols, nb = a.shape
-    box = []
-
-    def alloc(_user, nbytes):
-        blob = _pyapi.PyBytes_FromStringAndSize(None, nbytes)       # uninitialised bytes, filled by the device copies
-        box.append(blob)
-        return _pyapi.PyBytes_AsString(blob)
-    cb = ALLOC_FN(alloc)
-    sizes = (ctypes.c_size_t * nb)()
-    head = bytes(prefix) if prefix is not None else b""
+    tail, result = _container(nb, prefix)
     check(lib().jpegx_host_compress_image_packed_n(a.ctypes.data, nb, rows, cols, cols * nb, int(bs), int(n), mode_of(mode), float(param),
-                                                   head, len(head), 1 if prefix is not None else 0, cb, None, sizes),
-          "jpegx_host_compress_image_packed_n")
-    whole = box[0]
-    if prefix is not None:
-        return whole
-    out, at = [], 0
-    for size in sizes:
-        out.append(whole[at:at + size])
-        at += size
-    return out
+                                                   *tail), "jpegx_host_compress_image_packed_n")
+    return result()
 
 
 def decompress_image_n(blobs, rows, cols, bs, n, mode="none", param=0.0, interleave=True):
     """All bands of one picture back at dct_size n in ONE pooled device job (jpegx_host_decompress_image_n): uint8
     (rows, cols, nbands) when ``interleave`` (what PIL's Image.fromarray takes), else (nbands, rows, cols); every band is
     what decompress_band_n returns for its bytes.  JpegxError when the device refuses a band's stream."""
-    bufs = [np.frombuffer(b if isinstance(b, bytes) else bytes(b), dtype=np.uint8) for b in blobs]
-    nb = len(bufs)
+    coded = [_coded(b) for b in blobs]
+    nb = len(coded)
     rows, cols = int(rows), int(cols)
     if not 1 <= nb <= 4:
         raise JpegxError("decompress_image_n takes 1..4 bands")
     if rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:      # before NumPy is asked for it
         raise JpegxError("decompress_image_n: rows and cols must be at least 1 and hold at most 2^31 - 1 samples")
-    ptrs = (ctypes.c_void_p * nb)(*[b.ctypes.data if b.size else None for b in bufs])
-    sizes = (ctypes.c_size_t * nb)(*[b.size for b in bufs])
+    ptrs = (ctypes.c_void_p * nb)(*[c[0] for c in coded])
+    sizes = (ctypes.c_size_t * nb)(*[c[1] for c in coded])
     out = np.empty((rows, cols, nb) if interleave else (nb, rows, cols), dtype=np.uint8)
     check(lib().jpegx_host_decompress_image_n(ptrs, sizes, nb, rows, cols, int(bs), int(n), mode_of(mode), float(param), out.ctypes.data,
                                               cols * nb if interleave else cols, 1 if interleave else 0),
@@ -1476,24 +1424,20 @@ def batch_compress(planes, block_size=1, mode="qtable", param=0.0, pixel_input=N
     a = np.zeros((n * hh, pitch), dtype=src.dtype)
     a[:, :ww] = src.reshape(n * hh, ww)
     require_device()
-    din, dws, dout = DeviceBuffer(a.nbytes), DeviceBuffer(batch_workspace_bytes(n, h, w)), None
-    try:
+    with _Buffers() as dev:
+        din, dws = dev(a.nbytes), dev(batch_workspace_bytes(n, h, w))
         din.upload(a)
         batch_compress_device(din.ptr, elem, n, h, w, dws.ptr, None, 0, mode, param, flags, pitch=pitch, block_size=bs)
         rc, total, off = batch_compress_status(dws.ptr, n, h, w)
         if rc != 0:
             check(rc, "jpegx_batch_compress_status")
-        dout = DeviceBuffer(max(1, total))
+        dout = dev(max(1, total))
         batch_emit_device(dws.ptr, n, h, w, dout.ptr, total)
         rc, total2, off = batch_compress_status(dws.ptr, n, h, w)
         if rc != 0 or total2 != total:
             check(rc if rc else -1, "jpegx_batch_emit")
         blob = dout.download((total,), np.uint8)
         return [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(n)]
-    finally:
-        for b in (din, dws, dout):
-            if b is not None:
-                b.free()
 
 
 def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.0, out="u8"):
@@ -1513,14 +1457,11 @@ def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.
     stream_bytes[:total] = np.frombuffer(b"".join(blobs), dtype=np.uint8)
     pitch = (width * bs * dtype.itemsize + 15) // 16 * 16 // dtype.itemsize
     require_device()
-    din = DeviceBuffer(stream_bytes.nbytes)
-    dws = DeviceBuffer(max(256, batch_decompress_workspace_bytes(total, n, height, width)))
-    dout = DeviceBuffer(n * height * bs * pitch * dtype.itemsize)
-    try:
+    with _Buffers() as dev:
+        din = dev(stream_bytes.nbytes)
+        dws = dev(max(256, batch_decompress_workspace_bytes(total, n, height, width)))
+        dout = dev(n * height * bs * pitch * dtype.itemsize)
         din.upload(stream_bytes)
         batch_decompress_device(din.ptr, off, n, height, width, dws.ptr, dout.ptr, pitch, bs, mode, param, 0, out_type)
         res = dout.download((n, height * bs, pitch), dtype)
         return np.ascontiguousarray(res[:, :, :width * bs])
-    finally:
-        for b in (din, dws, dout):
-            b.free()

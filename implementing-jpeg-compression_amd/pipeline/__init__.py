@@ -20,6 +20,7 @@ device is usable and the plane holds at least ``DCTN_MIN_SAMPLES`` samples; othe
 NumPy road runs, exactly as the reference does it.
 """
 import json
+import operator
 
 import numpy as np
 
@@ -212,22 +213,164 @@ def _dctn_mode(config):
     return args if args is not None and args[0] != "qtable" else None
 
 
-def _hot_forward_n(pre, config):
-    """Steps 4+5+6 for dct_size N in one launch: int32 (H/N, W/N, N*N), or None when this plane stays on the host
-    (too small, not real, not whole blocks, or coefficients that could leave the int32 range)."""
+# ---------------------------------------------------------------------------------------------------------------------
+# the questions every road asks, each answered in one place
+# ---------------------------------------------------------------------------------------------------------------------
+def _admits(gate, config, samples):
+    """What a DCTN_<X>_MIN_SAMPLES constant means.  ``gate`` is its value as the road reads it from this module when it
+    is called: the road is on, the plane holds at least that many samples, and dctn_on_device takes such a plane."""
+    return gate is not None and samples >= gate and dctn_on_device(config, samples)
+
+
+def _kept_for_plane_job(samples):
+    """A set DCTN_ENTROPY_MIN_SAMPLES that admits this plane keeps it: the plane goes on taking jpegx.compress_plane_n
+    behind the host steps, not the band job or the picture job."""
+    return DCTN_ENTROPY_MIN_SAMPLES is not None and samples >= DCTN_ENTROPY_MIN_SAMPLES
+
+
+def _job_sizes(config):
+    """(block_size, dct_size) as the device jobs for dct_size N take them, or None: block_size is no integer in 1..255, or
+    the configuration is not one for the dct_size-N kernels (_dctn_config)."""
+    bs = config.block_size
+    if not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 255 or not _dctn_config(config):
+        return None
+    return int(bs), int(config.dct_size)
+
+
+def _job_mode(config):
+    """(mode, param) for a device job that fuses whole groups of steps at dct_size N, or None: the registry is not stock or
+    the quantiser is none the kernels take."""
+    return _dctn_mode(config) if _stock_registry() else None
+
+
+def _blocked_shape(rows, cols, bs, n):
+    """(H, W) of the plane of whole n x n blocks that a rows x cols band becomes (geometry.band_geometry's last pair, from
+    the numbers: the band job sizes from the band it is handed, the decoding jobs from the configuration)."""
+    return tuple(-(-(-(-v // bs)) // n) * n for v in (rows, cols))
+
+
+def _compress_job_n(config, rows, cols, gate):
+    """(block_size, dct_size, mode, param) for a job that compresses 8-bit samples of rows x cols per band at dct_size N, or
+    None.  The cheap questions come first, since most calls end at the gate: the road is off, _job_sizes says no, the
+    plane of whole blocks holds more than 2^31 - 1 samples, ``gate`` does not admit it or a set DCTN_ENTROPY_MIN_SAMPLES
+    keeps it; then _job_mode says no, or a coefficient could reach 2^31 - 1 -- _device_job_n's guard with the 8-bit bound
+    255 in place of a scan."""
+    sizes = None if gate is None else _job_sizes(config)
+    if sizes is None:
+        return None
+    bs, n = sizes
+    h, w = _blocked_shape(rows, cols, bs, n)
+    if h * w > 2 ** 31 - 1 or not _admits(gate, config, h * w) or _kept_for_plane_job(h * w):
+        return None
+    args = _job_mode(config)
+    if args is None or not _reach(255.0, n, *args) <= 2.0 ** 31 - 1.0:
+        return None
+    return (bs, n) + tuple(args)
+
+
+def _decompress_job_n(config, blobs, gate):
+    """(rows, cols, block_size, dct_size, mode, param) for a job that decodes ``blobs`` to bands of the configured size at
+    dct_size N, or None.  Cheap questions first: the road is off, _job_sizes says no, height or width is no integer of at
+    least 1 or they hold more than 2^31 - 1 samples, ``gate`` does not admit the plane of whole blocks; then _job_mode says
+    no, the divisor is no integer (the jobs restore without the reference's truncation, _whole_divisor), or a blob is not
+    coded bytes."""
+    sizes = None if gate is None else _job_sizes(config)
+    rows, cols = config.height, config.width
+    if sizes is None or not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) \
+            or rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:
+        return None
+    bs, n = sizes
+    h, w = _blocked_shape(rows, cols, bs, n)
+    if not _admits(gate, config, h * w):
+        return None
+    args = _job_mode(config)
+    if args is None or not _whole_divisor(args) or not all(_is_coded(b) for b in blobs):
+        return None
+    return (int(rows), int(cols), bs, n) + tuple(args)
+
+
+def _blocks(config):
+    """(hb, wb): the blocks of the configured band's plane, as RunLengthEncoding.invert counts them."""
+    rle = run_length_encoding.RunLengthEncoding(config)
+    return rle._height_in_blocks(), rle._width_in_blocks()
+
+
+def _reach(peak, n, mode, param):
+    """The largest magnitude a quantised coefficient of an n x n block can take when no sample exceeds ``peak``.  The roads
+    differ in the peak (a scan of the plane, or the 8-bit bound 255) and in the bound they hold it against, which stay
+    with them."""
+    return peak * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0)
+
+
+def _is_coded(blob):
+    """Coded bytes as the device decoders take them: bytes or bytearray, not empty."""
+    return isinstance(blob, (bytes, bytearray)) and len(blob) > 0
+
+
+def _inverse_8_refuses(mode, param):
+    """The fused 8x8 inverse kernels restore in fp32 from int16: a divisor that takes 32767 past 2^24 is not exact there."""
+    return mode == "divide" and abs(param) * 32767 >= 2 ** 24
+
+
+def _none_on_bad_rle(entry, *args, **kwargs):
+    """entry(*args, **kwargs); None where the job met an amplitude beyond 15 bits -- the caller's road of before then ends
+    in the host step raising the reference's BadRleCodeError with its own text.  Any other failure is the caller's."""
+    import jpegx
+    try:
+        return entry(*args, **kwargs)
+    except jpegx.JpegxError as exc:
+        if "BadRleCodeError" not in str(exc):
+            raise
+        return None
+
+
+def _none_on_refusal(entry, *args, **kwargs):
+    """entry(*args, **kwargs); None for whatever libjpegx refuses or fails at.  For the decoding roads: the road of before
+    then ends in the host parser and the host steps, which name the fault with the reference's exceptions."""
+    import jpegx
+    try:
+        return entry(*args, **kwargs)
+    except jpegx.JpegxError:
+        return None
+
+
+def _walk(classes, method, a, config, at=None, hot=None):
+    """``method`` ('execute' or 'invert') of every class in turn; with ``at``, the three hot steps that stand there are
+    one call of ``hot`` in their place."""
+    for k, cls in enumerate(classes):
+        if at is not None and at < k <= at + 2:
+            continue                                    # folded into the fused launch at `at`
+        a = hot(a, config) if k == at else getattr(cls(config), method)(a)
+    return a
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dct_size other than 8
+# ---------------------------------------------------------------------------------------------------------------------
+def _forward_plane_n(pre, config):
+    """(float64 plane, reach, mode, param) for the forward kernels of dct_size N, or None when this plane stays on the host:
+    too small, not real, not whole blocks, or a quantiser the kernels do not take."""
     n = config.dct_size
     pre = np.asarray(pre)
     args = _dctn_mode(config)
     if args is None or pre.ndim != 2 or pre.dtype.kind not in "fiu" or not dctn_on_device(config, pre.size) \
             or pre.shape[0] % n or pre.shape[1] % n:
         return None
-    mode, param = args
     pre = pre.astype(np.float64, copy=False)
-    reach = max(abs(float(pre.max())), abs(float(pre.min()))) * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0)
+    return (pre, _reach(max(abs(float(pre.max())), abs(float(pre.min()))), n, *args)) + tuple(args)
+
+
+def _hot_forward_n(pre, config):
+    """Steps 4+5+6 for dct_size N in one launch: int32 (H/N, W/N, N*N), or None when this plane stays on the host
+    (too small, not real, not whole blocks, or coefficients that could leave the int32 range)."""
+    todo = _forward_plane_n(pre, config)
+    if todo is None:
+        return None
+    pre, reach, mode, param = todo
     if not reach < 2.0 ** 31:                       # also catches NaN
         return None
     import jpegx
-    zz = jpegx.forward_fused_n(pre, n, mode, param)
+    zz = jpegx.forward_fused_n(pre, config.dct_size, mode, param)
     # a coefficient in [2^31 - 0.5, 2^31) rounds to 2^31, which the kernel saturates to 2^31 - 1: not the reference's
     # integer, so such a plane stays on the host as well (-2^31 itself is an int32)
     if reach > 2.0 ** 31 - 1.0 and zz.max() == 2 ** 31 - 1:
@@ -254,8 +397,9 @@ def _restored_stream_n(zz, args):
     return restored.astype(np.int32), "none", 0.0
 
 
-def _hot_inverse_n(zz, config):
-    """Steps 6+5+4 inverted for dct_size N in one launch (int samples), or None when the stream stays on the host."""
+def _hot_inverse_n(zz, config, out="i32"):
+    """Steps 6+5+4 inverted for dct_size N in one launch (int samples; for out 'u8' the uint8 samples with the clamp of
+    Normalization.invert fused), or None when the stream stays on the host."""
     n = config.dct_size
     zz = np.asarray(zz)
     args = _dctn_mode(config)
@@ -271,70 +415,40 @@ def _hot_inverse_n(zz, config):
             return None
         zz = zz.astype(np.int32)
     import jpegx
-    return jpegx.inverse_fused_n(zz, n, mode, param).astype(int)
+    plane = jpegx.inverse_fused_n(zz, n, mode, param, out=out)
+    return plane.astype(int) if out == "i32" else plane
 
 
 def _device_job_n(pre, config):
     """Steps 4-8 for dct_size N as one pooled device job (jpegx.compress_plane_n: forward kernel + the run-time block length
     entropy stage, the coefficient stream never leaves the device), or None: the job road is switched off
     (DCTN_ENTROPY_MIN_SAMPLES), _hot_forward_n's preconditions do not hold, a coefficient could reach 2^31 - 1 (where the
-    kernel's saturation would go unseen), or the job met an amplitude beyond 15 bits -- the caller's road then ends in the
-    host step raising the reference's BadRleCodeError with its own text."""
-    n = config.dct_size
-    pre = np.asarray(pre)
-    args = _dctn_mode(config)
-    if DCTN_ENTROPY_MIN_SAMPLES is None or pre.size < DCTN_ENTROPY_MIN_SAMPLES:
+    kernel's saturation would go unseen), or the job met an amplitude beyond 15 bits."""
+    if not _admits(DCTN_ENTROPY_MIN_SAMPLES, config, np.asarray(pre).size):
         return None
-    if args is None or pre.ndim != 2 or pre.dtype.kind not in "fiu" or not dctn_on_device(config, pre.size) \
-            or pre.shape[0] % n or pre.shape[1] % n:
+    todo = _forward_plane_n(pre, config)
+    if todo is None:
         return None
-    mode, param = args
-    pre = pre.astype(np.float64, copy=False)
-    reach = max(abs(float(pre.max())), abs(float(pre.min()))) * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0)
+    pre, reach, mode, param = todo
     if not reach <= 2.0 ** 31 - 1.0:                # also catches NaN
         return None
     import jpegx
-    try:
-        return jpegx.compress_plane_n(pre, n, mode, param)
-    except jpegx.JpegxError as exc:
-        if "BadRleCodeError" not in str(exc):
-            raise
-        return None
+    return _none_on_bad_rle(jpegx.compress_plane_n, pre, config.dct_size, mode, param)
 
 
 def _band_job_n(band, config):
     """All nine steps for dct_size N as one device job from the band's 8-bit samples (jpegx.compress_band_n), or None: the
-    road is switched off (DCTN_BAND_JOB_MIN_SAMPLES) or the plane is below it, the registry is not stock, the plane is one
-    that a set DCTN_ENTROPY_MIN_SAMPLES sends to jpegx.compress_plane_n, the quantiser or the band is not what the job
-    takes (a real 2-D non-empty band of an integer dtype with samples in 0..255, block_size 1..255), a coefficient of an
-    8-bit band could reach 2^31 - 1, or the job met an amplitude beyond 15 bits -- the caller's road of before then ends in
-    the host step raising the reference's BadRleCodeError with its own text."""
-    args = _dctn_mode(config)
-    if DCTN_BAND_JOB_MIN_SAMPLES is None or args is None or not _stock_registry():
-        return None
-    bs, n = config.block_size, config.dct_size
+    band is not what the job takes (a real 2-D non-empty band of an integer dtype; the job itself refuses samples outside
+    0..255), _compress_job_n says no for DCTN_BAND_JOB_MIN_SAMPLES, or the job met an amplitude beyond 15 bits."""
     band = np.asarray(band)
-    if band.ndim != 2 or band.size == 0 or band.dtype.kind not in "ui" or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 255:
+    if band.ndim != 2 or band.size == 0 or band.dtype.kind not in "ui":
         return None
-    pooled = [-(-v // bs) for v in band.shape]                          # geometry.band_geometry's last two pairs, from the band itself
-    h, w = (-(-v // n) * n for v in pooled)
-    samples = h * w
-    if samples > 2 ** 31 - 1 or samples < DCTN_BAND_JOB_MIN_SAMPLES or not dctn_on_device(config, samples):
-        return None
-    if DCTN_ENTROPY_MIN_SAMPLES is not None and samples >= DCTN_ENTROPY_MIN_SAMPLES:
-        return None
-    mode, param = args
-    # _device_job_n's guard with the 8-bit bound in place of a scan of the band
-    if not 255.0 * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0) <= 2.0 ** 31 - 1.0:
+    job = _compress_job_n(config, band.shape[0], band.shape[1], DCTN_BAND_JOB_MIN_SAMPLES)     # sized from the band itself
+    if job is None:
         return None
     import jpegx
     native = band if band.dtype in (np.uint8, np.int32, np.int64) else band.astype(np.int64)
-    try:
-        return jpegx.compress_band_n(native, int(bs), int(n), mode, param)
-    except jpegx.JpegxError as exc:
-        if "BadRleCodeError" not in str(exc):
-            raise
-        return None
+    return _none_on_bad_rle(jpegx.compress_band_n, native, *job)
 
 
 def _compress_band_n(a, config):
@@ -351,97 +465,116 @@ def _compress_band_n(a, config):
     blob = _band_job_n(a, config)
     if blob is not None:
         return blob                                 # all nine steps in one device job
-    for cls in todo[:at]:
-        a = cls(config).execute(a)
+    a = _walk(todo[:at], "execute", a, config)
     if _stock_registry():
         blob = _device_job_n(a, config)
         if blob is not None:
             return blob                             # steps 4-8 in one device job
     zz = _hot_forward_n(a, config)
-    rest = todo[at + 3:]
     if zz is None:
-        rest = todo[at:]
-    elif _stock_registry():
+        return _walk(todo[at:], "execute", a, config)
+    if _stock_registry():
         try:
             return jpegx.entropy_encode_n(zz, config.dct_size ** 2)
         except jpegx.JpegxError:
             pass                                    # an amplitude beyond 15 bits: the host step raises the reference's error
-        a = zz.astype(np.float64)
-    else:
-        a = zz.astype(np.float64)                   # what Quantization + ZigzagOrder hand to the next step
-    for cls in rest:
-        a = cls(config).execute(a)
-    return a
+    # what Quantization + ZigzagOrder hand to the next step
+    return _walk(todo[at + 3:], "execute", zz.astype(np.float64), config)
 
 
-def _decode_stream_n(blob, config):
+def _decode_stream_n(blob, config, blocks=None):
     """Steps 8+7 inverted by libjpegx's sequential parser: int32 (hb, wb, N*N), or None (a malformed stream: the host
-    steps then name the fault as they always did)."""
+    steps then name the fault as they always did).  Asks for no stock registry and no whole divisor itself.  ``blocks``:
+    _blocks(config), where the caller has it already."""
     import jpegx
-    rle = run_length_encoding.RunLengthEncoding(config)
-    hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
+    hb, wb = blocks or _blocks(config)
     nn = config.dct_size ** 2
-    if not isinstance(blob, (bytes, bytearray)) or not len(blob) or hb * wb <= 0 or _dctn_mode(config) is None \
-            or not dctn_on_device(config, hb * wb * nn):
+    if not _is_coded(blob) or hb * wb <= 0 or _dctn_mode(config) is None or not dctn_on_device(config, hb * wb * nn):
         return None
-    try:
-        return jpegx.entropy_decode_n(blob, hb * wb, nn).reshape(hb, wb, nn)
-    except jpegx.JpegxError:
-        return None
+    zz = _none_on_refusal(jpegx.entropy_decode_n, blob, hb * wb, nn)
+    return None if zz is None else zz.reshape(hb, wb, nn)
 
 
-def _decode_job_n(blob, config, out):
+def _decode_job_n(blob, config, out, blocks=None):
     """Steps 8-4 inverted for dct_size N as one pooled device job (jpegx.decompress_plane_n): the samples of the plane of
     whole N x N blocks, uint8 (clamped) for out 'u8' or int32 for 'i32'; or None -- the job road is switched off
-    (DCTN_ENTROPY_DECODE_MIN_SAMPLES), _decode_stream_n's preconditions do not hold, the divisor is no integer (the job
-    restores without the reference's truncation, _whole_divisor), or the device refused the stream: the caller's road of
-    before then ends in the host parser and the host steps naming the fault."""
+    (DCTN_ENTROPY_DECODE_MIN_SAMPLES), _decode_stream_n's preconditions do not hold, the registry is not stock, the divisor
+    is no integer (the job restores without the reference's truncation, _whole_divisor), or the device refused the stream:
+    the caller's road of before then ends in the host parser and the host steps naming the fault.  The plane has no
+    block_size, so unlike the band jobs this one does not ask about it.  ``blocks``: _blocks(config), where the caller has
+    it already."""
     import jpegx
-    rle = run_length_encoding.RunLengthEncoding(config)
-    hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
+    hb, wb = blocks or _blocks(config)
     n = config.dct_size
-    args = _dctn_mode(config)
-    if DCTN_ENTROPY_DECODE_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
+    if hb * wb <= 0 or not _admits(DCTN_ENTROPY_DECODE_MIN_SAMPLES, config, hb * wb * n * n):
+        return None                                 # the cheap question first: most calls end at the gate
+    args = _job_mode(config)
+    if args is None or not _whole_divisor(args) or not _is_coded(blob):
         return None
-    if not isinstance(blob, (bytes, bytearray)) or not len(blob) or hb * wb <= 0:
-        return None
-    if hb * wb * n * n < DCTN_ENTROPY_DECODE_MIN_SAMPLES or not dctn_on_device(config, hb * wb * n * n):
-        return None
-    try:
-        return jpegx.decompress_plane_n(blob, hb * n, wb * n, n, *args, out=out)
-    except jpegx.JpegxError:
-        return None
+    return _none_on_refusal(jpegx.decompress_plane_n, blob, hb * n, wb * n, n, *args, out=out)
 
 
 def _band_decode_job_n(blob, config, out):
     """All nine steps inverted for dct_size N as one pooled device job (jpegx.decompress_band_n): the band at its configured
-    size, uint8 for out 'u8' or int64 for 'i64'; or None -- the road is switched off (DCTN_BAND_DECODE_JOB_MIN_SAMPLES) or
-    the plane is below it, _decode_job_n's other conditions do not hold (stock registry, a quantiser the kernels take, a
-    whole divisor, non-empty bytes, a usable device), block_size is no integer in 1..255, height or width no integer of at
-    least 1, the band holds more than 2^31 - 1 samples, or the device refused the stream: the caller's road of before
-    then names the fault with the reference's exceptions."""
-    args = _dctn_mode(config)
-    if DCTN_BAND_DECODE_JOB_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
-        return None
-    if not isinstance(blob, (bytes, bytearray)) or not len(blob):
-        return None
-    bs, n, rows, cols = config.block_size, config.dct_size, config.height, config.width
-    if not all(isinstance(v, (int, np.integer)) for v in (bs, rows, cols)) or not 1 <= bs <= 255 or rows < 1 or cols < 1 \
-            or rows * cols > 2 ** 31 - 1:
-        return None
-    pooled = [-(-v // bs) for v in (rows, cols)]                        # geometry.band_geometry's last two pairs
-    h, w = (-(-v // n) * n for v in pooled)
-    if h * w < DCTN_BAND_DECODE_JOB_MIN_SAMPLES or not dctn_on_device(config, h * w):
+    size, uint8 for out 'u8' or int64 for 'i64'; or None -- _decompress_job_n says no for DCTN_BAND_DECODE_JOB_MIN_SAMPLES,
+    or the device refused the stream: the caller's road of before then names the fault with the reference's exceptions."""
+    job = _decompress_job_n(config, (blob,), DCTN_BAND_DECODE_JOB_MIN_SAMPLES)
+    if job is None:
         return None
     import jpegx
-    try:
-        return jpegx.decompress_band_n(blob, int(rows), int(cols), int(bs), int(n), *args, out=out)
-    except jpegx.JpegxError:
-        return None
+    return _none_on_refusal(jpegx.decompress_band_n, blob, *job, out=out)
+
+
+def _decode_n(blob, config, want):
+    """The way back for dct_size N, for ``want`` 'u8' (displayable samples) or 'int' (the reference's integers), as
+    (array, whether it is the finished band): the band decode job's band; else the plane of whole blocks by the plane
+    decode job, else by libjpegx's host parser and jpegx.inverse_fused_n -- the caller's geometry steps remain; else
+    (None, False) and the host steps run.  A JpegxError of the inverse kernel is the caller's to map."""
+    band_out, plane_out = ("u8", "u8") if want == "u8" else ("i64", "i32")
+    band = _band_decode_job_n(blob, config, band_out)
+    if band is not None:
+        return band, True                           # all nine steps inverted in one device job
+    blocks = _blocks(config)                        # once for both roads below
+    plane = _decode_job_n(blob, config, plane_out, blocks)
+    if plane is not None:
+        return (plane if want == "u8" else plane.astype(int)), False
+    zz = _decode_stream_n(blob, config, blocks)
+    return (None if zz is None else _hot_inverse_n(zz, config, plane_out)), False
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dct_size 8
+# ---------------------------------------------------------------------------------------------------------------------
+def _mode_8(config):
+    """(mode, param) of the accelerated configuration -- transform 'DCT', dct_size 8, a quantiser libjpegx holds -- else None."""
+    return config.quantization.gpu_mode() if config.transform == "DCT" and config.dct_size == 8 else None
 
 
 def _accelerated(config):
-    return config.transform == "DCT" and config.dct_size == 8 and config.quantization.gpu_mode() is not None
+    return _mode_8(config) is not None
+
+
+def _job_config_8(config):
+    """(block_size, mode, param) where the 8x8 device jobs take the configuration, or None: not the accelerated
+    configuration, a registry that is not stock, or a block_size beyond 1..255 (one that is no integer, such as 2.0, passes:
+    the native entries take int(block_size))."""
+    args = _mode_8(config)
+    if args is None or not _stock_registry() or not 1 <= config.block_size <= 255:
+        return None
+    return (config.block_size,) + tuple(args)
+
+
+def _decode_job_8(config):
+    """(height, width, block_size, mode, param) of the plane for the 8x8 device decoding entries, or None: _job_config_8
+    says no, or the divisor is one the fused inverse refuses."""
+    job = _job_config_8(config)
+    if job is None:
+        return None
+    bs, mode, param = job
+    if _inverse_8_refuses(mode, param):
+        return None
+    hb, wb = _blocks(config)
+    return hb * 8, wb * 8, bs, mode, param
 
 
 def _hot_forward(pre, config):
@@ -467,8 +600,7 @@ def _hot_inverse(zz, config):
     import jpegx
     mode, param = config.quantization.gpu_mode()
     zz = np.asarray(zz)
-    if zz.size and np.abs(zz).max() <= 32767 and np.array_equal(zz, np.rint(zz)) and \
-            (mode != "divide" or abs(param) * 32767 < 2 ** 24):
+    if zz.size and np.abs(zz).max() <= 32767 and np.array_equal(zz, np.rint(zz)) and not _inverse_8_refuses(mode, param):
         return jpegx.inverse_fused(zz.astype(np.int16), mode, param, out="f32").astype(int)
     plane = jpegx.restore_f64(jpegx.unzigzag(zz.astype(np.float64)), mode, param)
     return jpegx.idct8x8_f64(plane, do_round=True).astype(int)
@@ -482,7 +614,7 @@ _BUILTIN_STEPS = (padding.Padding, subsampling.SubSampling, dct_padding.DCTPaddi
 
 def _stock_registry():
     """True while nobody has registered extra steps: only then may whole groups of steps be fused."""
-    return len(step_classes) == len(_BUILTIN_STEPS) and all(a is b for a, b in zip(step_classes, _BUILTIN_STEPS))
+    return len(step_classes) == len(_BUILTIN_STEPS) and all(map(operator.is_, step_classes, _BUILTIN_STEPS))
 
 
 def _hot_run(classes):
@@ -531,9 +663,7 @@ def _front_end_fused(band, config, with_entropy):
     if padded.shape[0] % (8 * bs) or padded.shape[1] % (8 * bs):
         # DCT padding is needed: it replicates POOLED edge samples (dct_padding.py:8-9), so pool on
         # the host first (steps 1-3), then the device does steps 4-8 on the padded plane
-        pre = padded
-        for cls in (subsampling.SubSampling, dct_padding.DCTPadding, normalization.Normalization):
-            pre = cls(config).execute(pre)
+        pre = _walk((subsampling.SubSampling, dct_padding.DCTPadding, normalization.Normalization), "execute", padded, config)
         if not np.array_equal(pre.astype(np.float32).astype(np.float64), pre):
             return None
         plane = pre.astype(np.uint8) if np.array_equal(pre, np.rint(pre)) else pre.astype(np.float32)
@@ -552,9 +682,7 @@ def _back_end_fused(zz, config):
     bs = config.block_size
     zz = np.asarray(zz)
     mode, param = config.quantization.gpu_mode()
-    if not 1 <= bs <= 255 or zz.ndim != 3 or zz.shape[2] != 64 or zz.size == 0:
-        return None
-    if mode == "divide" and abs(param) * 32767 >= 2 ** 24:
+    if not 1 <= bs <= 255 or zz.ndim != 3 or zz.shape[2] != 64 or zz.size == 0 or _inverse_8_refuses(mode, param):
         return None
     if zz.dtype != np.int16:                  # the C++ entropy decoder hands over int16; anything else is checked
         if np.abs(zz).max() > 32767 or not np.array_equal(zz, np.rint(zz)):
@@ -565,6 +693,9 @@ def _back_end_fused(zz, config):
     return full[:config.height, :config.width].astype(int)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the public entries
+# ---------------------------------------------------------------------------------------------------------------------
 def compress_band(a, config):
     """Run every registered step forward (pipeline/__init__.py:71-76)."""
     import jpegx
@@ -579,15 +710,7 @@ def compress_band(a, config):
             blob = _front_end_fused(a, config, with_entropy=True)
             if blob is not None:
                 return blob                               # all nine steps on the device
-        at = _hot_run(todo) if fused else None
-        for k, cls in enumerate(todo):
-            if at is not None and at < k <= at + 2:
-                continue                                   # folded into the fused launch at `at`
-            if at is not None and k == at:
-                a = _hot_forward(a, config)
-                continue
-            a = cls(config).execute(a)
-        return a
+        return _walk(todo, "execute", a, config, _hot_run(todo) if fused else None, _hot_forward)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 
@@ -598,32 +721,21 @@ def decompress_band_u8(compression_result, config):
     for a 4096x4096 band that conversion alone costs more than the whole device pipeline."""
     import jpegx
     a = compression_result
-    if _accelerated(config) and _stock_registry() and isinstance(a, (bytes, bytearray)) and len(a) \
-            and 1 <= config.block_size <= 255:
-        mode, param = config.quantization.gpu_mode()
-        if not (mode == "divide" and abs(param) * 32767 >= 2 ** 24):
-            rle = run_length_encoding.RunLengthEncoding(config)
-            hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
-            try:
-                return jpegx.decompress_plane(a, hb * 8, wb * 8, config.block_size, mode, param)[:config.height, :config.width]
-            except jpegx.JpegxError:
-                pass
+    job = _decode_job_8(config) if _is_coded(a) else None
+    band = None if job is None else _none_on_refusal(jpegx.decompress_plane, a, *job)
+    if band is not None:
+        return band[:config.height, :config.width]
     if not _accelerated(config) and _stock_registry():
-        band = _band_decode_job_n(a, config, "u8")
-        if band is not None:
-            return band                             # all nine steps inverted in one device job
-        plane = _decode_job_n(a, config, "u8")
-        zz = None if plane is not None else _decode_stream_n(a, config)
-        todo = None if zz is None else _restored_stream_n(zz, _dctn_mode(config))
-        if plane is not None or todo is not None:
-            # inverse with the clamp fused, then the geometry steps on uint8: crop the DCT padding, replicate, crop
-            n, bs = config.dct_size, config.block_size
+        try:
+            plane, done = _decode_n(a, config, "u8")
+        except jpegx.JpegxError as exc:
+            raise _bad_rle(exc)
+        if done:
+            return plane
+        if plane is not None:
+            # the clamp was fused into the inverse; the geometry steps on uint8: crop the DCT padding, replicate, crop
+            bs = config.block_size
             (rows, cols), _, pooled, _ = geometry.band_geometry(config)
-            if plane is None:
-                try:
-                    plane = jpegx.inverse_fused_n(todo[0], n, todo[1], todo[2], out="u8")
-                except jpegx.JpegxError as exc:
-                    raise _bad_rle(exc)
             plane = plane[:pooled[0], :pooled[1]]
             if bs != 1:
                 plane = np.repeat(np.repeat(plane, bs, axis=0), bs, axis=1)
@@ -635,55 +747,35 @@ def decompress_band(compression_result, config):
     """Run every registered step backwards (pipeline/__init__.py:79-88)."""
     import jpegx
     a = compression_result
+    # dct_size 8: all nine steps inverted on the device, entropy decoding included; only the samples come back
+    job = _decode_job_8(config) if _is_coded(a) else None
+    band = None if job is None else _none_on_refusal(jpegx.decompress_plane_i64, a, *job, config.height, config.width)
+    if band is not None:
+        return band if band.dtype == np.dtype(int) else band.astype(int)
     fused = _accelerated(config)
     todo = list(reversed(step_classes))
     try:
         if fused and _stock_registry():
             if isinstance(a, (bytes, bytearray)):
-                rle = run_length_encoding.RunLengthEncoding(config)
-                hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
-                mode, param = config.quantization.gpu_mode()
-                if 1 <= config.block_size <= 255 and len(a) and not (mode == "divide" and abs(param) * 32767 >= 2 ** 24):
-                    # all nine steps inverted on the device, entropy decoding included; only the samples come back
-                    try:
-                        band = jpegx.decompress_plane_i64(a, hb * 8, wb * 8, config.block_size, mode, param,
-                                                          config.height, config.width)
-                        return band if band.dtype == np.dtype(int) else band.astype(int)
-                    except jpegx.JpegxError:
-                        pass        # not a well-formed stream: the host parser below says exactly what is wrong
-                # entropy stage inverted on the host by libjpegx's C++ parser (steps 8, 7)
+                # not a well-formed stream, or one the device job does not take: the host parser of libjpegx says exactly
+                # what is wrong (steps 8, 7)
+                hb, wb = _blocks(config)
                 a = jpegx.entropy_decode(a, hb * wb).reshape(hb, wb, 64)
             else:
-                for cls in todo[:2]:
-                    a = cls(config).invert(a)
+                a = _walk(todo[:2], "invert", a, config)
             band = _back_end_fused(a, config)
             if band is not None:
                 return band
             todo = todo[2:]
         if not fused and _stock_registry():
-            band = _band_decode_job_n(a, config, "i64")
-            if band is not None:                    # all nine steps inverted in one device job: this is the band
+            band, done = _decode_n(a, config, "int")
+            if done:                                # all nine steps inverted in one device job: this is the band
                 return band if band.dtype == np.dtype(int) else band.astype(int)
-            band = _decode_job_n(a, config, "i32")
             if band is not None:
-                band = band.astype(int)
-            else:
-                zz = _decode_stream_n(a, config)
-                band = None if zz is None else _hot_inverse_n(zz, config)
-            if band is not None:
-                for cls in todo[5:]:                         # Normalization, DCTPadding, SubSampling, Padding
-                    band = cls(config).invert(band)
-                return band
+                return _walk(todo[5:], "invert", band, config)      # Normalization, DCTPadding, SubSampling, Padding
         at = _hot_run(list(reversed(todo))) if fused else None      # position counted in forward order
         at = None if at is None else len(todo) - 3 - at             # -> index of ZigzagOrder in the reversed list
-        for k, cls in enumerate(todo):
-            if at is not None and at < k <= at + 2:
-                continue
-            if at is not None and k == at:
-                a = _hot_inverse(a, config)
-                continue
-            a = cls(config).invert(a)
-        return a
+        return _walk(todo, "invert", a, config, at, _hot_inverse)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 
@@ -731,30 +823,40 @@ class Jpeg:
         return Image.fromarray(packed, mode="YCbCr")
 
 
+def _picture_size(image, config):
+    """(rows, cols) of a picture that the picture jobs take whole -- three bands (CompressedData holds three), mode YCbCr,
+    RGB, LAB or HSV, of the configured size -- else None."""
+    try:
+        bands = image.getbands()
+    except Exception:
+        return None
+    if len(bands) != 3 or image.mode not in ("YCbCr", "RGB", "LAB", "HSV") \
+            or (config.height, config.width) != (image.height, image.width):
+        return None
+    return image.height, image.width
+
+
+def _picture_pixels(image):
+    """The interleaved uint8 pixels (rows, cols, 3) of a picture _picture_size took, C-contiguous, else None.  The costly
+    part of the vetting (14 ms for 4096 x 4096), so the roads ask for it last."""
+    pixels = np.asarray(image)
+    return np.ascontiguousarray(pixels) if pixels.dtype == np.uint8 and pixels.ndim == 3 else None
+
+
 def _compress_pixels(image, config):
     """Jpeg.compress without `image.split()`: for a 4096 x 4096 picture PIL needs 25 ms to split the bands and hand each
     over as an array, 14 ms to hand over the interleaved pixels in one piece (np.asarray(image)) -- and the native job
     behind either takes 1.5 ms.  Multi-band 8-bit pictures of any size take this road (the device pads: Padding and
     DCTPadding are a margin fill in the padded device planes); the bytes are those of the per-band road.  None otherwise."""
     import jpegx
-    if not (_accelerated(config) and _stock_registry()):
+    job = _job_config_8(config)
+    if job is None or _picture_size(image, config) is None:
         return None
-    bs = config.block_size
+    pixels = _picture_pixels(image)
+    if pixels is None:
+        return None
     try:
-        bands = image.getbands()
-    except Exception:
-        return None
-    if not 1 <= bs <= 255 or len(bands) != 3 or image.mode not in ("YCbCr", "RGB", "LAB", "HSV"):      # CompressedData holds three bands
-        return None
-    if (config.height, config.width) != (image.height, image.width):
-        return None
-    pixels = np.asarray(image)
-    if pixels.dtype != np.uint8 or pixels.ndim != 3:
-        return None
-    mode, param = config.quantization.gpu_mode()
-    try:
-        return jpegx.compress_image_packed(np.ascontiguousarray(pixels), bs, mode, param, prefix=file_format.create_header(config),
-                                           ragged=True)
+        return jpegx.compress_image_packed(pixels, *job, prefix=file_format.create_header(config), ragged=True)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 
@@ -765,14 +867,11 @@ def _compress_image(arrays, config):
     file_format.py:86-93), with the bands alternating between two streams and no concatenation on the host; bands of
     any size, padded on the device.  None when the configuration or the bands do not take that road."""
     import jpegx
-    if not (_accelerated(config) and _stock_registry()):
+    job = _job_config_8(config)
+    if job is None or any(a.ndim != 2 or a.size == 0 or a.dtype.kind not in "ui" for a in arrays):
         return None
-    bs = config.block_size
-    if not 1 <= bs <= 255 or any(a.ndim != 2 or a.size == 0 or a.dtype.kind not in "ui" for a in arrays):
-        return None
-    mode, param = config.quantization.gpu_mode()
     try:
-        return jpegx.compress_image_native([np.ascontiguousarray(a) for a in arrays], bs, mode, param,
+        return jpegx.compress_image_native([np.ascontiguousarray(a) for a in arrays], *job,
                                            prefix=file_format.create_header(config), ragged=True)
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
@@ -783,91 +882,37 @@ def _decompress_image(blobs, config):
     (height, width, 3) uint8, or None when this road does not apply or the device decoder refuses a stream (the
     per-band road then names the fault)."""
     import jpegx
-    if not (_accelerated(config) and _stock_registry() and 1 <= config.block_size <= 255):
+    job = _decode_job_8(config)
+    if job is None or not all(_is_coded(b) for b in blobs):
         return None
-    if any(not isinstance(b, (bytes, bytearray)) or not len(b) for b in blobs):
-        return None
-    mode, param = config.quantization.gpu_mode()
-    if mode == "divide" and abs(param) * 32767 >= 2 ** 24:
-        return None
-    rle = run_length_encoding.RunLengthEncoding(config)
-    hb, wb = rle._height_in_blocks(), rle._width_in_blocks()
-    try:
-        return jpegx.decompress_image_native(blobs, hb * 8, wb * 8, config.block_size, mode, param, config.height, config.width)
-    except jpegx.JpegxError:
-        return None
-
-
-def _plane_samples_n(rows, cols, bs, n):
-    """H * W of the plane of whole n x n blocks for a rows x cols band (geometry.band_geometry's last pair)."""
-    h, w = (-(-(-(-v // bs)) // n) * n for v in (rows, cols))
-    return h * w
+    return _none_on_refusal(jpegx.decompress_image_native, blobs, *job, config.height, config.width)
 
 
 def _compress_pixels_n(image, config):
     """_compress_pixels for dct_size other than 8: the picture's interleaved pixels through ONE device job that writes the
     finished container (jpegx.compress_image_packed_n) -- no `image.split()`, one upload instead of three, one wait per band
     for its size instead of a whole job -- with the bytes of file_format.generate_data over three compress_band calls.  None:
-    the road is switched off (DCTN_IMAGE_JOB_MIN_SAMPLES) or the plane is below it; _compress_pixels' conditions do not
-    hold (three bands, mode YCbCr / RGB / LAB / HSV, the image of the configured size, uint8 pixels) or _band_job_n's do not
-    (stock registry, a quantiser the kernels take, a usable device, no coefficient of an 8-bit band that could reach
-    2^31 - 1, no DCTN_ENTROPY_MIN_SAMPLES admitting the plane); or the job met an amplitude beyond 15 bits -- the per-band
-    road then raises the reference's BadRleCodeError with its own text."""
-    args = _dctn_mode(config)
-    if DCTN_IMAGE_JOB_MIN_SAMPLES is None or args is None or not _stock_registry() or not _dctn_config(config):
+    the picture is not one the picture jobs take (_picture_size, _picture_pixels) or is empty or holds more than 2^31 - 1
+    pixels per band; _compress_job_n says no for DCTN_IMAGE_JOB_MIN_SAMPLES; or the job met an amplitude beyond 15 bits --
+    the per-band road then raises the reference's BadRleCodeError with its own text.  Unlike _compress_pixels this road
+    refuses a block_size that is no integer."""
+    size = _picture_size(image, config)
+    if size is None or size[0] < 1 or size[1] < 1 or size[0] * size[1] > 2 ** 31 - 1:
         return None
-    bs, n = config.block_size, config.dct_size
-    try:
-        bands = image.getbands()
-    except Exception:
-        return None
-    if not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 255 or len(bands) != 3 or image.mode not in ("YCbCr", "RGB", "LAB", "HSV"):
-        return None
-    if (config.height, config.width) != (image.height, image.width) or image.height < 1 or image.width < 1:
-        return None
-    samples = _plane_samples_n(image.height, image.width, bs, n)
-    if samples > 2 ** 31 - 1 or image.height * image.width > 2 ** 31 - 1 or samples < DCTN_IMAGE_JOB_MIN_SAMPLES \
-            or not dctn_on_device(config, samples):
-        return None
-    if DCTN_ENTROPY_MIN_SAMPLES is not None and samples >= DCTN_ENTROPY_MIN_SAMPLES:
-        return None
-    mode, param = args
-    if not 255.0 * n * n / (min(abs(param), 1.0) if mode == "divide" else 1.0) <= 2.0 ** 31 - 1.0:      # _band_job_n's guard
-        return None
-    pixels = np.asarray(image)
-    if pixels.dtype != np.uint8 or pixels.ndim != 3:
+    job = _compress_job_n(config, size[0], size[1], DCTN_IMAGE_JOB_MIN_SAMPLES)
+    pixels = None if job is None else _picture_pixels(image)
+    if pixels is None:
         return None
     import jpegx
-    try:
-        return jpegx.compress_image_packed_n(np.ascontiguousarray(pixels), int(bs), int(n), mode, param,
-                                             prefix=file_format.create_header(config))
-    except jpegx.JpegxError as exc:
-        if "BadRleCodeError" not in str(exc):
-            raise
-        return None
+    return _none_on_bad_rle(jpegx.compress_image_packed_n, pixels, *job, prefix=file_format.create_header(config))
 
 
 def _decompress_image_n(blobs, config):
     """_decompress_image for dct_size other than 8: three decompress_band_u8 calls and the np.dstack as ONE device job
-    (jpegx.decompress_image_n); (height, width, 3) uint8.  None: the road is switched off
-    (DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES) or the plane is below it, _band_decode_job_n's conditions do not hold (stock
-    registry, a quantiser the kernels take, a whole divisor, non-empty bytes, block_size an integer in 1..255, height and
-    width integers of at least 1 holding at most 2^31 - 1 samples, a usable device), or the device refused a band's
-    stream: the per-band road then names the fault."""
-    args = _dctn_mode(config) if _dctn_config(config) else None
-    if DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES is None or not _stock_registry() or args is None or not _whole_divisor(args):
-        return None
-    if any(not isinstance(b, (bytes, bytearray)) or not len(b) for b in blobs):
-        return None
-    bs, n, rows, cols = config.block_size, config.dct_size, config.height, config.width
-    if not all(isinstance(v, (int, np.integer)) for v in (bs, rows, cols)) or not 1 <= bs <= 255 or rows < 1 or cols < 1 \
-            or rows * cols > 2 ** 31 - 1:
-        return None
-    samples = _plane_samples_n(rows, cols, bs, n)
-    if samples < DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES or not dctn_on_device(config, samples):
+    (jpegx.decompress_image_n); (height, width, 3) uint8.  None: _decompress_job_n says no for
+    DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES, or the device refused a band's stream: the per-band road then names the fault."""
+    job = _decompress_job_n(config, blobs, DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES)
+    if job is None:
         return None
     import jpegx
-    try:
-        return jpegx.decompress_image_n(blobs, int(rows), int(cols), int(bs), int(n), *args)
-    except jpegx.JpegxError:
-        return None
+    return _none_on_refusal(jpegx.decompress_image_n, blobs, *job)
