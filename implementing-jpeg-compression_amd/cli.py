@@ -42,16 +42,20 @@ def quantization_from_args(args):
 
 def compress(input_fname, output_fname, block_size=4, dct_size=8, transform="DCT", quantization=None):
     from PIL import Image
-    image = Image.open(input_fname).convert("YCbCr")
+    image = Image.open(input_fname)
     config = Configuration(width=image.width, height=image.height, block_size=block_size, dct_size=dct_size,
                            transform=transform, quantization=quantization)
     with open(output_fname, "wb") as sink:
-        sink.write(Jpeg(config).compress(image))
+        # the reference's Image.open(f).convert('YCbCr') (compress.py:9): for an RGB picture inside the device job, same bytes
+        if image.mode == "RGB":
+            sink.write(Jpeg(config).compress_rgb(image))
+        else:
+            sink.write(Jpeg(config).compress(image.convert("YCbCr")))
 
 
 def decompress(input_path, output_path):
     with open(input_path, "rb") as source:
-        Jpeg.decompress(source.read()).convert("RGB").save(output_path)
+        Jpeg.decompress_rgb(source.read()).save(output_path)
 
 
 def main_compress(argv=None):

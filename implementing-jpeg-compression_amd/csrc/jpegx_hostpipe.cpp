@@ -57,6 +57,10 @@ struct Span {
 constexpr int MAX_DEVICES = 16;
 constexpr int MAX_BANDS = JPEGX_MAX_IMAGE_BANDS;
 
+// What a picture job does to the pixels while they lie in d_packed: nothing, or Pillow's conversion in place
+// (csrc/jpegx_colour.hip) -- RGB -> YCbCr on the way in, YCbCr -> RGB on the way out.
+enum class Colour { None, Rgb };
+
 // the device-side working set of one band
 struct BandSlot final : jpegx_decode::Ladder {     // the decoder's level ladder finds its memory in the slot's grow-only spans
     Span d_in, d_zz, d_ws, d_out, d_tmp;
@@ -527,6 +531,20 @@ int planes_ready(DevicePool *pool)
     return JPEGX_OK;
 }
 
+// Pillow's RGB -> YCbCr on the three-band picture in d_packed (rows back to back), in place, on aux[0] behind the upload
+int pixels_to_ycbcr(DevicePool *pool, int rows, int cols)
+{
+    uint8_t *px = static_cast<uint8_t *>(pool->d_packed.p);
+    return jpegx_rgb_to_ycbcr_u8(px, (ptrdiff_t)cols * 3, rows, cols, px, (ptrdiff_t)cols * 3, pool->aux[0]);
+}
+
+// the way back on `st`, behind the kernel that packed the three bands into d_packed and in front of the copy down
+int pixels_to_rgb(DevicePool *pool, int rows, int cols, hipStream_t st)
+{
+    uint8_t *px = static_cast<uint8_t *>(pool->d_packed.p);
+    return jpegx_ycbcr_to_rgb_u8(px, (ptrdiff_t)cols * 3, rows, cols, px, (ptrdiff_t)cols * 3, st);
+}
+
 // What the picture jobs share from the point where band k's 16-byte head is on its way to heads[2 * k] on aux[k & 1] with
 // ev[k] behind it: per band the wait, the verdict, the 32-bit length check and `emit(k, total)` (the emitter on the band's
 // stream, its destination slot[k].d_out); then ONE call of `alloc` for [prefix][u32 LE length][band 0]..., its pages
@@ -735,7 +753,7 @@ int jpegx_host_compress_abort(void)
 // copied from the device straight to their place.
 static int compress_image_impl(const void *const *h_planes, const uint8_t *h_packed, int nbands, int elem_size, int H, int W, int rows, int cols,
                                bool ragged, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len,
-                               int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+                               int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes, Colour colour = Colour::None)
 {
     if ((!h_planes && !h_packed) || !alloc || !nbytes || (prefix_len && !prefix)) return fail(JPEGX_E_INVALID, "null pointer");
     if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "compress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
@@ -769,6 +787,7 @@ static int compress_image_impl(const void *const *h_planes, const uint8_t *h_pac
             planes[k] = pool->slot[k].d_in.p;
         }
         if ((rc = upload_packed(pool, h_packed, rows, row_bytes, pitch))) return rc;
+        if (colour == Colour::Rgb && (rc = pixels_to_ycbcr(pool, rows, cols))) return rc;
         if ((rc = jpegx_deinterleave_u8(static_cast<const uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, nbands, rows, cols, planes, (ptrdiff_t)W * bs, pool->aux[0]))) return rc;
         if ((rc = planes_ready(pool))) return rc;
         tr.mark("pixels enqueued");
@@ -837,9 +856,9 @@ int jpegx_host_compress_image_packed_ragged(const uint8_t *h_pixels, int nbands,
 // file_format.py:86-93) from [rows][cols][nbands] pixels.  One upload into d_packed and ONE launch for steps 0-3 of every
 // band (jpegx_band_planes_packed_n into the slots' d_tmp) on aux[0]; then band k on aux[k & 1] with slot[k] -- forward
 // kernel, sizes, head, ev[k] -- and, once a band's size is known, its emitter; the container as compress_image_impl writes it.
-int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
-                                       double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc,
-                                       void *user, size_t *nbytes)
+static int compress_image_packed_n_impl(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                                        double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc,
+                                        void *user, size_t *nbytes, Colour colour)
 {
     if (!h_pixels || !alloc || !nbytes || (prefix_len && !prefix)) return fail(JPEGX_E_INVALID, "null pointer");
     if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "compress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
@@ -861,7 +880,7 @@ int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int 
         planes[k] = static_cast<double *>(pool->slot[k].d_tmp.p);
     }
     const size_t row_bytes = (size_t)cols * nbands;
-    if ((rc = upload_packed(pool, h_pixels, rows, row_bytes, pitch)) ||
+    if ((rc = upload_packed(pool, h_pixels, rows, row_bytes, pitch)) || (colour == Colour::Rgb && (rc = pixels_to_ycbcr(pool, rows, cols))) ||
         (rc = jpegx_band_planes_packed_n(static_cast<const uint8_t *>(pool->d_packed.p), nbands, rows, cols, (ptrdiff_t)row_bytes, bs, N, planes, W, pool->aux[0])) ||
         (rc = planes_ready(pool)))
         return rc;
@@ -875,6 +894,34 @@ int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int 
     return finish_container(job, nbands, prefix, prefix_len, length_prefixes, alloc, user, nbytes, tr, [&](int k, unsigned long long total) -> int {
         return enqueue_emit_n(pool->slot[k], H, W, N, total, pool->aux[k & 1]);
     });
+}
+
+int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                                       double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc,
+                                       void *user, size_t *nbytes)
+{
+    return compress_image_packed_n_impl(h_pixels, nbands, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user,
+                                        nbytes, Colour::None);
+}
+
+// The two compress jobs from RGB pixels: Image.open(f).convert('YCbCr') of the command line (compress.py:9) as Pillow computes
+// it, on the device between the upload and the gather; the bytes are those of the parent job on Pillow's YCbCr pixels.
+int jpegx_host_compress_image_rgb(const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param,
+                                  const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+{
+    if (!h_pixels) return fail(JPEGX_E_INVALID, "null pointer");
+    int H = 0, W = 0;
+    const int rc = ragged_shape(rows, cols, bs, &H, &W);
+    if (rc) return rc;
+    return compress_image_impl(nullptr, h_pixels, 3, 1, H, W, rows, cols, true, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc,
+                               user, nbytes, Colour::Rgb);
+}
+
+int jpegx_host_compress_image_rgb_n(const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param,
+                                    const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes)
+{
+    return compress_image_packed_n_impl(h_pixels, 3, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes,
+                                        Colour::Rgb);
 }
 
 }  // extern "C"
@@ -1039,8 +1086,8 @@ int jpegx_host_decompress_plane_i64(const uint8_t *h_bytes, size_t nbytes, int H
 // behind each other ([band][H*bs][out_pitch], interleave = 0) or as the pixel-interleaved array PIL wants
 // ([H*bs][W*bs][nbands] with rows `out_pitch` bytes apart, interleave = 1: np.dstack on the host costs more than the
 // whole device pipeline), cropped to rows x cols.
-int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int H, int W, int bs, int mode,
-                                double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols, int interleave)
+static int decompress_image_impl(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int H, int W, int bs, int mode,
+                                 double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols, int interleave, Colour colour)
 {
     if (!h_bytes || !nbytes || !h_out) return fail(JPEGX_E_INVALID, "null pointer");
     if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "decompress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
@@ -1100,6 +1147,7 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
             }
             uint8_t *packed = static_cast<uint8_t *>(pool->d_packed.p);
             if ((rc = jpegx_interleave_u8(planes, nbands, rows, cols, dev_pitch, packed, (ptrdiff_t)packed_pitch, st))) return rc;
+            if (colour == Colour::Rgb && (rc = pixels_to_rgb(pool, rows, cols, st))) return rc;
             touch.wait();                                    // the helper thread's zeros first, then the copy (see above)
             if (hipMemcpy2DAsync(h_out, (size_t)out_pitch, packed, packed_pitch, packed_pitch, (size_t)rows, hipMemcpyDeviceToHost, st) != hipSuccess)
                 return fail(JPEGX_E_HIP, "device to host copy failed");
@@ -1117,6 +1165,20 @@ int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nby
         if (!again) return job.done();
     }
     return jpegx_decode::ladder_exhausted();
+}
+
+int jpegx_host_decompress_image(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int H, int W, int bs, int mode,
+                                double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols, int interleave)
+{
+    return decompress_image_impl(h_bytes, nbytes, nbands, H, W, bs, mode, param, h_out, out_pitch, rows, cols, interleave, Colour::None);
+}
+
+// The same to RGB pixels: reconstructed.convert('RGB') of the command line (decompress.py:10) as Pillow computes it, on the
+// device between the packing kernel and the copy down, in every attempt of the retry loop.
+int jpegx_host_decompress_image_rgb(const uint8_t *const *h_bytes, const size_t *nbytes, int H, int W, int bs, int mode, double param,
+                                    uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols)
+{
+    return decompress_image_impl(h_bytes, nbytes, 3, H, W, bs, mode, param, h_out, out_pitch, rows, cols, 1, Colour::Rgb);
 }
 
 // bytes -> int16 [nblocks][64] on the device, host arrays in and out (what jpegx_host_entropy_decode does on the CPU)
@@ -1299,8 +1361,8 @@ int jpegx_host_decompress_band_i64_n(const uint8_t *h_bytes, size_t nbytes, int 
 // with the clamp -- then either ONE scatter of all bands into d_packed on aux[0] behind both streams (interleave:
 // jpegx_inflate_crop_pack_u8, [rows][cols][nbands]) or per band jpegx_inflate_crop_u8 where it changes anything (planes stacked,
 // [band][rows][out_pitch]).  Nothing is copied to h_out before EVERY band's verdict is good: a refused band leaves it as it was.
-int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode,
-                                  double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave)
+static int decompress_image_n_impl(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode,
+                                   double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave, Colour colour)
 {
     if (!h_bytes || !nbytes || !h_out) return fail(JPEGX_E_INVALID, "null pointer");
     if (nbands < 1 || nbands > MAX_BANDS) return fail(JPEGX_E_INVALID, "decompress_image takes 1..JPEGX_MAX_IMAGE_BANDS bands");
@@ -1331,7 +1393,8 @@ int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *n
         // the packing scatter runs on aux[0] behind every band: aux[1]'s bands are all in front of ev_x
         if (nbands > 1 && (hipEventRecord(pool->ev_x, pool->aux[1]) != hipSuccess || hipStreamWaitEvent(pool->aux[0], pool->ev_x, 0) != hipSuccess))
             return fail(JPEGX_E_HIP, "event between the image job's streams failed");
-        if ((rc = jpegx_inflate_crop_pack_u8(planes, nbands, W, rows, cols, bs, static_cast<uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, pool->aux[0])))
+        if ((rc = jpegx_inflate_crop_pack_u8(planes, nbands, W, rows, cols, bs, static_cast<uint8_t *>(pool->d_packed.p), (ptrdiff_t)row_bytes, pool->aux[0])) ||
+            (colour == Colour::Rgb && (rc = pixels_to_rgb(pool, rows, cols, pool->aux[0]))))
             return rc;
     }
     for (int k = 0; k < nbands; ++k)
@@ -1351,6 +1414,20 @@ int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *n
     HIP_TRY(hipStreamSynchronize(pool->aux[0]));
     HIP_TRY(hipStreamSynchronize(pool->aux[1]));
     return job.done();
+}
+
+int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode,
+                                  double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave)
+{
+    return decompress_image_n_impl(h_bytes, nbytes, nbands, rows, cols, bs, N, mode, param, h_out, out_pitch, interleave, Colour::None);
+}
+
+// The same to RGB pixels (decompress.py:10), the conversion between the scatter and the copy down; like its parent it copies
+// nothing to h_out before every band's verdict is good.
+int jpegx_host_decompress_image_rgb_n(const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols, int bs, int N, int mode,
+                                      double param, uint8_t *h_out, ptrdiff_t out_pitch)
+{
+    return decompress_image_n_impl(h_bytes, nbytes, 3, rows, cols, bs, N, mode, param, h_out, out_pitch, 1, Colour::Rgb);
 }
 
 // used by host_roundtrip (jpegx_internal.h): the synchronous host-pointer conveniences borrow the pool's

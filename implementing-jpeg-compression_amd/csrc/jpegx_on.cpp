@@ -131,3 +131,15 @@ JPEGX_ON(jpegx_host_compress_image_packed_n, (int device, const uint8_t *h_pixel
          (h_pixels, nbands, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
 JPEGX_ON(jpegx_host_decompress_image_n, (int device, const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch, int interleave),
          (h_bytes, nbytes, nbands, rows, cols, bs, N, mode, param, h_out, out_pitch, interleave))
+JPEGX_ON(jpegx_rgb_to_ycbcr_u8, (int device, const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_in, in_pitch, rows, cols, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_ycbcr_to_rgb_u8, (int device, const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_in, in_pitch, rows, cols, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_host_compress_image_rgb, (int device, const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
+         (h_pixels, rows, cols, pitch, bs, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
+JPEGX_ON(jpegx_host_decompress_image_rgb, (int device, const uint8_t *const *h_bytes, const size_t *nbytes, int H, int W, int bs, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols),
+         (h_bytes, nbytes, H, W, bs, mode, param, h_out, out_pitch, rows, cols))
+JPEGX_ON(jpegx_host_compress_image_rgb_n, (int device, const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc, void *user, size_t *nbytes),
+         (h_pixels, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
+JPEGX_ON(jpegx_host_decompress_image_rgb_n, (int device, const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch),
+         (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, out_pitch))

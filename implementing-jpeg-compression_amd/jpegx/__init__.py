@@ -9,6 +9,7 @@ Layers in this module
                          used by the reference-compatible step classes in ``pipeline/``.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -180,6 +181,12 @@ SIGNATURES = {
     "jpegx_inflate_crop_pack_u8": [_vp, _int, _pd, _int, _int, _int, _vp, _pd, _vp],
     "jpegx_host_compress_image_packed_n": [_vp, _int, _int, _int, _pd, _int, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
     "jpegx_host_decompress_image_n": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _int, _int, _dbl, _vp, _pd, _int],
+    "jpegx_rgb_to_ycbcr_u8": [_vp, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_ycbcr_to_rgb_u8": [_vp, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_host_compress_image_rgb": [_vp, _int, _int, _pd, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
+    "jpegx_host_decompress_image_rgb": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _dbl, _vp, _pd, _int, _int],
+    "jpegx_host_compress_image_rgb_n": [_vp, _int, _int, _pd, _int, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
+    "jpegx_host_decompress_image_rgb_n": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _int, _dbl, _vp, _pd],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -203,7 +210,9 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_entropy_decode_n_gpu", "jpegx_host_decompress_plane_n", "jpegx_band_shape_n", "jpegx_band_plane_n",
               "jpegx_host_compress_begin_band_n", "jpegx_inflate_crop_u8", "jpegx_host_decompress_band_n",
               "jpegx_host_decompress_band_i64_n", "jpegx_band_planes_packed_n", "jpegx_inflate_crop_pack_u8",
-              "jpegx_host_compress_image_packed_n", "jpegx_host_decompress_image_n"):
+              "jpegx_host_compress_image_packed_n", "jpegx_host_decompress_image_n", "jpegx_rgb_to_ycbcr_u8",
+              "jpegx_ycbcr_to_rgb_u8", "jpegx_host_compress_image_rgb", "jpegx_host_decompress_image_rgb",
+              "jpegx_host_compress_image_rgb_n", "jpegx_host_decompress_image_rgb_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -843,17 +852,60 @@ def compress_image_native(planes, block_size=1, mode="qtable", param=0.0, prefix
     return result()
 
 
-def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
-    """compress_image_native from pixel-interleaved samples: ``pixels`` is the (rows, cols, nbands) uint8 array that
-    np.asarray(image) gives for a multi-band PIL image -- half the host time of image.split() plus an array per band; the
-    planes are made on the device (jpegx_host_compress_image_packed).  rows and cols must be multiples of 8 * block_size
-    unless ``ragged`` (jpegx_host_compress_image_packed_ragged: any rows x cols, padded on the device).  Same bytes as
-    compress_image_native; None when this road does not apply."""
+def _colour_keyword(plain, rgb_form):
+    """``plain`` with the picture jobs' keyword ``colour``: None (the default: ``plain`` itself is called, as it always
+    was -- the bands as they come) or 'rgb' (``rgb_form``, same arguments: three-band RGB pixels outside, Pillow's
+    conversion to or from YCbCr inside the job).  The keyword is added here and not to ``plain``, whose signature and
+    calls stay what they are."""
+    @functools.wraps(plain)
+    def entry(*args, colour=None, **kwargs):
+        if colour is None:
+            return plain(*args, **kwargs)
+        if colour != "rgb":
+            raise JpegxError("%s: colour must be None or 'rgb', got %r" % (plain.__name__, colour))
+        return rgb_form(*args, **kwargs)
+    return entry
+
+
+def _three_bands(rgb, nbands, what):
+    if rgb and nbands != 3:
+        raise JpegxError("%s: colour='rgb' takes three bands, got %d" % (what, nbands))
+
+
+def _convert_pixels(pixels, entry):
+    a = _pixels_u8(pixels)
+    if a.shape[2] != 3:
+        raise JpegxError("%s: expected pixels (rows, cols, 3), got %r" % (entry, a.shape))
+    rows, cols = a.shape[:2]
+    if rows * cols > 2 ** 31 - 1:
+        raise JpegxError("%s: more than 2^31 - 1 pixels in one picture" % entry)
+    require_device()
+    with _Buffers() as dev:
+        buf = dev(a.nbytes)
+        buf.upload(a)
+        check(getattr(lib(), entry)(buf.ptr, cols * 3, rows, cols, buf.ptr, cols * 3, None), entry)
+        return buf.download(a.shape, np.uint8)
+
+
+def rgb_to_ycbcr(pixels):
+    """uint8 RGB pixels (rows, cols, 3) -> the YCbCr pixels Pillow's Image.convert('YCbCr') gives, byte for byte, on the
+    device (jpegx_rgb_to_ycbcr_u8, in place on the uploaded copy)."""
+    return _convert_pixels(pixels, "jpegx_rgb_to_ycbcr_u8")
+
+
+def ycbcr_to_rgb(pixels):
+    """uint8 YCbCr pixels (rows, cols, 3) -> the RGB pixels Pillow's Image.convert('RGB') gives, byte for byte, on the
+    device (jpegx_ycbcr_to_rgb_u8)."""
+    return _convert_pixels(pixels, "jpegx_ycbcr_to_rgb_u8")
+
+
+def _compress_image_packed(rgb, pixels, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
     a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
     bs = int(block_size)
     if a.ndim != 3 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
         return None
     hh, ww, nb = a.shape
+    _three_bands(rgb, nb, "compress_image_packed")
     if hh > 65535:
         return None
     if (_ragged_refused if ragged else _tiles_refused)(hh, ww, bs, mode, param):
@@ -861,26 +913,55 @@ def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix
     L = lib()
     tail, result = _container(nb, prefix)
     tail = (ww * nb, bs, mode_of(mode), float(param)) + tail
-    if ragged:
+    if rgb:
+        check(L.jpegx_host_compress_image_rgb(a.ctypes.data, hh, ww, *tail), "jpegx_host_compress_image_rgb")
+    elif ragged:
         check(L.jpegx_host_compress_image_packed_ragged(a.ctypes.data, nb, hh, ww, *tail), "jpegx_host_compress_image_packed_ragged")
     else:
         check(L.jpegx_host_compress_image_packed(a.ctypes.data, nb, hh // bs, ww // bs, *tail), "jpegx_host_compress_image_packed")
     return result()
 
 
-def decompress_image_native(blobs, height, width, block_size, mode, param, rows, cols, interleave=True):
-    """All bands of one picture back in ONE native job (jpegx_host_decompress_image).  (height, width): a band after
-    pooling (multiples of 8); the result is cropped to (rows, cols): uint8 (rows, cols, nbands) when ``interleave``
-    (what PIL's Image.fromarray takes), else (nbands, rows, cols)."""
+def compress_image_packed(pixels, block_size=1, mode="qtable", param=0.0, prefix=None, ragged=False):
+    """compress_image_native from pixel-interleaved samples: ``pixels`` is the (rows, cols, nbands) uint8 array that
+    np.asarray(image) gives for a multi-band PIL image -- half the host time of image.split() plus an array per band; the
+    planes are made on the device (jpegx_host_compress_image_packed).  rows and cols must be multiples of 8 * block_size
+    unless ``ragged`` (jpegx_host_compress_image_packed_ragged: any rows x cols, padded on the device).  Same bytes as
+    compress_image_native; None when this road does not apply.  Keyword ``colour='rgb'``: the pixels are RGB and become Pillow's
+    YCbCr on the device first (jpegx_host_compress_image_rgb, the ragged job) -- the bytes of this call on
+    np.asarray(image.convert('YCbCr'))."""
+    return _compress_image_packed(False, pixels, block_size, mode, param, prefix, ragged)
+
+
+def _decompress_image_native(rgb, blobs, height, width, block_size, mode, param, rows, cols, interleave=True):
     coded = [_coded(b) for b in blobs]
     n = len(coded)
     ptrs = (ctypes.c_void_p * n)(*[c[0] for c in coded])
     sizes = (ctypes.c_size_t * n)(*[c[1] for c in coded])
+    _three_bands(rgb, n, "decompress_image_native")
+    if rgb and not interleave:
+        raise JpegxError("decompress_image_native: colour='rgb' gives interleaved pixels")
     out = np.empty((rows, cols, n) if interleave else (n, rows, cols), dtype=np.uint8)
+    if rgb:
+        check(lib().jpegx_host_decompress_image_rgb(ptrs, sizes, int(height), int(width), int(block_size), mode_of(mode), float(param),
+                                                    out.ctypes.data, cols * 3, int(rows), int(cols)), "jpegx_host_decompress_image_rgb")
+        return out
     check(lib().jpegx_host_decompress_image(ptrs, sizes, n, int(height), int(width), int(block_size), mode_of(mode), float(param),
                                             out.ctypes.data, cols * n if interleave else cols, int(rows), int(cols), 1 if interleave else 0),
           "jpegx_host_decompress_image")
     return out
+
+
+def decompress_image_native(blobs, height, width, block_size, mode, param, rows, cols, interleave=True):
+    """All bands of one picture back in ONE native job (jpegx_host_decompress_image).  (height, width): a band after
+    pooling (multiples of 8); the result is cropped to (rows, cols): uint8 (rows, cols, nbands) when ``interleave``
+    (what PIL's Image.fromarray takes), else (nbands, rows, cols).  Keyword ``colour='rgb'``: the three bands are Y, Cb, Cr and the
+    interleaved result is Pillow's RGB of them, converted on the device (jpegx_host_decompress_image_rgb)."""
+    return _decompress_image_native(False, blobs, height, width, block_size, mode, param, rows, cols, interleave)
+
+
+compress_image_packed = _colour_keyword(compress_image_packed, functools.partial(_compress_image_packed, True))
+decompress_image_native = _colour_keyword(decompress_image_native, functools.partial(_decompress_image_native, True))
 
 
 def compress_plane(plane, block_size=1, mode="qtable", param=0.0):
@@ -1308,40 +1389,66 @@ def inflate_crop_pack_u8(planes, rows, cols, bs, pitch=None, out_pitch=None):
         return np.ascontiguousarray(dout.download((rows, opitch), np.uint8)[:, :cols * nb]).reshape(rows, cols, nb)
 
 
+def _compress_image_packed_n(rgb, pixels, bs, n, mode="none", param=0.0, prefix=None):
+    a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if a.ndim != 3 or a.size == 0 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
+        return None
+    rows, cols, nb = a.shape
+    _three_bands(rgb, nb, "compress_image_packed_n")
+    tail, result = _container(nb, prefix)
+    if rgb:
+        check(lib().jpegx_host_compress_image_rgb_n(a.ctypes.data, rows, cols, cols * 3, int(bs), int(n), mode_of(mode), float(param), *tail),
+              "jpegx_host_compress_image_rgb_n")
+    else:
+        check(lib().jpegx_host_compress_image_packed_n(a.ctypes.data, nb, rows, cols, cols * nb, int(bs), int(n), mode_of(mode), float(param),
+                                                       *tail), "jpegx_host_compress_image_packed_n")
+    return result()
+
+
 def compress_image_packed_n(pixels, bs, n, mode="none", param=0.0, prefix=None):
     """compress_image_packed for dct_size n: ``pixels`` is the C-contiguous (rows, cols, 1..4) uint8 array np.asarray(image)
     gives; all bands through ONE pooled device job (jpegx_host_compress_image_packed_n).  With ``prefix`` (the container
     header) the finished file -- prefix, then every band behind its '<L' byte count; without it the list of the bands' byte
     strings, each what compress_band_n returns for its band.  None when the pixels are not in that layout; JpegxError
-    naming BadRleCodeError for an amplitude beyond 15 bits."""
-    a = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
-    if a.ndim != 3 or a.size == 0 or a.dtype != np.uint8 or not 1 <= a.shape[2] <= 4 or not a.flags.c_contiguous:
-        return None
-    rows, cols, nb = a.shape
-    tail, result = _container(nb, prefix)
-    check(lib().jpegx_host_compress_image_packed_n(a.ctypes.data, nb, rows, cols, cols * nb, int(bs), int(n), mode_of(mode), float(param),
-                                                   *tail), "jpegx_host_compress_image_packed_n")
-    return result()
+    naming BadRleCodeError for an amplitude beyond 15 bits.  Keyword ``colour='rgb'``: the pixels are RGB and become Pillow's YCbCr
+    on the device first (jpegx_host_compress_image_rgb_n)."""
+    return _compress_image_packed_n(False, pixels, bs, n, mode, param, prefix)
 
 
-def decompress_image_n(blobs, rows, cols, bs, n, mode="none", param=0.0, interleave=True):
-    """All bands of one picture back at dct_size n in ONE pooled device job (jpegx_host_decompress_image_n): uint8
-    (rows, cols, nbands) when ``interleave`` (what PIL's Image.fromarray takes), else (nbands, rows, cols); every band is
-    what decompress_band_n returns for its bytes.  JpegxError when the device refuses a band's stream."""
+def _decompress_image_n(rgb, blobs, rows, cols, bs, n, mode="none", param=0.0, interleave=True):
     coded = [_coded(b) for b in blobs]
     nb = len(coded)
     rows, cols = int(rows), int(cols)
     if not 1 <= nb <= 4:
         raise JpegxError("decompress_image_n takes 1..4 bands")
+    _three_bands(rgb, nb, "decompress_image_n")
+    if rgb and not interleave:
+        raise JpegxError("decompress_image_n: colour='rgb' gives interleaved pixels")
     if rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:      # before NumPy is asked for it
         raise JpegxError("decompress_image_n: rows and cols must be at least 1 and hold at most 2^31 - 1 samples")
     ptrs = (ctypes.c_void_p * nb)(*[c[0] for c in coded])
     sizes = (ctypes.c_size_t * nb)(*[c[1] for c in coded])
     out = np.empty((rows, cols, nb) if interleave else (nb, rows, cols), dtype=np.uint8)
+    if rgb:
+        check(lib().jpegx_host_decompress_image_rgb_n(ptrs, sizes, rows, cols, int(bs), int(n), mode_of(mode), float(param), out.ctypes.data, cols * 3),
+              "jpegx_host_decompress_image_rgb_n")
+        return out
     check(lib().jpegx_host_decompress_image_n(ptrs, sizes, nb, rows, cols, int(bs), int(n), mode_of(mode), float(param), out.ctypes.data,
                                               cols * nb if interleave else cols, 1 if interleave else 0),
           "jpegx_host_decompress_image_n")
     return out
+
+
+def decompress_image_n(blobs, rows, cols, bs, n, mode="none", param=0.0, interleave=True):
+    """All bands of one picture back at dct_size n in ONE pooled device job (jpegx_host_decompress_image_n): uint8
+    (rows, cols, nbands) when ``interleave`` (what PIL's Image.fromarray takes), else (nbands, rows, cols); every band is
+    what decompress_band_n returns for its bytes.  JpegxError when the device refuses a band's stream.  Keyword ``colour='rgb'``:
+    the three bands are Y, Cb, Cr and the interleaved result is Pillow's RGB of them (jpegx_host_decompress_image_rgb_n)."""
+    return _decompress_image_n(False, blobs, rows, cols, bs, n, mode, param, interleave)
+
+
+compress_image_packed_n = _colour_keyword(compress_image_packed_n, functools.partial(_compress_image_packed_n, True))
+decompress_image_n = _colour_keyword(decompress_image_n, functools.partial(_decompress_image_n, True))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -810,6 +810,35 @@ class Jpeg:
         bands = [compress_band(a, self.config) for a in arrays]
         return file_format.generate_data(self.config, CompressedData(*bands))
 
+    def compress_rgb(self, image):
+        """The bytes of ``self.compress(image.convert("YCbCr"))`` -- what the command line does with an opened picture
+        (compress.py:9, 19-20).  An 8-bit mode-'RGB' picture of the configured size that a picture job admits goes up as
+        it is and becomes Pillow's YCbCr on the device, inside the job (jpegx.compress_image_packed / _packed_n with
+        colour='rgb'); every other case is literally that line."""
+        if getattr(image, "mode", None) == "RGB":
+            whole = _compress_pixels(image, self.config, colour="rgb")
+            if whole is None:
+                whole = _compress_pixels_n(image, self.config, colour="rgb")
+            if whole is not None:
+                return whole
+        return self.compress(image.convert("YCbCr"))
+
+    @staticmethod
+    def decompress_rgb(bytestream):
+        """A mode-'RGB' image equal to ``Jpeg.decompress(bytestream).convert("RGB")`` -- the command line's way back
+        (decompress.py:9-10).  Where a picture job decodes the container, Pillow's conversion runs on the device inside
+        it (jpegx.decompress_image_native / decompress_image_n with colour='rgb'); otherwise, and for a stream the device
+        refuses, literally that line."""
+        from PIL import Image
+        config, data = file_format.read_data(bytestream)
+        blobs = (data.y, data.cb, data.cr)
+        packed = _decompress_image(blobs, config, colour="rgb")
+        if packed is None:
+            packed = _decompress_image_n(blobs, config, colour="rgb")
+        if packed is None:
+            return Jpeg.decompress(bytestream).convert("RGB")
+        return Image.fromarray(packed, mode="RGB")
+
     @staticmethod
     def decompress(bytestream):
         from PIL import Image
@@ -836,6 +865,11 @@ def _picture_size(image, config):
     return image.height, image.width
 
 
+def _colour_kw(colour):
+    """The picture jobs' ``colour`` keyword where a road sets it; the roads of before call their entries as they always did."""
+    return {} if colour is None else {"colour": colour}
+
+
 def _picture_pixels(image):
     """The interleaved uint8 pixels (rows, cols, 3) of a picture _picture_size took, C-contiguous, else None.  The costly
     part of the vetting (14 ms for 4096 x 4096), so the roads ask for it last."""
@@ -843,11 +877,12 @@ def _picture_pixels(image):
     return np.ascontiguousarray(pixels) if pixels.dtype == np.uint8 and pixels.ndim == 3 else None
 
 
-def _compress_pixels(image, config):
+def _compress_pixels(image, config, colour=None):
     """Jpeg.compress without `image.split()`: for a 4096 x 4096 picture PIL needs 25 ms to split the bands and hand each
     over as an array, 14 ms to hand over the interleaved pixels in one piece (np.asarray(image)) -- and the native job
     behind either takes 1.5 ms.  Multi-band 8-bit pictures of any size take this road (the device pads: Padding and
-    DCTPadding are a margin fill in the padded device planes); the bytes are those of the per-band road.  None otherwise."""
+    DCTPadding are a margin fill in the padded device planes); the bytes are those of the per-band road.  None otherwise.
+    ``colour``: handed to the job (Jpeg.compress_rgb: 'rgb', the picture becomes Pillow's YCbCr on the device)."""
     import jpegx
     job = _job_config_8(config)
     if job is None or _picture_size(image, config) is None:
@@ -856,7 +891,7 @@ def _compress_pixels(image, config):
     if pixels is None:
         return None
     try:
-        return jpegx.compress_image_packed(pixels, *job, prefix=file_format.create_header(config), ragged=True)
+        return jpegx.compress_image_packed(pixels, *job, prefix=file_format.create_header(config), ragged=True, **_colour_kw(colour))
     except jpegx.JpegxError as exc:
         raise _bad_rle(exc)
 
@@ -877,25 +912,25 @@ def _compress_image(arrays, config):
         raise _bad_rle(exc)
 
 
-def _decompress_image(blobs, config):
+def _decompress_image(blobs, config, colour=None):
     """Jpeg.decompress's three decompress_band calls + np.dstack (pipeline/__init__.py:112-124) as ONE native job;
     (height, width, 3) uint8, or None when this road does not apply or the device decoder refuses a stream (the
-    per-band road then names the fault)."""
+    per-band road then names the fault).  ``colour``: handed to the job (Jpeg.decompress_rgb: 'rgb', Pillow's RGB pixels)."""
     import jpegx
     job = _decode_job_8(config)
     if job is None or not all(_is_coded(b) for b in blobs):
         return None
-    return _none_on_refusal(jpegx.decompress_image_native, blobs, *job, config.height, config.width)
+    return _none_on_refusal(jpegx.decompress_image_native, blobs, *job, config.height, config.width, **_colour_kw(colour))
 
 
-def _compress_pixels_n(image, config):
+def _compress_pixels_n(image, config, colour=None):
     """_compress_pixels for dct_size other than 8: the picture's interleaved pixels through ONE device job that writes the
     finished container (jpegx.compress_image_packed_n) -- no `image.split()`, one upload instead of three, one wait per band
     for its size instead of a whole job -- with the bytes of file_format.generate_data over three compress_band calls.  None:
     the picture is not one the picture jobs take (_picture_size, _picture_pixels) or is empty or holds more than 2^31 - 1
     pixels per band; _compress_job_n says no for DCTN_IMAGE_JOB_MIN_SAMPLES; or the job met an amplitude beyond 15 bits --
     the per-band road then raises the reference's BadRleCodeError with its own text.  Unlike _compress_pixels this road
-    refuses a block_size that is no integer."""
+    refuses a block_size that is no integer.  ``colour``: handed to the job, as in _compress_pixels."""
     size = _picture_size(image, config)
     if size is None or size[0] < 1 or size[1] < 1 or size[0] * size[1] > 2 ** 31 - 1:
         return None
@@ -904,15 +939,16 @@ def _compress_pixels_n(image, config):
     if pixels is None:
         return None
     import jpegx
-    return _none_on_bad_rle(jpegx.compress_image_packed_n, pixels, *job, prefix=file_format.create_header(config))
+    return _none_on_bad_rle(jpegx.compress_image_packed_n, pixels, *job, prefix=file_format.create_header(config), **_colour_kw(colour))
 
 
-def _decompress_image_n(blobs, config):
+def _decompress_image_n(blobs, config, colour=None):
     """_decompress_image for dct_size other than 8: three decompress_band_u8 calls and the np.dstack as ONE device job
     (jpegx.decompress_image_n); (height, width, 3) uint8.  None: _decompress_job_n says no for
-    DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES, or the device refused a band's stream: the per-band road then names the fault."""
+    DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES, or the device refused a band's stream: the per-band road then names the fault.
+    ``colour``: handed to the job, as in _decompress_image."""
     job = _decompress_job_n(config, blobs, DCTN_IMAGE_DECODE_JOB_MIN_SAMPLES)
     if job is None:
         return None
     import jpegx
-    return _none_on_refusal(jpegx.decompress_image_n, blobs, *job)
+    return _none_on_refusal(jpegx.decompress_image_n, blobs, *job, **_colour_kw(colour))

@@ -625,6 +625,20 @@ int jpegx_deinterleave_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int nbands, i
  * cols * nbands bytes of every packed row are written.  A plane row is read up to cols rounded up to 4. */
 int jpegx_interleave_u8(const void *const *d_planes, int nbands, int rows, int cols, ptrdiff_t pitch, uint8_t *d_out,
                         ptrdiff_t out_pitch, jpegx_stream_t stream);
+/* Pillow's colour conversion on the device, bit for bit: what the command line does around the codec with
+ * Image.open(f).convert('YCbCr') (compress.py:9) and reconstructed.convert('RGB') (decompress.py:10).  Pillow
+ * converts in fixed point, scale 2^6, through per-channel tables; include/jpegx_colour_tables.inc holds them, recovered from
+ * Pillow's outputs and checked against it on all 2^24 inputs in both directions (tests/golden/make_colour_tables.py; the
+ * formulas: tests/colour_model.py).  Pixels are [rows][cols][3] uint8, rows in_pitch / out_pitch bytes apart; the pointers
+ * need NO alignment and the pitches are any number of bytes >= 3 * cols: 16-byte loads and stores where a lane's 16 pixels
+ * lie inside the row and are 16-byte aligned, single bytes otherwise (rows back to back on both sides: one run of rows * cols
+ * pixels, only its two ends go byte by byte).  Exactly 3 * cols bytes of every output row are written.  d_out == d_in with
+ * equal pitches converts in place; any other overlap is undefined.  rows, cols >= 1, rows * cols <= 2^31 - 1; arguments
+ * are checked before a device is touched (JPEGX_E_INVALID). */
+int jpegx_rgb_to_ycbcr_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out, ptrdiff_t out_pitch,
+                          jpegx_stream_t stream);
+int jpegx_ycbcr_to_rgb_u8(const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out, ptrdiff_t out_pitch,
+                          jpegx_stream_t stream);
 /* the entropy decoding alone on the device: bytes -> int16 [nblocks][64] (= jpegx_host_entropy_decode) */
 int jpegx_host_entropy_decode_gpu(const uint8_t *h_bytes, size_t nbytes, long long nblocks, int16_t *h_zz);
 /* the same for blocks of block_len coefficients: bytes -> int32 [nblocks][block_len] (= jpegx_host_entropy_decode_n;
@@ -680,6 +694,28 @@ int jpegx_host_compress_image_packed_n(const uint8_t *h_pixels, int nbands, int 
 int jpegx_host_decompress_image_n(const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows, int cols,
                                   int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch,
                                   int interleave);
+/* ---- the picture jobs with Pillow's colour conversion inside: the command line's two calls around the codec,
+ * Image.open(f).convert('YCbCr') (compress.py:9) in front of Jpeg.compress and reconstructed.convert('RGB')
+ * (decompress.py:10) behind Jpeg.decompress, as one more launch on the pixels while they lie in the job's packed device
+ * buffer (jpegx_rgb_to_ycbcr_u8 / jpegx_ycbcr_to_rgb_u8, in place).  Three bands and pixel-interleaved pixels implied:
+ * h_pixels / h_out are [rows][cols][3] uint8 RGB, rows pitch / out_pitch bytes apart.  Everything else -- the arguments,
+ * the refusals, the bytes of the container, the rule for a refused stream -- is the job each entry names:
+ *   compress_image_rgb      jpegx_host_compress_image_packed_ragged   (dct_size 8), conversion between upload and gather
+ *   decompress_image_rgb    jpegx_host_decompress_image, interleave 1 (dct_size 8), conversion between packing and copy down
+ *   compress_image_rgb_n    jpegx_host_compress_image_packed_n        (dct_size N), conversion between upload and gather
+ *   decompress_image_rgb_n  jpegx_host_decompress_image_n, interleave 1 (dct_size N), conversion between scatter and copy down
+ * The compressed bytes are those of the parent job on Pillow's YCbCr pixels; the decoded pixels are Pillow's RGB of the
+ * parent job's YCbCr pixels. */
+int jpegx_host_compress_image_rgb(const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int mode, double param,
+                                  const void *prefix, size_t prefix_len, int length_prefixes, jpegx_alloc_fn alloc,
+                                  void *user, size_t *nbytes);
+int jpegx_host_decompress_image_rgb(const uint8_t *const *h_bytes, const size_t *nbytes, int H, int W, int bs, int mode,
+                                    double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols);
+int jpegx_host_compress_image_rgb_n(const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                                    double param, const void *prefix, size_t prefix_len, int length_prefixes,
+                                    jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+int jpegx_host_decompress_image_rgb_n(const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols, int bs, int N,
+                                      int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch);
 /* frees the pooled device / pinned buffers and streams of every job context of the current device (waits for jobs
  * of other threads to finish; JPEGX_E_INVALID while the calling thread itself holds a context) */
 int jpegx_host_pool_release(void);
@@ -795,6 +831,20 @@ int jpegx_host_compress_image_packed_n_on(int device, const uint8_t *h_pixels, i
 int jpegx_host_decompress_image_n_on(int device, const uint8_t *const *h_bytes, const size_t *nbytes, int nbands, int rows,
                                      int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch,
                                      int interleave);
+int jpegx_rgb_to_ycbcr_u8_on(int device, const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out,
+                             ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_ycbcr_to_rgb_u8_on(int device, const uint8_t *d_in, ptrdiff_t in_pitch, int rows, int cols, uint8_t *d_out,
+                             ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_host_compress_image_rgb_on(int device, const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int mode,
+                                     double param, const void *prefix, size_t prefix_len, int length_prefixes,
+                                     jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+int jpegx_host_decompress_image_rgb_on(int device, const uint8_t *const *h_bytes, const size_t *nbytes, int H, int W, int bs,
+                                       int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch, int rows, int cols);
+int jpegx_host_compress_image_rgb_n_on(int device, const uint8_t *h_pixels, int rows, int cols, ptrdiff_t pitch, int bs, int N,
+                                       int mode, double param, const void *prefix, size_t prefix_len, int length_prefixes,
+                                       jpegx_alloc_fn alloc, void *user, size_t *nbytes);
+int jpegx_host_decompress_image_rgb_n_on(int device, const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols,
+                                         int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
