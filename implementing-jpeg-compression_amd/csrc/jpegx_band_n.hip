@@ -20,6 +20,10 @@
 // jpegx_band_planes_packed_n reads [rows][cols][nbands] pixels and writes every band's plane in one launch -- plane k is what
 // jpegx_band_plane_n makes of pixels[:, :, k], no uint8 planes in between, every input byte read once; and
 // jpegx_inflate_crop_pack_u8 writes out[y][x * nbands + k] = plane k[y / bs][x / bs], the np.dstack included.
+//
+// And both for a STACK of equally shaped bands (the batch codec, jpegx_batch_n.cpp): jpegx_band_planes_stacked_n reads bands
+// stacked [nplanes * rows][pitch] and writes planes stacked [nplanes * H][out_pitch], plane p bit for bit what
+// jpegx_band_plane_n makes of band p, every clamp against the band's own edge; jpegx_inflate_crop_stacked_u8 is the way back.
 // Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
@@ -109,6 +113,99 @@ __global__ __launch_bounds__(256) void k_inflate_crop_u8(const uint8_t *__restri
         }
     }
     uint8_t *dst = out + (size_t)y * opitch + x0;
+    if (left >= 16 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < left) dst[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
+// ---- the same two steps for a STACK of equally shaped bands (the batch codec, jpegx_batch_n.cpp): one launch --------------
+// Bands stacked [nplanes * rows][pitch], planes stacked [nplanes * H][opitch].  A lane's tall output row yy belongs to plane
+// p = yy / H and is that plane's row y = yy - p * H; from there on the lane is the single-band kernel's, with the band's
+// base moved to row p * rows of the stack.  Every clamp is against the band's OWN rows - 1 and cols - 1, so no read
+// reaches the band above or below in the stack (min(y, rows - 1) < rows, then + p * rows).  p * rows and yy stay below
+// 2^31 (the entry checks nplanes * rows and nplanes * H); the row offsets are size_t products.
+__global__ __launch_bounds__(256) void k_band_planes_stacked_n_bs1(const uint8_t *__restrict__ bands, size_t pitch, int rows, int cols, int H, int W,
+                                                                   int quads, long long items, double *__restrict__ out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int yy = (int)(i / quads), x0 = (int)(i - (long long)yy * quads) * 4;
+    const int p = yy / H, y = yy - p * H;
+    const uint8_t *src = bands + ((size_t)p * rows + min(y, rows - 1)) * pitch;
+    unsigned v[4];
+    if (x0 + 4 <= cols && (reinterpret_cast<uintptr_t>(src + x0) & 3u) == 0) {
+        const unsigned q = *reinterpret_cast<const unsigned *>(src + x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (q >> (8 * k)) & 0xFFu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = src[min(x0 + k, cols - 1)];
+    }
+    double *dst = out + (size_t)yy * opitch + x0;
+    if (x0 + 4 <= W && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        reinterpret_cast<double2 *>(dst)[0] = make_double2((double)v[0], (double)v[1]);
+        reinterpret_cast<double2 *>(dst)[1] = make_double2((double)v[2], (double)v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x0 + k < W) dst[k] = (double)v[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_band_planes_stacked_n(const uint8_t *__restrict__ bands, size_t pitch, int rows, int cols, int bs, int prows,
+                                                               int pcols, int H, int W, long long items, double *__restrict__ out, size_t opitch)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int yy = (int)(i / W), x = (int)(i - (long long)yy * W);
+    const int p = yy / H, y = yy - p * H;
+    const int r0 = min(y, prows - 1) * bs, c0 = min(x, pcols - 1) * bs;      // r0 < rows, c0 < cols: the tile starts inside band p
+    const uint8_t *band = bands + (size_t)p * rows * pitch;                 // band p's first row
+    unsigned s = 0;
+    const int rlast = rows - 1 - r0, clast = cols - 1 - c0;                // both >= 0; the clamps below never add past rows - 1, cols - 1
+    if (bs <= clast + 1) {                                                  // the tile's columns are all there: no clamp per sample
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *q = band + (size_t)(r0 + min(u, rlast)) * pitch + c0;
+            for (int w = 0; w < bs; ++w) s += q[w];
+        }
+    } else {
+        for (int u = 0; u < bs; ++u) {
+            const uint8_t *q = band + (size_t)(r0 + min(u, rlast)) * pitch + c0;
+            for (int w = 0; w < bs; ++w) s += q[min(w, clast)];
+        }
+    }
+    out[(size_t)yy * opitch + x] = (double)s / (double)(bs * bs);
+}
+
+// The way back for the stack: uint8 planes stacked [nplanes * H][pitch] -> bands stacked [nplanes * rows][opitch],
+// out[p][y][x] = plane p[y / bs][x / bs].  k_inflate_crop_u8's lane (SIXTEEN consecutive output bytes of one output row)
+// with the tall output row yy split into p = yy / rows and y = yy - p * rows; the source row is p * H + y / bs, and y / bs <=
+// (rows - 1) / bs < H, so no read leaves plane p.  Bytes are written for x < cols only: the pitch slack stays as it was.
+// items can pass 2^32 (nplanes * rows * ceil(cols / 16)), so the index is 64 bits wide; yy < 2^31 (the entry checks it).
+__global__ __launch_bounds__(256) void k_inflate_crop_stacked_u8(const uint8_t *__restrict__ planes, size_t pitch, int H, int rows, int cols, unsigned bs,
+                                                                 unsigned chunks, unsigned long long items, uint8_t *__restrict__ out, size_t opitch)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= items) return;
+    const unsigned yy = (unsigned)(i / chunks), x0 = (unsigned)(i - (unsigned long long)yy * chunks) * 16u;
+    const unsigned p = yy / (unsigned)rows, y = yy - p * (unsigned)rows;
+    const uint8_t *src = planes + ((size_t)p * H + y / bs) * pitch;
+    unsigned q = x0 / bs, r = x0 - q * bs;
+    const int left = cols - (int)x0;                                       // >= 1: bytes of this chunk inside the row
+    unsigned v = 0, w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (k < left) {
+            if (k == 0 || r == 0) v = src[q];
+            w[k >> 2] |= v << (8 * (k & 3));
+            if (++r == bs) { r = 0; ++q; }
+        }
+    }
+    uint8_t *dst = out + (size_t)yy * opitch + x0;
     if (left >= 16 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
         *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
     } else {
@@ -326,6 +423,55 @@ int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int
     const unsigned items = (unsigned)rows * chunks;                         // at most rows * cols: below 2^31
     hipLaunchKernelGGL(k_inflate_crop_u8, dim3((items + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_plane, (size_t)pitch, cols, (unsigned)bs,
                        chunks, items, d_out, (size_t)out_pitch);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_band_planes_stacked_n(const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out,
+                                ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_bands || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (nplanes < 1) return fail(JPEGX_E_INVALID, "band_planes_stacked_n: the plane count must be positive");
+    int H = 0, W = 0;
+    const int rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W);
+    if (rc) return rc;
+    if ((long long)H * W > 0x7FFFFFFFLL / nplanes) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one stack of planes");
+    if ((long long)rows * nplanes > INT_MAX) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 rows in one stack of bands");
+    if (pitch < (ptrdiff_t)cols || out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if (reinterpret_cast<uintptr_t>(d_out) % 8) return fail(JPEGX_E_INVALID, "band_planes_stacked_n: misaligned output pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long tall = (long long)nplanes * H;                          // below 2^31: nplanes * H * W is
+    if (bs == 1) {
+        const int quads = (W + 3) / 4;
+        const long long items = tall * quads;
+        hipLaunchKernelGGL(k_band_planes_stacked_n_bs1, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d_bands, (size_t)pitch, rows, cols, H,
+                           W, quads, items, d_out, (size_t)out_pitch);
+    } else {
+        const long long items = tall * W;
+        hipLaunchKernelGGL(k_band_planes_stacked_n, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d_bands, (size_t)pitch, rows, cols, bs,
+                           (int)(((long long)rows + bs - 1) / bs), (int)(((long long)cols + bs - 1) / bs), H, W, items, d_out, (size_t)out_pitch);
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_inflate_crop_stacked_u8(const uint8_t *d_planes, int nplanes, int H, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
+                                  ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_planes || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (nplanes < 1) return fail(JPEGX_E_INVALID, "inflate_crop_stacked_u8: the plane count must be positive");
+    if (rows < 1 || cols < 1) return fail(JPEGX_E_INVALID, "inflate_crop_stacked_u8: rows and cols must be at least 1");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "inflate_crop_stacked_u8: block_size must be in 1..255");
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if ((long long)H < ((long long)rows + bs - 1) / bs) return fail(JPEGX_E_INVALID, "inflate_crop_stacked_u8: the planes are lower than the pooled band");
+    if ((long long)rows * nplanes > INT_MAX || (long long)H * nplanes > INT_MAX)
+        return fail(JPEGX_E_INVALID, "more than 2^31 - 1 rows in one stack");
+    if (pitch < (ptrdiff_t)(((long long)cols + bs - 1) / bs) || out_pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    const unsigned chunks = ((unsigned)cols + 15u) / 16u;
+    const unsigned long long items = (unsigned long long)nplanes * rows * chunks;
+    if ((items + 255u) / 256u > 0x7FFFFFFFull) return fail(JPEGX_E_INVALID, "inflate_crop_stacked_u8: more than 2^39 output bytes in one launch");
+    hipLaunchKernelGGL(k_inflate_crop_stacked_u8, dim3((unsigned)((items + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, d_planes, (size_t)pitch, H,
+                       rows, cols, (unsigned)bs, chunks, items, d_out, (size_t)out_pitch);
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

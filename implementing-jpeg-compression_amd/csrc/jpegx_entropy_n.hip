@@ -168,9 +168,11 @@ __global__ __launch_bounds__(64) void k_group_totals_n(int nblocks, void *ws)
     if (lane == 0) W.wave_bytes[blockIdx.x] = sum | (anybad ? 0x80000000u : 0u);
 }
 
-template <bool SMALL>
+// GUARD (the batch entries, jpegx_batch_n.cpp): nothing is written either when the scanned total does not fit the caller's
+// buffer -- the total is on the device once the scan has run, one uniform load (k_rle_emit2<GUARD> of jpegx_entropy.hip).
+template <bool SMALL, bool GUARD>
 __global__ __launch_bounds__(64) void k_emit_n(const int32_t *__restrict__ zz, int nblocks, int len, const void *ws,
-                                               unsigned char *__restrict__ out)
+                                               unsigned char *__restrict__ out, unsigned long long out_cap)
 {
     // the wave's bit string as big-endian 32-bit words (ds_or_b32 at each code's bit offset), at the same offset modulo
     // 16 as the global destination; byte-swapped on the way out
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(64) void k_emit_n(const int32_t *__restrict__ zz, i
     // the sizes pass flagged an amplitude beyond 15 bits: nothing is written, whether or not the caller looked at
     // jpegx_entropy_total's return code
     if (*W.error != 0) return;
+    if (GUARD && *W.total > out_cap) return;
     const int lane = threadIdx.x, unit = blockIdx.x;
     const int per = SMALL ? 64 / len : 1;
     const int b0 = unit * per;                             // the wave's first block
@@ -315,9 +318,28 @@ int jpegx_entropy_emit_n(const int32_t *d_zz, long long nblocks, int block_len, 
     const int nblk = (int)nblocks, units = units_of(nblk, block_len);
     hipStream_t st = (hipStream_t)stream;
     if (block_len < 64)
-        hipLaunchKernelGGL(k_emit_n<true>, dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out);
+        hipLaunchKernelGGL((k_emit_n<true, false>), dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out, 0ull);
     else
-        hipLaunchKernelGGL(k_emit_n<false>, dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out);
+        hipLaunchKernelGGL((k_emit_n<false, false>), dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out, 0ull);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+// the same for the batch entries (jpegx_batch_n.cpp): writes nothing either when the scanned total exceeds out_cap
+int jpegx_internal_entropy_emit_n_guarded(const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace, uint8_t *d_out,
+                                          size_t out_cap, jpegx_stream_t stream)
+{
+    int rc = check_args(d_zz, nblocks, block_len, d_workspace);
+    if (rc) return rc;
+    if (!d_out) return fail(JPEGX_E_INVALID, "null output pointer");
+    const int nblk = (int)nblocks, units = units_of(nblk, block_len);
+    hipStream_t st = (hipStream_t)stream;
+    if (block_len < 64)
+        hipLaunchKernelGGL((k_emit_n<true, true>), dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out,
+                           (unsigned long long)out_cap);
+    else
+        hipLaunchKernelGGL((k_emit_n<false, true>), dim3(units), dim3(64), 0, st, d_zz, nblk, block_len, d_workspace, d_out,
+                           (unsigned long long)out_cap);
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

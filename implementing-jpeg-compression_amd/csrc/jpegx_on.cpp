@@ -143,3 +143,15 @@ JPEGX_ON(jpegx_host_compress_image_rgb_n, (int device, const uint8_t *h_pixels, 
          (h_pixels, rows, cols, pitch, bs, N, mode, param, prefix, prefix_len, length_prefixes, alloc, user, nbytes))
 JPEGX_ON(jpegx_host_decompress_image_rgb_n, (int device, const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols, int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch),
          (h_bytes, nbytes, rows, cols, bs, N, mode, param, h_out, out_pitch))
+JPEGX_ON(jpegx_band_planes_stacked_n, (int device, const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs, int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_bands, nplanes, rows, cols, pitch, bs, N, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_inflate_crop_stacked_u8, (int device, const uint8_t *d_planes, int nplanes, int H, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_planes, nplanes, H, pitch, rows, cols, bs, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_batch_compress_n, (int device, const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_bands, nplanes, rows, cols, pitch, bs, N, mode, param, group_planes, d_workspace, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_compress_status_n, (int device, const void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes, unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream),
+         (d_workspace, nplanes, rows, cols, bs, N, group_planes, h_total, h_plane_offsets, stream))
+JPEGX_ON(jpegx_batch_emit_n, (int device, void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_workspace, nplanes, rows, cols, bs, N, group_planes, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_decompress_n, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols, int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_bytes, h_plane_offsets, nplanes, rows, cols, bs, N, mode, param, group_planes, d_workspace, d_out, out_pitch, stream))

@@ -24,6 +24,8 @@ int jpegx_internal_entropy_scan(long long nblocks, void *d_workspace, jpegx_stre
 int jpegx_internal_entropy_emit2(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
 int jpegx_internal_entropy_emit2_guarded(const int16_t *d_zz, long long nblocks, const void *d_workspace, uint8_t *d_out, size_t out_cap,
                                          jpegx_stream_t stream);
+int jpegx_internal_entropy_emit_n_guarded(const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace, uint8_t *d_out,
+                                          size_t out_cap, jpegx_stream_t stream);   // jpegx_entropy_n.hip: jpegx_entropy_emit_n for the batch entries
 int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
                                        jpegx_stream_t stream);
 // jpegx_hostpipe.cpp: a job context of the current device borrowed for one call (host_roundtrip, jpegx_internal.h)

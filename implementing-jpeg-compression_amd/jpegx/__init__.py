@@ -187,6 +187,16 @@ SIGNATURES = {
     "jpegx_host_decompress_image_rgb": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _dbl, _vp, _pd, _int, _int],
     "jpegx_host_compress_image_rgb_n": [_vp, _int, _int, _pd, _int, _int, _int, _dbl, _vp, _sz, _int, _vp, _vp, _c.POINTER(_sz)],
     "jpegx_host_decompress_image_rgb_n": [_vp, _c.POINTER(_sz), _int, _int, _int, _int, _int, _dbl, _vp, _pd],
+    "jpegx_band_planes_stacked_n": [_vp, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_inflate_crop_stacked_u8": [_vp, _int, _int, _pd, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_batch_workspace_bytes_n": [_int, _int, _int, _int, _int, _int],
+    "jpegx_batch_max_bytes_n": [_int, _int, _int, _int, _int],
+    "jpegx_batch_compress_n": [_vp, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
+    "jpegx_batch_compress_status_n": [_vp, _int, _int, _int, _int, _int, _int, _c.POINTER(_c.c_ulonglong), _vp, _vp],
+    "jpegx_batch_emit_n": [_vp, _int, _int, _int, _int, _int, _int, _vp, _sz, _vp],
+    "jpegx_batch_groups_n": [_vp, _int, _int, _int, _int, _int, _int, _vp, _c.POINTER(_int)],
+    "jpegx_batch_decompress_workspace_bytes_n": [_sz, _int, _int, _int, _int, _int, _int],
+    "jpegx_batch_decompress_n": [_vp, _vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _vp, _vp, _pd, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -212,11 +222,14 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_decompress_band_i64_n", "jpegx_band_planes_packed_n", "jpegx_inflate_crop_pack_u8",
               "jpegx_host_compress_image_packed_n", "jpegx_host_decompress_image_n", "jpegx_rgb_to_ycbcr_u8",
               "jpegx_ycbcr_to_rgb_u8", "jpegx_host_compress_image_rgb", "jpegx_host_decompress_image_rgb",
-              "jpegx_host_compress_image_rgb_n", "jpegx_host_decompress_image_rgb_n"):
+              "jpegx_host_compress_image_rgb_n", "jpegx_host_decompress_image_rgb_n", "jpegx_band_planes_stacked_n",
+              "jpegx_inflate_crop_stacked_u8", "jpegx_batch_compress_n", "jpegx_batch_compress_status_n", "jpegx_batch_emit_n",
+              "jpegx_batch_decompress_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
-            "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz}   # everything else returns int
+            "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz, "jpegx_batch_workspace_bytes_n": _sz,
+            "jpegx_batch_max_bytes_n": _sz, "jpegx_batch_decompress_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -1572,3 +1585,148 @@ def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.
         batch_decompress_device(din.ptr, off, n, height, width, dws.ptr, dout.ptr, pitch, bs, mode, param, 0, out_type)
         res = dout.download((n, height * bs, pitch), dtype)
         return np.ascontiguousarray(res[:, :, :width * bs])
+
+
+# ---------------------------------------------------------------------------------------------
+# the batch codec for any DCT size: a stack of 8-bit bands -> one coded stream with a plane index, and back
+# ---------------------------------------------------------------------------------------------
+def batch_workspace_bytes_n(nplanes, rows, cols, bs, n, group_planes=0):
+    return lib().jpegx_batch_workspace_bytes_n(int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes))
+
+
+def batch_max_bytes_n(nplanes, rows, cols, bs, n):
+    return lib().jpegx_batch_max_bytes_n(int(nplanes), int(rows), int(cols), int(bs), int(n))
+
+
+def batch_decompress_workspace_bytes_n(nbytes, nplanes, rows, cols, bs, n, group_planes=0):
+    return lib().jpegx_batch_decompress_workspace_bytes_n(int(nbytes), int(nplanes), int(rows), int(cols), int(bs), int(n),
+                                                          int(group_planes))
+
+
+def batch_groups_n(plane_offsets, nplanes, rows, cols, bs, n, group_planes=0):
+    """The cut of a coded batch into decoding groups (jpegx_batch_groups_n; host arithmetic, no device needed): the first
+    plane of every group and, last, nplanes."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(nplanes) + 1,):
+        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    first = np.zeros(int(nplanes) + 1, dtype=np.int32)
+    ngroups = ctypes.c_int(0)
+    check(lib().jpegx_batch_groups_n(off.ctypes.data, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes),
+                                     first.ctypes.data, ctypes.byref(ngroups)), "jpegx_batch_groups_n")
+    return first[:ngroups.value + 1].copy()
+
+
+def band_planes_stacked_n_device(d_bands, nplanes, rows, cols, bs, n, d_out, pitch=None, out_pitch=None, stream=None, device=None):
+    """Enqueue jpegx_band_planes_stacked_n: bands stacked [nplanes * rows][pitch] (default cols) -> float64 planes stacked
+    [nplanes * H][out_pitch] (default W), (H, W) = band_shape_n(rows, cols, bs, n)."""
+    args = (d_bands, int(nplanes), int(rows), int(cols), int(cols if pitch is None else pitch), int(bs), int(n), d_out,
+            int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_band_planes_stacked_n(*args) if device is None else L.jpegx_band_planes_stacked_n_on(int(device), *args),
+          "jpegx_band_planes_stacked_n")
+
+
+def inflate_crop_stacked_u8_device(d_planes, nplanes, height, pitch, rows, cols, bs, d_out, out_pitch=None, stream=None, device=None):
+    """Enqueue jpegx_inflate_crop_stacked_u8: uint8 planes stacked [nplanes * height][pitch] -> bands stacked
+    [nplanes * rows][out_pitch] (default cols)."""
+    args = (d_planes, int(nplanes), int(height), int(pitch), int(rows), int(cols), int(bs), d_out,
+            int(cols if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_inflate_crop_stacked_u8(*args) if device is None else L.jpegx_inflate_crop_stacked_u8_on(int(device), *args),
+          "jpegx_inflate_crop_stacked_u8")
+
+
+def batch_compress_n_device(d_bands, nplanes, rows, cols, bs, n, d_workspace, d_out, out_cap, mode="none", param=0.0,
+                            group_planes=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_compress_n: bands stacked [nplanes * rows][pitch] (bytes, default cols) -> coded bytes at d_out
+    (None: sizes only).  Verdict and plane index: batch_compress_status_n."""
+    args = (d_bands, int(nplanes), int(rows), int(cols), int(cols if pitch is None else pitch), int(bs), int(n), mode_of(mode),
+            float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress_n(*args) if device is None else L.jpegx_batch_compress_n_on(int(device), *args), "jpegx_batch_compress_n")
+
+
+def batch_compress_status_n(d_workspace, nplanes, rows, cols, bs, n, group_planes=0, stream=None, device=None):
+    """Synchronises; returns (rc, total, offsets) as batch_compress_status does."""
+    total = ctypes.c_ulonglong(0)
+    off = np.zeros(int(nplanes) + 1, dtype=np.uint64)
+    args = (d_workspace, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes), ctypes.byref(total), off.ctypes.data, stream)
+    L = lib()
+    rc = L.jpegx_batch_compress_status_n(*args) if device is None else L.jpegx_batch_compress_status_n_on(int(device), *args)
+    if rc not in (0, 1, -1):
+        check(rc, "jpegx_batch_compress_status_n")
+    return rc, total.value, off
+
+
+def batch_emit_n_device(d_workspace, nplanes, rows, cols, bs, n, d_out, out_cap, group_planes=0, stream=None, device=None):
+    args = (d_workspace, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes), d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_emit_n(*args) if device is None else L.jpegx_batch_emit_n_on(int(device), *args), "jpegx_batch_emit_n")
+
+
+def batch_decompress_n_device(d_bytes, plane_offsets, nplanes, rows, cols, bs, n, d_workspace, d_out, out_pitch=None, mode="none",
+                              param=0.0, group_planes=0, stream=None, device=None):
+    """jpegx_batch_decompress_n (synchronises the stream once per group); plane_offsets: nplanes + 1 host integers; bands
+    stacked [nplanes * rows][out_pitch] (default cols) at d_out.  Raises JpegxError for whatever the entry refuses."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(nplanes) + 1,):
+        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    args = (d_bytes, off.ctypes.data, int(nplanes), int(rows), int(cols), int(bs), int(n), mode_of(mode), float(param),
+            int(group_planes), d_workspace, d_out, int(cols if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_batch_decompress_n(*args) if device is None else L.jpegx_batch_decompress_n_on(int(device), *args), "jpegx_batch_decompress_n")
+
+
+def batch_compress_n(bands, bs, n, mode="none", param=0.0, group_planes=0):
+    """[k][rows][cols] uint8 bands -> list of k byte strings, each what compress_band_n gives for that band.  Host
+    convenience over the device entries (upload, sizes-only compress, status, emit into a buffer of exactly the total,
+    download).  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the batch."""
+    src = bands if isinstance(bands, np.ndarray) else np.asarray(bands)
+    if src.ndim != 3 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols] uint8 bands, got %r of %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    k, rows, cols = src.shape
+    shape = (k, rows, cols, int(bs), int(n))
+    nws = batch_workspace_bytes_n(*shape, group_planes)
+    if nws == 0:                                        # the entry names the refusal, before any device is touched
+        batch_compress_n_device(1, *shape, 16, None, 0, mode, param, group_planes)
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dws = dev(src.nbytes), dev(nws)
+        din.upload(src)
+        batch_compress_n_device(din.ptr, *shape, dws.ptr, None, 0, mode, param, group_planes)
+        rc, total, off = batch_compress_status_n(dws.ptr, *shape, group_planes)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status_n")
+        dout = dev(max(1, total))
+        batch_emit_n_device(dws.ptr, *shape, dout.ptr, total, group_planes)
+        rc, total2, off = batch_compress_status_n(dws.ptr, *shape, group_planes)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit_n")
+        blob = dout.download((total,), np.uint8)
+        return [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(k)]
+
+
+def batch_decompress_n(blobs, rows, cols, bs, n, mode="none", param=0.0, group_planes=0):
+    """k byte strings (one per band, as batch_compress_n or compress_band_n return them) -> uint8 [k][rows][cols], band p what
+    decompress_band_n gives for blobs[p].  JpegxError naming a plane range for a stream the device refuses."""
+    blobs = [bytes(b) for b in blobs]
+    k = len(blobs)
+    if k < 1:
+        raise JpegxError("expected at least one band")
+    rows, cols = int(rows), int(cols)
+    off = np.zeros(k + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in blobs])
+    total = int(off[k])
+    shape = (k, rows, cols, int(bs), int(n))
+    nws = batch_decompress_workspace_bytes_n(max(total, 1), *shape, group_planes)
+    if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
+        batch_decompress_n_device(1, off, *shape, 16, 1, None, mode, param, group_planes)
+        raise JpegxError("batch_decompress_n: empty stream")
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dout = dev(total), dev(nws), dev(k * rows * cols)
+        din.upload(np.frombuffer(b"".join(blobs), dtype=np.uint8))
+        batch_decompress_n_device(din.ptr, off, *shape, dws.ptr, dout.ptr, cols, mode, param, group_planes)
+        return dout.download((k, rows, cols), np.uint8)

@@ -952,3 +952,116 @@ def _decompress_image_n(blobs, config, colour=None):
         return None
     import jpegx
     return _none_on_refusal(jpegx.decompress_image_n, blobs, *job, **_colour_kw(colour))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# many bands of one shape at once
+# ---------------------------------------------------------------------------------------------------------------------
+# compress_bands / decompress_bands_u8 take the batch road (jpegx.batch_compress_n / batch_decompress_n for dct_size other
+# than 8, jpegx.batch_compress / batch_decompress for dct_size 8: one upload, one launch chain and one download for the whole
+# stack) from this many bands on; None: the road is off and both functions are a loop over the per-band functions.  Never
+# below 2: one band is what the per-band functions are for.  All three constants are read when the functions are called.
+# Measured (profiles/batch_codec_n.json; bands of 64 x 64 at N 4 and N 16, the batch road against the loop,
+# alternating call by call on one MI355X): with 2 bands the batch loses three of four comparisons (compressing 0.21-0.22 ms
+# against 0.17-0.18 ms: its two status reads and three allocations against two pooled jobs), with 4 it wins all four
+# (0.22-0.23 against 0.37-0.38 ms compressing, 0.15-0.26 against 0.45-0.46 ms decompressing), and so at 8 and 16 (2.1-8.3x),
+# 64 (10-19x) and 4096 bands (47-55x).  The smallest measured count with no loss at or above it.
+DCTN_BATCH_MIN_PLANES = 4
+
+# ... and only for planes of at most this many samples ENTERING STEP 4 / LEAVING THE INVERSE (H * W of one band after both
+# paddings, like the DCTN_*_MIN_SAMPLES constants); None: no upper limit.  The batch pays its launches and copies once, which
+# is what many SMALL bands gain from; it also stacks the bands on the host and moves the stack through pageable memory in one
+# piece, while the per-band jobs stream through the pool's pinned staging, and that is what large bands lose by.  Measured
+# (the same record and profiles/batch_codec_n_run1.json, two runs): compressing, the batch is 13-55x faster than the loop on
+# 4096 planes of 4096 samples and 256 of 14 400, and 1.4-1.9x SLOWER on 256 planes of 262 144 samples in both runs; on 16 planes
+# of 489 600 and 12 M samples it was 2.5-5.1x slower in one run and faster in the other, in which the loop itself took 4-22x
+# longer (a shared host).  Decompressing, it is 1.3-51x faster up to 262 144 samples in both runs and lost at one
+# configuration each at 489 600 and 12 M samples in the first.  Each constant is the largest measured plane with no loss at
+# or below it in either run.
+DCTN_BATCH_COMPRESS_MAX_SAMPLES = 14400
+DCTN_BATCH_DECOMPRESS_MAX_SAMPLES = 262144
+
+
+def _batch_gate(count, samples, most):
+    """What the three constants above mean, for ``count`` bands whose planes hold ``samples`` samples each; ``most`` is
+    the direction's DCTN_BATCH_*_MAX_SAMPLES as the caller reads it from this module."""
+    gate = DCTN_BATCH_MIN_PLANES
+    return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
+
+
+def _stacked_u8(bands):
+    """The bands as one uint8 array [n][rows][cols], or None: they are not all real 2-D non-empty integer bands of one
+    shape with samples in 0..255."""
+    arrays = [b if isinstance(b, np.ndarray) else np.asarray(b) for b in bands]
+    shape = arrays[0].shape
+    if len(shape) != 2 or 0 in shape or any(a.shape != shape or a.dtype.kind not in "ui" for a in arrays):
+        return None
+    if any(a.dtype != np.uint8 and (a.min() < 0 or a.max() > 255) for a in arrays):
+        return None
+    return np.stack([a.astype(np.uint8, copy=False) for a in arrays])
+
+
+def _compress_batch(bands, config):
+    """The byte strings of the batch road, or None: the gate, the bands or the configuration do not admit it, or libjpegx
+    refused or failed -- the per-band loop then names the band and the fault."""
+    most = DCTN_BATCH_COMPRESS_MAX_SAMPLES
+    if not _batch_gate(len(bands), 0, most) or not _stock_registry() or not _device_usable():
+        return None
+    shape = np.shape(bands[0])
+    if len(shape) != 2 or 0 in shape:
+        return None
+    rows, cols = shape
+    eight = _accelerated(config)
+    job = _job_config_8(config) if eight else _compress_job_n(config, rows, cols, 0)
+    if job is None:
+        return None
+    if eight and (job[0] not in (1, 2, 4) or rows % (8 * job[0]) or cols % (8 * job[0])):
+        return None                                     # the shape and block_size limits of jpegx.batch_compress
+    h, w = (rows // int(job[0]), cols // int(job[0])) if eight else _blocked_shape(rows, cols, job[0], job[1])
+    if not _batch_gate(len(bands), h * w, most) or h * w * len(bands) > 2 ** 31 - 1:
+        return None
+    stack = _stacked_u8(bands)                          # the costly part of the vetting: last
+    if stack is None:
+        return None
+    import jpegx
+    return _none_on_refusal(jpegx.batch_compress if eight else jpegx.batch_compress_n, stack, *job)
+
+
+def compress_bands(bands, config):
+    """[compress_band(b, config) for b in bands], byte for byte.  At least DCTN_BATCH_MIN_PLANES 8-bit bands of one shape
+    whose planes hold at most DCTN_BATCH_COMPRESS_MAX_SAMPLES samples, under a configuration the device jobs admit (_job_sizes / _job_mode; dct_size 8: _job_config_8 within the shape and
+    block_size limits of jpegx.batch_compress) go to the device as ONE batch; everything else, and every refusal of the
+    batch -- a BadRleCodeError included, so that the failing band is named as before -- is that loop."""
+    bands = list(bands)
+    blobs = _compress_batch(bands, config) if bands else None
+    return blobs if blobs is not None else [compress_band(b, config) for b in bands]
+
+
+def _decompress_batch(blobs, config):
+    """uint8 [n][height][width] by the batch road, or None (see _compress_batch)."""
+    most = DCTN_BATCH_DECOMPRESS_MAX_SAMPLES
+    if not _batch_gate(len(blobs), 0, most) or not _stock_registry() or not _device_usable() or not all(_is_coded(b) for b in blobs):
+        return None
+    import jpegx
+    if _accelerated(config):
+        job = _decode_job_8(config)
+        if job is None or not _batch_gate(len(blobs), job[0] * job[1], most):
+            return None
+        planes = _none_on_refusal(jpegx.batch_decompress, blobs, *job, out="u8")
+        return None if planes is None else planes[:, :config.height, :config.width]
+    job = _decompress_job_n(config, blobs, 0)
+    if job is None:
+        return None
+    h, w = _blocked_shape(*job[:4])
+    if not _batch_gate(len(blobs), h * w, most) or h * w * len(blobs) > 2 ** 31 - 1:
+        return None
+    return _none_on_refusal(jpegx.batch_decompress_n, blobs, *job)
+
+
+def decompress_bands_u8(compression_results, config):
+    """[decompress_band_u8(r, config) for r in compression_results], sample for sample: the batch road under the conditions
+    of compress_bands (coded bytes in place of 8-bit bands; DCTN_BATCH_DECOMPRESS_MAX_SAMPLES; a whole divisor, as the decoding
+    jobs ask), else that loop."""
+    results = list(compression_results)
+    stack = _decompress_batch(results, config) if results else None
+    return list(stack) if stack is not None else [decompress_band_u8(r, config) for r in results]

@@ -451,6 +451,84 @@ int jpegx_band_plane_n(const uint8_t *d_band, int rows, int cols, ptrdiff_t pitc
 int jpegx_inflate_crop_u8(const uint8_t *d_plane, ptrdiff_t pitch, int rows, int cols, int bs, uint8_t *d_out,
                           ptrdiff_t out_pitch, jpegx_stream_t stream);
 
+/* ---- both for a STACK of equally shaped bands, any number of planes in one launch (the batch codec below) -----------------
+ * jpegx_band_planes_stacked_n (enqueue only): uint8 bands stacked [nplanes * rows][pitch] -> float64 planes stacked
+ * [nplanes * H][out_pitch], H, W from jpegx_band_shape_n.  Plane p is bit for bit what jpegx_band_plane_n makes of band p
+ * (pipeline/padding.py:8-12, subsampling.py:9-11, dct_padding.py:8-9, normalization.py:7-8): the same clamped gather, the
+ * exact integer tile sum, one division.  Every clamp is against the band's own last row and column: no read crosses from
+ * one band into its neighbour in the stack.  To convert planes p0 .. p0 + k - 1 of a larger stack alone, pass d_bands +
+ * p0 * rows * pitch and nplanes = k.  nplanes >= 1; nplanes * H * W <= 2^31 - 1; nplanes * rows <= 2^31 - 1; d_out 8-byte
+ * aligned; the other limits of jpegx_band_plane_n.
+ * jpegx_inflate_crop_stacked_u8 (enqueue only): uint8 planes stacked [nplanes * H][pitch] -- the clamped output of
+ * jpegx_inverse_fused_n on the tall plane -> bands stacked [nplanes * rows][out_pitch], out[p][y][x] = plane p[y / bs][x / bs]
+ * (pipeline/dct_padding.py:11-21, subsampling.py:13-14, padding.py:14-16 per band).  Exactly cols bytes of each of the rows
+ * rows of each band are written, nothing in the pitch slack; no read leaves [ceil(rows / bs)] x [ceil(cols / bs)] of a plane.
+ * H >= ceil(rows / bs); nplanes * rows and nplanes * H <= 2^31 - 1; the other limits of jpegx_inflate_crop_u8.          */
+int jpegx_band_planes_stacked_n(const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs, int N,
+                                double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_inflate_crop_stacked_u8(const uint8_t *d_planes, int nplanes, int H, ptrdiff_t pitch, int rows, int cols, int bs,
+                                  uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+
+/* ---- batch codec on device buffers for any DCT size: a stack of 8-bit bands -> one coded stream with a plane index, and
+ * back (csrc/jpegx_batch_n.cpp) ---------------------------------------------------------------------------------------
+ * For every band what the reference's compress_band makes of it for transform 'DCT', dct_size N in 2..32
+ * (pipeline/__init__.py:71-76: all nine steps; the entropy stage is pipeline/run_length_encoding.py:47-64 +
+ * pipeline/rle_byte_stream.py:48-59) as jpegx_host_compress_begin_band_n computes it, the bands' byte strings concatenated
+ * and a per-plane index beside them; the way back is decompress_band (pipeline/__init__.py:79-88) as
+ * jpegx_host_decompress_band_n computes it.  A batch is `nplanes` bands of rows x cols uint8 samples STACKED: one array
+ * [nplanes * rows][pitch], any pitch >= cols, no alignment asked of the bands.  One configuration per batch: bs in 1..255
+ * (else JPEGX_E_UNSUPPORTED), N in 2..32, JPEGX_Q_NONE / _DISCARD / _DIVIDE (JPEGX_Q_QTABLE is JPEGX_E_INVALID).  With H, W
+ * from jpegx_band_shape_n: nplanes * H * W <= 2^31 - 1 and nplanes * rows <= 2^31 - 1.  All of this is checked before any
+ * device work.  Everything lives in the caller's workspace (16-byte aligned).
+ * group_planes: the float64 scratch of the compressor holds that many whole planes at a time, and a decoding group holds
+ * at most that many; 0 = as many planes as stay within 2^26 samples H * W, one at least.  The SAME value goes to every call
+ * on one workspace (it places the pieces).
+ * Footprints: the compress workspace is 4 bytes per sample H * W of the batch (the int32 stream) + 8 bytes per sample of
+ * one group + jpegx_entropy_workspace_bytes_n + the index; jpegx_batch_max_bytes_n is the worst case of the coded stream,
+ * (23 N^2 + 15) / 8 bytes per block + 64.  The small-footprint road is that of the 8x8 entries: compress with d_out ==
+ * NULL (sizes only), _status_n for the total, _emit_n into exactly that many bytes.                                    */
+size_t jpegx_batch_workspace_bytes_n(int nplanes, int rows, int cols, int bs, int N, int group_planes);
+size_t jpegx_batch_max_bytes_n(int nplanes, int rows, int cols, int bs, int N);
+/* enqueue only (the first call for a size N on a device uploads that size's tables, as jpegx_forward_fused_n does): per
+ * group jpegx_band_planes_stacked_n + jpegx_forward_fused_n into the group's rows of the int32 stream, then one
+ * jpegx_entropy_sizes_n over all blocks, the plane index, the guarded emitter.  d_out == NULL (out_cap ignored): sizes
+ * only.  d_out may start at any byte.  Nothing at all is written to d_out when the stream does not fit out_cap or an
+ * amplitude is beyond 15 bits.                                                                                        */
+int jpegx_batch_compress_n(const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs, int N, int mode,
+                           double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                           jpegx_stream_t stream);
+/* synchronises the stream; the verdicts of jpegx_batch_compress_status: JPEGX_OK; JPEGX_E_INVALID = BadRleCodeError
+ * (util.py:140-149) -- nothing was written; 1 = total > out_cap of the last compress / emit on this workspace -- nothing
+ * was written, *h_total says how much is needed.  h_plane_offsets (may be NULL): nplanes + 1 byte offsets.             */
+int jpegx_batch_compress_status_n(const void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes,
+                                  unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+/* enqueue only: emit from a workspace whose sizes are in place (after a sizes-only or a too-small compress) */
+int jpegx_batch_emit_n(void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes, uint8_t *d_out,
+                       size_t out_cap, jpegx_stream_t stream);
+/* The cut of a coded batch into decoding groups, host arithmetic only, no device needed: from the first plane not yet
+ * taken, a group takes whole planes while it holds fewer than group_planes of them (0: the planes within 2^26 samples)
+ * and its bytes stay within 64 MiB, and one plane at least.  h_group_first (may be NULL; room for nplanes + 1): group g is
+ * planes h_group_first[g] .. h_group_first[g + 1] - 1, h_group_first[*ngroups] = nplanes.  JPEGX_E_INVALID for offsets that
+ * decrease and for a plane of 2^32 - 4096 bytes or more (one decode call stays below that).                             */
+int jpegx_batch_groups_n(const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols, int bs, int N,
+                         int group_planes, int *h_group_first, int *ngroups);
+/* The way back: d_bytes + plane index (a HOST array of nplanes + 1 offsets) -> uint8 bands stacked [nplanes * rows]
+ * [out_pitch], exactly cols bytes written per row.  NOT enqueue-only: per group of jpegx_batch_groups_n the bytes are
+ * copied to a dword-aligned staging area in the workspace with 16 zero bytes behind them, jpegx_entropy_decode_n decodes
+ * them, jpegx_entropy_decode_status_n reads the verdict (ONE stream synchronisation per group), jpegx_inverse_fused_n with
+ * JPEGX_F_CLAMP_U8 runs on the group's tall plane and jpegx_inflate_crop_stacked_u8 writes the group's rows of d_out.  A
+ * refused group is JPEGX_E_INVALID with its first and last plane in the message: planes of earlier groups have been
+ * written, nothing of this group or of later ones.  Refused before any device work: offsets that decrease, and a group
+ * whose bytes cannot be its blocks (fewer bytes than blocks; a lone plane of more than 64 MiB and more than (23 N^2 + 15) / 8
+ * bytes per block).
+ * A divisor that is no integer is taken as jpegx_host_decompress_band_n takes it.  d_bytes needs no alignment and no
+ * slack behind it.  The workspace (16-byte aligned) is 5 bytes per sample of one group + 13 bytes per stream byte of the
+ * longest group.                                                                                                        */
+size_t jpegx_batch_decompress_workspace_bytes_n(size_t nbytes, int nplanes, int rows, int cols, int bs, int N, int group_planes);
+int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols,
+                             int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out,
+                             ptrdiff_t out_pitch, jpegx_stream_t stream);
+
 /* ---- both for a whole pixel-interleaved picture, every band in one launch (Jpeg.compress / Jpeg.decompress,
  * pipeline/__init__.py:98-124: `image.split()` and three bands one after another, np.dstack on the way back) ----------
  * jpegx_band_planes_packed_n (enqueue only): [rows][cols][nbands] uint8 pixels, rows `pitch` BYTES apart (np.asarray(image))
@@ -845,6 +923,21 @@ int jpegx_host_compress_image_rgb_n_on(int device, const uint8_t *h_pixels, int 
                                        jpegx_alloc_fn alloc, void *user, size_t *nbytes);
 int jpegx_host_decompress_image_rgb_n_on(int device, const uint8_t *const *h_bytes, const size_t *nbytes, int rows, int cols,
                                          int bs, int N, int mode, double param, uint8_t *h_out, ptrdiff_t out_pitch);
+int jpegx_band_planes_stacked_n_on(int device, const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs,
+                                   int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_inflate_crop_stacked_u8_on(int device, const uint8_t *d_planes, int nplanes, int H, ptrdiff_t pitch, int rows,
+                                     int cols, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_batch_compress_n_on(int device, const uint8_t *d_bands, int nplanes, int rows, int cols, ptrdiff_t pitch, int bs,
+                              int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out,
+                              size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_compress_status_n_on(int device, const void *d_workspace, int nplanes, int rows, int cols, int bs, int N,
+                                     int group_planes, unsigned long long *h_total, unsigned long long *h_plane_offsets,
+                                     jpegx_stream_t stream);
+int jpegx_batch_emit_n_on(int device, void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes,
+                          uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_decompress_n_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes,
+                                int rows, int cols, int bs, int N, int mode, double param, int group_planes,
+                                void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
