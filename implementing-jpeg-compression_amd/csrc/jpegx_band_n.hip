@@ -24,10 +24,16 @@
 // And both for a STACK of equally shaped bands (the batch codec, jpegx_batch_n.cpp): jpegx_band_planes_stacked_n reads bands
 // stacked [nplanes * rows][pitch] and writes planes stacked [nplanes * H][out_pitch], plane p bit for bit what
 // jpegx_band_plane_n makes of band p, every clamp against the band's own edge; jpegx_inflate_crop_stacked_u8 is the way back.
+//
+// And both for a STACK of equally shaped PICTURES (the picture batch, jpegx_batch_n.cpp): jpegx_band_planes_packed_stacked_n
+// reads pictures stacked [npictures * rows][pitch] and writes planes stacked picture-major, plane p * nbands + k what
+// jpegx_band_plane_n makes of pixels[p][:, :, k]; jpegx_inflate_crop_pack_stacked_u8 is the way back.  With colour = 1 the
+// pixels are RGB and the planes Pillow's YCbCr (compress.py:9, decompress.py:9-10): the conversion of jpegx_colour.hip on
+// every pixel the gather reads and on every source triple the scatter replicates.
 // Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
-#include "jpegx_internal.h"
+#include "jpegx_colour_device.h"
 
 namespace {
 
@@ -369,6 +375,215 @@ void launch_inflate_crop_pack_u8(const PlanesU8 &in, size_t pitch, int rows, int
     hipLaunchKernelGGL(k_inflate_crop_pack_u8<NB>, dim3((items + 255u) / 256u), dim3(256), 0, st, in, pitch, cols, (unsigned)bs, chunks, items, out, opitch);
 }
 
+// ---- the same two steps for a STACK of equally shaped pixel-interleaved pictures: packed and stacked at once ------------
+// Pictures stacked [npictures * rows][pitch] of cols * NB bytes a row, planes stacked [npictures * NB * H][opitch] picture-
+// major: plane p * NB + k is band k of picture p.  The lanes are those of the packed kernels above with the tall row split
+// of the stacked ones: a lane's tall row tt (over npictures * H) is row y = tt - p * H of picture p = tt / H, the picture's
+// base is row p * rows of the stack, and every clamp is against the picture's OWN rows - 1 and cols - 1 -- no read reaches
+// the neighbouring picture or the pitch gap.  p * NB + k < npictures * NB and tt stay below 2^31 (the entry checks
+// npictures * NB * H * W and npictures * rows); the row offsets are size_t products.
+// COLOUR (NB == 3 only): the pixels are RGB and the planes Pillow's YCbCr.  The gather converts EVERY pixel it reads with
+// the forward tables before the pixel enters the tile sum (convert("YCbCr"), then SubSampling); the scatter converts each
+// source triple once with the inverse tables and replicates the result.  The tables are indexed per lane with the pixel's
+// own bytes, so they live in LDS (3.5 KiB forward, 2 KiB inverse), filled once per workgroup; those instantiations run
+// grid-stride under COLOUR_MAX_BLOCKS like k_colour_u8, so that a fill serves many items.  Without COLOUR the LDS array is
+// never touched and the compiler drops it: no LDS, no fill, no barrier, and the grid covers the items (one trip of the loop).
+constexpr unsigned COLOUR_MAX_BLOCKS = 1024;       // k_colour_u8's: four 256-thread workgroups per CU
+
+template <bool INVERSE>
+__device__ __forceinline__ void fill_colour_tables(int16_t *t)
+{
+    if (threadIdx.x < (INVERSE ? INV_TABLES : FWD_TABLES) * 32)
+        reinterpret_cast<uint4 *>(t)[threadIdx.x] = reinterpret_cast<const uint4 *>(INVERSE ? g_colour_inv : g_colour_fwd)[threadIdx.x];
+    __syncthreads();
+}
+
+template <int NB, bool COLOUR>
+__global__ __launch_bounds__(256) void k_band_planes_packed_stacked_n_bs1(const uint8_t *__restrict__ px, size_t pitch, int rows, int cols, int H, int W,
+                                                                          int quads, long long items, double *__restrict__ out, size_t opitch)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? FWD_TABLES * 256 : 8];
+    if (COLOUR) fill_colour_tables<false>(t);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int tt = (int)(i / quads), x0 = (int)(i - (long long)tt * quads) * 4;
+        const int p = tt / H, y = tt - p * H;
+        const uint8_t *src = px + ((size_t)p * rows + min(y, rows - 1)) * pitch;
+        unsigned v[NB][4];
+        const uint8_t *quad = src + (size_t)x0 * NB;
+        if (x0 + 4 <= cols && (reinterpret_cast<uintptr_t>(quad) & 3u) == 0) {
+            unsigned q[NB];
+#pragma unroll
+            for (int d = 0; d < NB; ++d) q[d] = reinterpret_cast<const unsigned *>(quad)[d];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int k = 0; k < NB; ++k) v[k][j] = (q[(j * NB + k) >> 2] >> (8 * ((j * NB + k) & 3))) & 0xFFu;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint8_t *one = src + (size_t)min(x0 + j, cols - 1) * NB;
+#pragma unroll
+                for (int k = 0; k < NB; ++k) v[k][j] = one[k];
+            }
+        }
+        if (COLOUR) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                unsigned o0, o1, o2;
+                colour_forward_px(t, v[0][j], v[1 % NB][j], v[2 % NB][j], o0, o1, o2);
+                v[0][j] = o0; v[1 % NB][j] = o1; v[2 % NB][j] = o2;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            double *dst = out + ((size_t)(p * NB + k) * H + y) * opitch + x0;
+            if (x0 + 4 <= W && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+                reinterpret_cast<double2 *>(dst)[0] = make_double2((double)v[k][0], (double)v[k][1]);
+                reinterpret_cast<double2 *>(dst)[1] = make_double2((double)v[k][2], (double)v[k][3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < W) dst[j] = (double)v[k][j];
+            }
+        }
+    }
+}
+
+// one pixel of the walk below into the NB sums, converted first where COLOUR says so
+template <int NB, bool COLOUR>
+__device__ __forceinline__ void add_pixel(const int16_t *t, const uint8_t *one, unsigned (&s)[NB])
+{
+    if (COLOUR) {
+        unsigned o0, o1, o2;
+        colour_forward_px(t, one[0], one[1 % NB], one[2 % NB], o0, o1, o2);
+        s[0] += o0; s[1 % NB] += o1; s[2 % NB] += o2;
+    } else {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s[k] += one[k];
+    }
+}
+
+template <int NB, bool COLOUR>
+__global__ __launch_bounds__(256) void k_band_planes_packed_stacked_n(const uint8_t *__restrict__ px, size_t pitch, int rows, int cols, int bs, int prows,
+                                                                      int pcols, int H, int W, long long items, double *__restrict__ out, size_t opitch)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? FWD_TABLES * 256 : 8];
+    if (COLOUR) fill_colour_tables<false>(t);
+    const double area = (double)(bs * bs);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int tt = (int)(i / W), x = (int)(i - (long long)tt * W);
+        const int p = tt / H, y = tt - p * H;
+        const int r0 = min(y, prows - 1) * bs, c0 = min(x, pcols - 1) * bs;  // r0 < rows, c0 < cols: the tile starts inside picture p
+        const uint8_t *pic = px + (size_t)p * rows * pitch;                 // picture p's first row
+        unsigned s[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s[k] = 0;
+        const int rlast = rows - 1 - r0, clast = cols - 1 - c0;            // both >= 0; the clamps below never add past rows - 1, cols - 1
+        if (bs <= clast + 1) {                                              // the tile's columns are all there: no clamp per pixel
+            for (int u = 0; u < bs; ++u) {
+                const uint8_t *q = pic + (size_t)(r0 + min(u, rlast)) * pitch + (size_t)c0 * NB;
+                for (int w = 0; w < bs; ++w) add_pixel<NB, COLOUR>(t, q + w * NB, s);
+            }
+        } else {
+            for (int u = 0; u < bs; ++u) {
+                const uint8_t *q = pic + (size_t)(r0 + min(u, rlast)) * pitch + (size_t)c0 * NB;
+                for (int w = 0; w < bs; ++w) add_pixel<NB, COLOUR>(t, q + min(w, clast) * NB, s);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) out[((size_t)(p * NB + k) * H + y) * opitch + x] = (double)s[k] / area;
+    }
+}
+
+// The way back for the stack of pictures: k_inflate_crop_pack_u8's lane (PIX consecutive pixels of one output row, whole
+// 16-byte units) with the tall output row yy split into p = yy / rows and y = yy - p * rows; band k's source row is
+// (p * NB + k) * H + y / bs, and y / bs <= (rows - 1) / bs < H, so no read leaves plane (p, k).  The NB source bytes are loaded
+// (and, with COLOUR, converted: once per source triple) when the (quotient, remainder) pair enters a source column and only
+// for x < cols.  items can pass 2^32 (npictures * rows * chunks), so the index is 64 bits wide; yy < 2^31.
+template <int NB, bool COLOUR>
+__global__ __launch_bounds__(256) void k_inflate_crop_pack_stacked_u8(const uint8_t *__restrict__ planes, size_t pitch, int H, int rows, int cols, unsigned bs,
+                                                                      unsigned chunks, unsigned long long items, uint8_t *__restrict__ out, size_t opitch)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    constexpr int UNIT = NB == 3 ? 48 : 16, PIX = UNIT / NB;
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? INV_TABLES * 256 : 8];
+    if (COLOUR) fill_colour_tables<true>(t);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * 256u) {
+        const unsigned yy = (unsigned)(i / chunks), x0 = (unsigned)(i - (unsigned long long)yy * chunks) * (unsigned)PIX;
+        const unsigned p = yy / (unsigned)rows, y = yy - p * (unsigned)rows;
+        const uint8_t *src = planes + ((size_t)p * NB * H + y / bs) * pitch;      // band 0 of picture p; band k lies k * H rows on
+        const size_t band = (size_t)H * pitch;
+        unsigned q = x0 / bs, r = x0 - q * bs;
+        const int left = cols - (int)x0;                                   // >= 1: pixels of this lane inside the row
+        unsigned v[NB], w[UNIT / 4];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) v[k] = 0;
+#pragma unroll
+        for (int d = 0; d < UNIT / 4; ++d) w[d] = 0;
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            if (j < left) {
+                if (j == 0 || r == 0) {
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) v[k] = src[k * band + q];
+                    if (COLOUR) {
+                        unsigned o0, o1, o2;
+                        colour_inverse_px(t, v[0], v[1 % NB], v[2 % NB], o0, o1, o2);
+                        v[0] = o0; v[1 % NB] = o1; v[2 % NB] = o2;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < NB; ++k) w[(j * NB + k) >> 2] |= v[k] << (8 * ((j * NB + k) & 3));
+                if (++r == bs) { r = 0; ++q; }
+            }
+        }
+        uint8_t *dst = out + (size_t)yy * opitch + (size_t)x0 * NB;
+        if (left >= PIX && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+#pragma unroll
+            for (int d = 0; d < UNIT / 16; ++d) reinterpret_cast<uint4 *>(dst)[d] = make_uint4(w[4 * d], w[4 * d + 1], w[4 * d + 2], w[4 * d + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < UNIT; ++j)
+                if (j / NB < left) dst[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
+// grid of an instantiation: all the items without COLOUR, at most COLOUR_MAX_BLOCKS workgroups with it
+template <bool COLOUR>
+unsigned stacked_blocks(unsigned long long items)
+{
+    const unsigned long long blocks = (items + 255u) / 256u;               // below 2^31: the entries check it
+    return COLOUR && blocks > COLOUR_MAX_BLOCKS ? COLOUR_MAX_BLOCKS : (unsigned)blocks;
+}
+
+template <int NB, bool COLOUR>
+void launch_band_planes_packed_stacked_n(const uint8_t *px, size_t pitch, int npictures, int rows, int cols, int bs, int H, int W, double *out, size_t opitch,
+                                         hipStream_t st)
+{
+    const long long tall = (long long)npictures * H;                        // below 2^31: npictures * NB * H * W is
+    if (bs == 1) {
+        const int quads = (W + 3) / 4;
+        const long long items = tall * quads;
+        hipLaunchKernelGGL((k_band_planes_packed_stacked_n_bs1<NB, COLOUR>), dim3(stacked_blocks<COLOUR>((unsigned long long)items)), dim3(256), 0, st, px,
+                           pitch, rows, cols, H, W, quads, items, out, opitch);
+    } else {
+        const long long items = tall * W;
+        hipLaunchKernelGGL((k_band_planes_packed_stacked_n<NB, COLOUR>), dim3(stacked_blocks<COLOUR>((unsigned long long)items)), dim3(256), 0, st, px, pitch,
+                           rows, cols, bs, (int)(((long long)rows + bs - 1) / bs), (int)(((long long)cols + bs - 1) / bs), H, W, items, out, opitch);
+    }
+}
+
+template <int NB, bool COLOUR>
+void launch_inflate_crop_pack_stacked_u8(const uint8_t *planes, size_t pitch, int H, int rows, int cols, int bs, unsigned chunks, unsigned long long items,
+                                         uint8_t *out, size_t opitch, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_inflate_crop_pack_stacked_u8<NB, COLOUR>), dim3(stacked_blocks<COLOUR>(items)), dim3(256), 0, st, planes, pitch, H, rows, cols,
+                       (unsigned)bs, chunks, items, out, opitch);
+}
+
 }  // namespace
 
 extern "C" {
@@ -523,6 +738,67 @@ int jpegx_inflate_crop_pack_u8(const uint8_t *const *d_planes, int nbands, ptrdi
     case 2: launch_inflate_crop_pack_u8<2>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
     case 3: launch_inflate_crop_pack_u8<3>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
     default: launch_inflate_crop_pack_u8<4>(in, (size_t)pitch, rows, cols, bs, d_out, (size_t)out_pitch, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_band_planes_packed_stacked_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N,
+                                       double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_pixels || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (npictures < 1) return fail(JPEGX_E_INVALID, "band_planes_packed_stacked_n: the picture count must be positive");
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) return fail(JPEGX_E_INVALID, "band_planes_packed_stacked_n takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    if (colour != 0 && colour != 1) return fail(JPEGX_E_INVALID, "band_planes_packed_stacked_n: colour must be 0 (as they are) or 1 (RGB pixels, YCbCr planes)");
+    if (colour == 1 && nbands != 3) return fail(JPEGX_E_INVALID, "band_planes_packed_stacked_n: the colour conversion needs three bands");
+    int H = 0, W = 0;
+    const int rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W);
+    if (rc) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if ((long long)H * W > 0x7FFFFFFFLL / nbands / npictures) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one stack of planes");
+    if ((long long)rows * npictures > INT_MAX) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 rows in one stack of pictures");
+    if (pitch < (ptrdiff_t)cols * nbands || out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if (reinterpret_cast<uintptr_t>(d_out) % 8) return fail(JPEGX_E_INVALID, "band_planes_packed_stacked_n: misaligned output pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ip = (size_t)pitch, op = (size_t)out_pitch;
+    if (colour) launch_band_planes_packed_stacked_n<3, true>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st);
+    else switch (nbands) {
+    case 1: launch_band_planes_packed_stacked_n<1, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
+    case 2: launch_band_planes_packed_stacked_n<2, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
+    case 3: launch_band_planes_packed_stacked_n<3, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
+    default: launch_band_planes_packed_stacked_n<4, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_inflate_crop_pack_stacked_u8(const uint8_t *d_planes, int npictures, int nbands, int H, ptrdiff_t pitch, int rows, int cols, int bs, int colour,
+                                       uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_planes || !d_out) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (npictures < 1) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: the picture count must be positive");
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8 takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    if (colour != 0 && colour != 1) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: colour must be 0 (as they are) or 1 (YCbCr planes, RGB pixels)");
+    if (colour == 1 && nbands != 3) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: the colour conversion needs three bands");
+    if (rows < 1 || cols < 1) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: rows and cols must be at least 1");
+    if (bs < 1 || bs > 255) return fail(JPEGX_E_UNSUPPORTED, "inflate_crop_pack_stacked_u8: block_size must be in 1..255");
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if ((long long)H < ((long long)rows + bs - 1) / bs) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: the planes are lower than the pooled band");
+    if ((long long)rows * npictures > INT_MAX || (long long)H * nbands * npictures > INT_MAX)
+        return fail(JPEGX_E_INVALID, "more than 2^31 - 1 rows in one stack");
+    if (pitch < (ptrdiff_t)(((long long)cols + bs - 1) / bs) || out_pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    const unsigned pix = (nbands == 3 ? 48u : 16u) / (unsigned)nbands;
+    const unsigned chunks = ((unsigned)cols + pix - 1u) / pix;
+    const unsigned long long items = (unsigned long long)npictures * rows * chunks;
+    if ((items + 255u) / 256u > 0x7FFFFFFFull) return fail(JPEGX_E_INVALID, "inflate_crop_pack_stacked_u8: more than 2^39 lanes in one launch");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ip = (size_t)pitch, op = (size_t)out_pitch;
+    if (colour) launch_inflate_crop_pack_stacked_u8<3, true>(d_planes, ip, H, rows, cols, bs, chunks, items, d_out, op, st);
+    else switch (nbands) {
+    case 1: launch_inflate_crop_pack_stacked_u8<1, false>(d_planes, ip, H, rows, cols, bs, chunks, items, d_out, op, st); break;
+    case 2: launch_inflate_crop_pack_stacked_u8<2, false>(d_planes, ip, H, rows, cols, bs, chunks, items, d_out, op, st); break;
+    case 3: launch_inflate_crop_pack_stacked_u8<3, false>(d_planes, ip, H, rows, cols, bs, chunks, items, d_out, op, st); break;
+    default: launch_inflate_crop_pack_stacked_u8<4, false>(d_planes, ip, H, rows, cols, bs, chunks, items, d_out, op, st); break;
     }
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;

@@ -12,6 +12,12 @@
 // into the right rows of the batch's int32 stream; the entropy workspace is the layout of jpegx_entropy_ws.h for both
 // stages, so the plane index is k_plane_index of jpegx_entropy.hip as it is; and the decoder has no levels.  Nothing is
 // allocated here: everything lives in the caller's workspace.
+//
+// A stack of pixel-interleaved PICTURES (Jpeg.compress / Jpeg.decompress, pipeline/__init__.py:98-124; with colour = 1 the
+// conversions of compress.py:9 and decompress.py:9-10 around them) is the same batch of nbands * npictures planes in
+// picture-major order: the _pictures_ entries differ in the gather and the scatter (jpegx_band_planes_packed_stacked_n,
+// jpegx_inflate_crop_pack_stacked_u8), in groups that are whole pictures, and in a staging area for a lone picture's worst
+// case; shape, workspace, status, emit and the cut itself are the band entries' code.
 #include <limits.h>
 
 #include <vector>
@@ -103,18 +109,19 @@ struct DecompressWs {
     size_t bytes;
 };
 
-// the longest stream one group can hold, given the whole stream's length
-unsigned long long group_bytes_max(size_t nbytes, int N, const Shape &s)
+// the longest stream one group can hold, given the whole stream's length; a group holds at least one unit of `unit` planes
+// (a band: 1, a picture: its bands)
+unsigned long long group_bytes_max(size_t nbytes, int N, const Shape &s, int unit)
 {
-    const unsigned long long lone = (unsigned long long)s.nb * max_block_bytes(N);
+    const unsigned long long lone = (unsigned long long)s.nb * unit * max_block_bytes(N);
     unsigned long long b = lone > GROUP_BYTES ? lone : GROUP_BYTES;
     if (b > MAX_STREAM - 1) b = MAX_STREAM - 1;
     return nbytes < b ? nbytes : b;
 }
 
-DecompressWs carve_decompress(void *ws, size_t nbytes, int N, const Shape &s)
+DecompressWs carve_decompress(void *ws, size_t nbytes, int N, const Shape &s, int unit)
 {
-    const size_t bmax = (size_t)group_bytes_max(nbytes, N, s);
+    const size_t bmax = (size_t)group_bytes_max(nbytes, N, s, unit);
     unsigned char *p = static_cast<unsigned char *>(ws);
     DecompressWs d;
     size_t o = 0;
@@ -126,9 +133,9 @@ DecompressWs carve_decompress(void *ws, size_t nbytes, int N, const Shape &s)
     return d;
 }
 
-// The cut: the next group is whole planes while it holds fewer than gp planes and the stream stays within GROUP_BYTES, one
-// plane at least.  first[g] .. first[g + 1] - 1 are group g's planes.
-int cut_groups(const unsigned long long *off, int nplanes, const Shape &s, std::vector<int> *first)
+// The cut: the next group is whole units (of `unit` planes each: a band is 1, a picture its bands) while it holds fewer than
+// gp planes and the stream stays within GROUP_BYTES, one unit at least.  first[g] .. first[g + 1] - 1 are group g's units.
+int cut_groups(const unsigned long long *off, int nplanes, const Shape &s, int unit, const char *unit_name, std::vector<int> *first)
 {
     for (int p = 0; p < nplanes; ++p) {
         if (off[p + 1] < off[p]) {
@@ -138,19 +145,45 @@ int cut_groups(const unsigned long long *off, int nplanes, const Shape &s, std::
         }
     }
     first->clear();
-    for (int p0 = 0; p0 < nplanes;) {
+    const int n = nplanes / unit, cap = s.gp / unit;
+    for (int p0 = 0; p0 < n;) {
         int p1 = p0 + 1;
-        while (p1 < nplanes && p1 - p0 < s.gp && off[p1 + 1] - off[p0] <= GROUP_BYTES) ++p1;
-        if (off[p1] - off[p0] >= MAX_STREAM) {           // only a lone plane can: one decode call is below 2^32 - 4096 bytes
+        while (p1 < n && p1 - p0 < cap && off[(size_t)(p1 + 1) * unit] - off[(size_t)p0 * unit] <= GROUP_BYTES) ++p1;
+        const unsigned long long held = off[(size_t)p1 * unit] - off[(size_t)p0 * unit];
+        if (held >= MAX_STREAM) {                        // only a lone unit can: one decode call is below 2^32 - 4096 bytes
             char buf[160];
-            snprintf(buf, sizeof(buf), "batch_n: plane %d holds %llu bytes, one decode call takes fewer than 2^32 - 4096", p0, off[p1] - off[p0]);
+            snprintf(buf, sizeof(buf), "batch_n: %s %d holds %llu bytes, one decode call takes fewer than 2^32 - 4096", unit_name, p0, held);
             return fail(JPEGX_E_INVALID, buf);
         }
         first->push_back(p0);
         p0 = p1;
     }
-    first->push_back(nplanes);
+    first->push_back(n);
     return JPEGX_OK;
+}
+
+// shape of a batch of pictures: the band batch of nbands * npictures planes, groups of whole pictures
+int picture_shape(const char *who, int npictures, int nbands, int rows, int cols, int bs, int N, int colour, int group_planes, Shape *s)
+{
+    char buf[200];
+    if (npictures <= 0) {
+        snprintf(buf, sizeof(buf), "%s: the picture count must be positive", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) {
+        snprintf(buf, sizeof(buf), "%s takes 1..JPEGX_MAX_IMAGE_BANDS bands", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if ((colour != 0 && colour != 1) || (colour == 1 && nbands != 3)) {
+        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (group_planes <= 0 || group_planes % nbands) {
+        snprintf(buf, sizeof(buf), "%s: group_planes must be a positive multiple of the band count (jpegx_batch_group_planes_pictures_n)", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (npictures > INT_MAX / nbands) return fail(JPEGX_E_INVALID, "batch_n: 2^31 or more coefficients in one batch");
+    return batch_shape(npictures * nbands, rows, cols, bs, N, group_planes, s);      // gp: min of two multiples of nbands
 }
 
 }  // namespace
@@ -237,7 +270,7 @@ int jpegx_batch_groups_n(const unsigned long long *h_plane_offsets, int nplanes,
     int rc = batch_shape(nplanes, rows, cols, bs, N, group_planes, &s);
     if (rc) return rc;
     std::vector<int> first;
-    if ((rc = cut_groups(h_plane_offsets, nplanes, s, &first))) return rc;
+    if ((rc = cut_groups(h_plane_offsets, nplanes, s, 1, "plane", &first))) return rc;
     *ngroups = (int)first.size() - 1;
     if (h_group_first)
         for (size_t g = 0; g < first.size(); ++g) h_group_first[g] = first[g];
@@ -248,7 +281,7 @@ size_t jpegx_batch_decompress_workspace_bytes_n(size_t nbytes, int nplanes, int 
 {
     Shape s;
     if (nbytes == 0 || batch_shape(nplanes, rows, cols, bs, N, group_planes, &s)) return 0;
-    return carve_decompress(nullptr, nbytes, N, s).bytes;
+    return carve_decompress(nullptr, nbytes, N, s, 1).bytes;
 }
 
 int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols, int bs, int N,
@@ -261,11 +294,11 @@ int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h
     if (out_pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "batch_decompress_n: output pitch smaller than the row");
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_decompress_n: workspace must be 16-byte aligned");
     std::vector<int> first;
-    if ((rc = cut_groups(h_plane_offsets, nplanes, s, &first))) return rc;
+    if ((rc = cut_groups(h_plane_offsets, nplanes, s, 1, "plane", &first))) return rc;
     const int ngroups = (int)first.size() - 1;
     char where[320];
     const size_t total = (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]);
-    const unsigned long long bmax = group_bytes_max(total, N, s);          // what the staging area holds
+    const unsigned long long bmax = group_bytes_max(total, N, s, 1);         // what the staging area holds
     for (int g = 0; g < ngroups; ++g) {                  // a block is 1 .. max_block_bytes bytes: refused before any device work
         const unsigned long long gbytes = h_plane_offsets[first[g + 1]] - h_plane_offsets[first[g]];
         const long long gblocks = s.nb * (first[g + 1] - first[g]);
@@ -275,7 +308,7 @@ int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h
             return fail(JPEGX_E_INVALID, where);
         }
     }
-    const DecompressWs w = carve_decompress(d_workspace, total, N, s);
+    const DecompressWs w = carve_decompress(d_workspace, total, N, s, 1);
     hipStream_t st = (hipStream_t)stream;
     for (int g = 0; g < ngroups; ++g) {
         const int p0 = first[g], np = first[g + 1] - p0;
@@ -294,6 +327,111 @@ int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h
         if (rc) return rc;
         if ((rc = jpegx_inverse_fused_n(w.zz, np * s.H, s.W, N, mode, param, JPEGX_F_CLAMP_U8, w.plane, s.W, stream)) ||
             (rc = jpegx_inflate_crop_stacked_u8(w.plane, np, s.H, s.W, rows, cols, bs, d_out + (size_t)p0 * rows * (size_t)out_pitch, out_pitch, stream)))
+            return rc;
+    }
+    return JPEGX_OK;
+}
+
+// ---- a stack of PICTURES: the band batch of nbands * npictures planes, picture-major, cut on picture boundaries --------
+int jpegx_batch_group_planes_pictures_n(int nbands, int rows, int cols, int bs, int N)
+{
+    int H = 0, W = 0;
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS || jpegx_band_shape_n(rows, cols, bs, N, &H, &W)) return 0;
+    const long long k = GROUP_SAMPLES / ((long long)H * W) / nbands * nbands;
+    return k < nbands ? nbands : (int)k;                 // k <= 2^26 / 4
+}
+
+int jpegx_batch_compress_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N,
+                                    int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream)
+{
+    if (!d_pixels || !d_workspace) return fail(JPEGX_E_INVALID, "batch_compress_pictures_n: null device pointer");
+    Shape s;
+    int rc = picture_shape("batch_compress_pictures_n", npictures, nbands, rows, cols, bs, N, colour, group_planes, &s);
+    if (rc || (rc = check_quantiser(mode, param))) return rc;
+    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_compress_pictures_n: pitch smaller than the row");
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_compress_pictures_n: workspace must be 16-byte aligned");
+    const int nplanes = npictures * nbands, gpics = s.gp / nbands;
+    const CompressWs c = carve_compress(d_workspace, nplanes, N, s);
+    for (int q0 = 0; q0 < npictures; q0 += gpics) {
+        const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
+        if ((rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, c.planes,
+                                                     s.W, stream)) ||
+            (rc = jpegx_forward_fused_n(c.planes, nq * nbands * s.H, s.W, s.W, N, mode, param, c.zz + (size_t)q0 * nbands * s.samples, stream)))
+            return rc;
+    }
+    if ((rc = jpegx_entropy_sizes_n(c.zz, s.nb * nplanes, N * N, c.ews, stream))) return rc;
+    return enqueue_index_and_emit(c, nplanes, N, s, d_out, out_cap, stream);
+}
+
+int jpegx_batch_groups_pictures_n(const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs, int N,
+                                  int group_planes, int *h_group_first, int *ngroups)
+{
+    if (!h_plane_offsets || !ngroups) return fail(JPEGX_E_INVALID, "batch_groups_pictures_n: null pointer");
+    Shape s;
+    int rc = picture_shape("batch_groups_pictures_n", npictures, nbands, rows, cols, bs, N, 0, group_planes, &s);
+    if (rc) return rc;
+    std::vector<int> first;
+    if ((rc = cut_groups(h_plane_offsets, npictures * nbands, s, nbands, "picture", &first))) return rc;
+    *ngroups = (int)first.size() - 1;
+    if (h_group_first)
+        for (size_t g = 0; g < first.size(); ++g) h_group_first[g] = first[g];
+    return JPEGX_OK;
+}
+
+size_t jpegx_batch_decompress_pictures_workspace_bytes_n(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs, int N, int group_planes)
+{
+    Shape s;
+    if (nbytes == 0 || picture_shape("batch_decompress_pictures_workspace_bytes_n", npictures, nbands, rows, cols, bs, N, 0, group_planes, &s)) return 0;
+    return carve_decompress(nullptr, nbytes, N, s, nbands).bytes;
+}
+
+int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols,
+                                      int bs, int N, int mode, double param, int colour, int group_planes, void *d_workspace, uint8_t *d_out,
+                                      ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_bytes || !h_plane_offsets || !d_workspace || !d_out) return fail(JPEGX_E_INVALID, "batch_decompress_pictures_n: null pointer");
+    Shape s;
+    int rc = picture_shape("batch_decompress_pictures_n", npictures, nbands, rows, cols, bs, N, colour, group_planes, &s);
+    if (rc || (rc = check_quantiser(mode, param))) return rc;
+    if (out_pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_decompress_pictures_n: output pitch smaller than the row");
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_decompress_pictures_n: workspace must be 16-byte aligned");
+    const int nplanes = npictures * nbands;
+    std::vector<int> first;                              // pictures
+    if ((rc = cut_groups(h_plane_offsets, nplanes, s, nbands, "picture", &first))) return rc;
+    const int ngroups = (int)first.size() - 1;
+    char where[320];
+    const size_t total = (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]);
+    const unsigned long long bmax = group_bytes_max(total, N, s, nbands);   // what the staging area holds
+    for (int g = 0; g < ngroups; ++g) {                  // a block is 1 .. max_block_bytes bytes: refused before any device work
+        const unsigned long long gbytes = h_plane_offsets[(size_t)first[g + 1] * nbands] - h_plane_offsets[(size_t)first[g] * nbands];
+        const long long gblocks = s.nb * nbands * (first[g + 1] - first[g]);
+        if (gbytes < (unsigned long long)gblocks || gbytes > bmax) {
+            snprintf(where, sizeof(where), "batch_decompress_pictures_n: pictures %d..%d: %llu bytes cannot be their %lld blocks", first[g], first[g + 1] - 1,
+                     gbytes, gblocks);
+            return fail(JPEGX_E_INVALID, where);
+        }
+    }
+    const DecompressWs w = carve_decompress(d_workspace, total, N, s, nbands);
+    hipStream_t st = (hipStream_t)stream;
+    for (int g = 0; g < ngroups; ++g) {
+        const int q0 = first[g], nq = first[g + 1] - q0, np = nq * nbands;
+        const unsigned long long start = h_plane_offsets[(size_t)q0 * nbands];
+        const size_t gbytes = (size_t)(h_plane_offsets[(size_t)(q0 + nq) * nbands] - start);
+        const long long gblocks = s.nb * np;
+        // the group's bytes, dword aligned and with zeros behind them, as the decoder wants them
+        HIP_TRY(hipMemsetAsync(w.stage + (gbytes & ~(size_t)3), 0, 16 + (gbytes & 3), st));
+        HIP_TRY(hipMemcpyAsync(w.stage, d_bytes + start, gbytes, hipMemcpyDeviceToDevice, st));
+        if ((rc = jpegx_entropy_decode_n(w.stage, gbytes, gblocks, N * N, w.dws, w.zz, stream))) return rc;
+        rc = jpegx_entropy_decode_status_n(w.dws, stream);      // synchronises: nothing of a refused group is written
+        if (rc == JPEGX_E_INVALID) {
+            snprintf(where, sizeof(where), "batch_decompress_pictures_n: pictures %d..%d: their %llu bytes are not %lld well-formed blocks (%.120s)", q0,
+                     q0 + nq - 1, (unsigned long long)gbytes, gblocks, jpegx_last_error());
+            return fail(JPEGX_E_INVALID, where);
+        }
+        if (rc) return rc;
+        if ((rc = jpegx_inverse_fused_n(w.zz, np * s.H, s.W, N, mode, param, JPEGX_F_CLAMP_U8, w.plane, s.W, stream)) ||
+            (rc = jpegx_inflate_crop_pack_stacked_u8(w.plane, nq, nbands, s.H, s.W, rows, cols, bs, colour, d_out + (size_t)q0 * rows * (size_t)out_pitch,
+                                                     out_pitch, stream)))
             return rc;
     }
     return JPEGX_OK;

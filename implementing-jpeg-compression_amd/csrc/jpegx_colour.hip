@@ -4,23 +4,12 @@
 // tables (include/jpegx_colour_tables.inc) are recovered from Pillow's outputs and checked against it on all 2^24 inputs by
 // tests/golden/make_colour_tables.py, the formulas are those of tests/colour_model.py.  Part of libjpegx.so (C ABI:
 // include/jpegx.h).
-#include "jpegx_internal.h"
-
-#include "../../include/jpegx_colour_tables.inc"
+#include "jpegx_colour_device.h"      // the tables and the two per-pixel formulas, shared with jpegx_band_n.hip
 
 namespace {
 
-constexpr int FWD_TABLES = 7, INV_TABLES = 4;      // y_r y_g y_b cb_r cb_g cr_g cr_b | d_r g_cb g_cr d_b, 256 int16 each
-
-__device__ __attribute__((aligned(16))) const int16_t g_colour_fwd[FWD_TABLES * 256] = {
-    JPEGX_COLOUR_Y_R JPEGX_COLOUR_Y_G JPEGX_COLOUR_Y_B JPEGX_COLOUR_CB_R JPEGX_COLOUR_CB_G JPEGX_COLOUR_CR_G JPEGX_COLOUR_CR_B};
-__device__ __attribute__((aligned(16))) const int16_t g_colour_inv[INV_TABLES * 256] = {
-    JPEGX_COLOUR_D_R JPEGX_COLOUR_G_CB JPEGX_COLOUR_G_CR JPEGX_COLOUR_D_B};
-
 constexpr int PIX = 16, UNIT = 48;                 // a lane's pixels and their bytes: the fewest that are whole 16-byte units
 constexpr unsigned MAX_BLOCKS = 1024;              // four 256-thread workgroups per CU walk the chunks: the table fill amortises
-
-__device__ __forceinline__ unsigned clamp_u8(int v) { return (unsigned)min(max(v, 0), 255); }
 
 // [rows][cols][3] uint8, rows in_pitch / out_pitch bytes apart.  A lane owns PIX consecutive pixels of one row, like
 // k_inflate_crop_pack_u8's: three 16-byte loads where its pixels are all inside the row and the address is 16-byte aligned,
@@ -65,15 +54,8 @@ __global__ __launch_bounds__(256) void k_colour_u8(const uint8_t *in, size_t in_
             const unsigned a = (w[(3 * p) >> 2] >> (8 * ((3 * p) & 3))) & 0xFFu, b = (w[(3 * p + 1) >> 2] >> (8 * ((3 * p + 1) & 3))) & 0xFFu,
                            c = (w[(3 * p + 2) >> 2] >> (8 * ((3 * p + 2) & 3))) & 0xFFu;
             unsigned o0, o1, o2;
-            if (INVERSE) {                                                  // (a, b, c) = (Y, Cb, Cr)
-                o0 = clamp_u8((int)a + t[c]);
-                o1 = clamp_u8((int)a + ((t[256 + b] + t[512 + c]) >> 6));
-                o2 = clamp_u8((int)a + t[768 + b]);
-            } else {                                                        // (a, b, c) = (R, G, B)
-                o0 = (unsigned)((t[a] + t[256 + b] + t[512 + c]) >> 6) & 0xFFu;
-                o1 = (unsigned)(((t[768 + a] + t[1024 + b] + 32 * (int)c) >> 6) + 128) & 0xFFu;
-                o2 = (unsigned)(((32 * (int)a + t[1280 + b] + t[1536 + c]) >> 6) + 128) & 0xFFu;
-            }
+            if (INVERSE) colour_inverse_px(t, a, b, c, o0, o1, o2);         // (a, b, c) = (Y, Cb, Cr)
+            else colour_forward_px(t, a, b, c, o0, o1, o2);                 // (a, b, c) = (R, G, B)
             v[(3 * p) >> 2] |= o0 << (8 * ((3 * p) & 3));
             v[(3 * p + 1) >> 2] |= o1 << (8 * ((3 * p + 1) & 3));
             v[(3 * p + 2) >> 2] |= o2 << (8 * ((3 * p + 2) & 3));

@@ -155,3 +155,11 @@ JPEGX_ON(jpegx_batch_emit_n, (int device, void *d_workspace, int nplanes, int ro
          (d_workspace, nplanes, rows, cols, bs, N, group_planes, d_out, out_cap, stream))
 JPEGX_ON(jpegx_batch_decompress_n, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols, int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
          (d_bytes, h_plane_offsets, nplanes, rows, cols, bs, N, mode, param, group_planes, d_workspace, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_band_planes_packed_stacked_n, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, N, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_inflate_crop_pack_stacked_u8, (int device, const uint8_t *d_planes, int npictures, int nbands, int H, ptrdiff_t pitch, int rows, int cols, int bs, int colour, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_planes, npictures, nbands, H, pitch, rows, cols, bs, colour, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_batch_compress_pictures_n, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, N, mode, param, group_planes, d_workspace, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_decompress_pictures_n, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs, int N, int mode, double param, int colour, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_bytes, h_plane_offsets, npictures, nbands, rows, cols, bs, N, mode, param, colour, group_planes, d_workspace, d_out, out_pitch, stream))

@@ -197,6 +197,13 @@ SIGNATURES = {
     "jpegx_batch_groups_n": [_vp, _int, _int, _int, _int, _int, _int, _vp, _c.POINTER(_int)],
     "jpegx_batch_decompress_workspace_bytes_n": [_sz, _int, _int, _int, _int, _int, _int],
     "jpegx_batch_decompress_n": [_vp, _vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _vp, _vp, _pd, _vp],
+    "jpegx_band_planes_packed_stacked_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_inflate_crop_pack_stacked_u8": [_vp, _int, _int, _int, _pd, _int, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_batch_group_planes_pictures_n": [_int, _int, _int, _int, _int],
+    "jpegx_batch_compress_pictures_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
+    "jpegx_batch_groups_pictures_n": [_vp, _int, _int, _int, _int, _int, _int, _int, _vp, _c.POINTER(_int)],
+    "jpegx_batch_decompress_pictures_workspace_bytes_n": [_sz, _int, _int, _int, _int, _int, _int, _int],
+    "jpegx_batch_decompress_pictures_n": [_vp, _vp, _int, _int, _int, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _pd, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -224,12 +231,14 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_ycbcr_to_rgb_u8", "jpegx_host_compress_image_rgb", "jpegx_host_decompress_image_rgb",
               "jpegx_host_compress_image_rgb_n", "jpegx_host_decompress_image_rgb_n", "jpegx_band_planes_stacked_n",
               "jpegx_inflate_crop_stacked_u8", "jpegx_batch_compress_n", "jpegx_batch_compress_status_n", "jpegx_batch_emit_n",
-              "jpegx_batch_decompress_n"):
+              "jpegx_batch_decompress_n", "jpegx_band_planes_packed_stacked_n", "jpegx_inflate_crop_pack_stacked_u8",
+              "jpegx_batch_compress_pictures_n", "jpegx_batch_decompress_pictures_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz, "jpegx_batch_workspace_bytes_n": _sz,
-            "jpegx_batch_max_bytes_n": _sz, "jpegx_batch_decompress_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_max_bytes_n": _sz, "jpegx_batch_decompress_workspace_bytes_n": _sz,
+            "jpegx_batch_decompress_pictures_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -1730,3 +1739,157 @@ def batch_decompress_n(blobs, rows, cols, bs, n, mode="none", param=0.0, group_p
         din.upload(np.frombuffer(b"".join(blobs), dtype=np.uint8))
         batch_decompress_n_device(din.ptr, off, *shape, dws.ptr, dout.ptr, cols, mode, param, group_planes)
         return dout.download((k, rows, cols), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the batch codec for whole pictures at any DCT size: a stack of pixel-interleaved pictures -> the coded bytes of every
+# band, picture-major, and back.  A stack of k pictures of nb bands is the band batch above of nb * k planes: workspace,
+# worst case, status and emit are batch_workspace_bytes_n / batch_max_bytes_n / batch_compress_status_n / batch_emit_n_device
+# with that plane count.  dct_size 8 is not served (its batch entries take block_size 1, 2, 4 and whole tiles only).
+# ---------------------------------------------------------------------------------------------
+def _colour_flag(colour, nbands, what):
+    """The C entries' ``colour``: None -> 0 (the bytes as they are), 'rgb' -> 1 (RGB pixels outside, Pillow's YCbCr inside)."""
+    if colour is None:
+        return 0
+    if colour != "rgb":
+        raise JpegxError("%s: colour must be None or 'rgb', got %r" % (what, colour))
+    _three_bands(True, nbands, what)
+    return 1
+
+
+def batch_group_planes_pictures_n(nbands, rows, cols, bs, n):
+    """The recommended group_planes of the picture entries (jpegx_batch_group_planes_pictures_n): the largest multiple of
+    nbands whose planes stay within 2^26 samples, nbands at least; 0 for a shape the entries refuse."""
+    return lib().jpegx_batch_group_planes_pictures_n(int(nbands), int(rows), int(cols), int(bs), int(n))
+
+
+def batch_decompress_pictures_workspace_bytes_n(nbytes, npictures, nbands, rows, cols, bs, n, group_planes):
+    return lib().jpegx_batch_decompress_pictures_workspace_bytes_n(int(nbytes), int(npictures), int(nbands), int(rows), int(cols),
+                                                                   int(bs), int(n), int(group_planes))
+
+
+def batch_groups_pictures_n(plane_offsets, npictures, nbands, rows, cols, bs, n, group_planes):
+    """The cut of a coded batch of pictures into decoding groups on picture boundaries (jpegx_batch_groups_pictures_n; host
+    arithmetic, no device needed): the first PICTURE of every group and, last, npictures."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(npictures) * int(nbands) + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    first = np.zeros(int(npictures) + 1, dtype=np.int32)
+    ngroups = ctypes.c_int(0)
+    check(lib().jpegx_batch_groups_pictures_n(off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n),
+                                              int(group_planes), first.ctypes.data, ctypes.byref(ngroups)), "jpegx_batch_groups_pictures_n")
+    return first[:ngroups.value + 1].copy()
+
+
+def band_planes_packed_stacked_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, d_out, colour=0, pitch=None, out_pitch=None,
+                                        stream=None, device=None):
+    """Enqueue jpegx_band_planes_packed_stacked_n: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands)
+    -> float64 planes stacked picture-major [npictures * nbands * H][out_pitch] (default W); colour 0 or 1 as in the header."""
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), int(n), d_out, int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_band_planes_packed_stacked_n(*args) if device is None else L.jpegx_band_planes_packed_stacked_n_on(int(device), *args),
+          "jpegx_band_planes_packed_stacked_n")
+
+
+def inflate_crop_pack_stacked_u8_device(d_planes, npictures, nbands, height, pitch, rows, cols, bs, d_out, colour=0, out_pitch=None,
+                                        stream=None, device=None):
+    """Enqueue jpegx_inflate_crop_pack_stacked_u8: uint8 planes stacked [npictures * nbands * height][pitch] -> pictures
+    stacked [npictures * rows][out_pitch] (bytes, default cols * nbands)."""
+    args = (d_planes, int(npictures), int(nbands), int(height), int(pitch), int(rows), int(cols), int(bs), int(colour), d_out,
+            int(cols * nbands if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_inflate_crop_pack_stacked_u8(*args) if device is None else L.jpegx_inflate_crop_pack_stacked_u8_on(int(device), *args),
+          "jpegx_inflate_crop_pack_stacked_u8")
+
+
+def batch_compress_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, d_workspace, d_out, out_cap, group_planes,
+                                     mode="none", param=0.0, colour=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_compress_pictures_n: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands) ->
+    coded bytes at d_out (None: sizes only).  Verdict and plane index: batch_compress_status_n with nbands * npictures planes."""
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), int(n), mode_of(mode), float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress_pictures_n(*args) if device is None else L.jpegx_batch_compress_pictures_n_on(int(device), *args),
+          "jpegx_batch_compress_pictures_n")
+
+
+def batch_decompress_pictures_n_device(d_bytes, plane_offsets, npictures, nbands, rows, cols, bs, n, d_workspace, d_out, group_planes,
+                                       out_pitch=None, mode="none", param=0.0, colour=0, stream=None, device=None):
+    """jpegx_batch_decompress_pictures_n (synchronises the stream once per group); plane_offsets: nbands * npictures + 1 host
+    integers; pictures stacked [npictures * rows][out_pitch] (default cols * nbands) at d_out.  Raises JpegxError for whatever
+    the entry refuses."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(npictures) * int(nbands) + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    args = (d_bytes, off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n), mode_of(mode), float(param),
+            int(colour), int(group_planes), d_workspace, d_out, int(cols * nbands if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_batch_decompress_pictures_n(*args) if device is None else L.jpegx_batch_decompress_pictures_n_on(int(device), *args),
+          "jpegx_batch_decompress_pictures_n")
+
+
+def batch_compress_pictures_n(pixels, bs, n, mode="none", param=0.0, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> a list of k lists of nb byte strings, each what compress_band_n gives for that band
+    of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host convenience over the device entries (upload,
+    sizes-only compress, status, emit into a buffer of exactly the total, download).  group_planes None: the recommended
+    value.  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the batch."""
+    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    k, rows, cols, nb = src.shape
+    flag = _colour_flag(colour, nb, "batch_compress_pictures_n")
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, n) or nb
+    pics, planes = (k, nb, rows, cols, int(bs), int(n)), (k * nb, rows, cols, int(bs), int(n))
+    nws = batch_workspace_bytes_n(*planes, group_planes) if group_planes > 0 and group_planes % nb == 0 else 0
+    if nws == 0:                                        # the entry names the refusal, before any device is touched
+        batch_compress_pictures_n_device(1, *pics, 16, None, 0, group_planes, mode, param, flag)
+        raise JpegxError("batch_compress_pictures_n: the batch was refused")
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dws = dev(src.nbytes), dev(nws)
+        din.upload(src)
+        batch_compress_pictures_n_device(din.ptr, *pics, dws.ptr, None, 0, group_planes, mode, param, flag)
+        rc, total, off = batch_compress_status_n(dws.ptr, *planes, group_planes)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status_n")
+        dout = dev(max(1, total))
+        batch_emit_n_device(dws.ptr, *planes, dout.ptr, total, group_planes)
+        rc, total2, off = batch_compress_status_n(dws.ptr, *planes, group_planes)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit_n")
+        blob = dout.download((total,), np.uint8)
+        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(k)]
+
+
+def batch_decompress_pictures_n(blobs, rows, cols, bs, n, mode="none", param=0.0, colour=None, group_planes=None):
+    """k lists of nb byte strings (as batch_compress_pictures_n returns them) -> uint8 [k][rows][cols][nb], picture p the
+    np.dstack of what decompress_band_n gives for its bands (with colour='rgb': Pillow's RGB of that).  JpegxError naming a
+    picture range for a stream the device refuses."""
+    blobs = [[bytes(b) for b in picture] for picture in blobs]
+    k = len(blobs)
+    nb = len(blobs[0]) if k else 0
+    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs):
+        raise JpegxError("expected at least one picture, and the same number of bands in each")
+    flag = _colour_flag(colour, nb, "batch_decompress_pictures_n")
+    rows, cols = int(rows), int(cols)
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, n) or nb
+    flat = [b for picture in blobs for b in picture]
+    off = np.zeros(k * nb + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in flat])
+    total = int(off[-1])
+    pics = (k, nb, rows, cols, int(bs), int(n))
+    nws = batch_decompress_pictures_workspace_bytes_n(max(total, 1), *pics, group_planes)
+    if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
+        batch_decompress_pictures_n_device(1, off, *pics, 16, 1, group_planes, None, mode, param, flag)
+        raise JpegxError("batch_decompress_pictures_n: empty stream")
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dout = dev(total), dev(nws), dev(k * rows * cols * nb)
+        din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
+        batch_decompress_pictures_n_device(din.ptr, off, *pics, dws.ptr, dout.ptr, group_planes, None, mode, param, flag)
+        return dout.download((k, rows, cols, nb), np.uint8)

@@ -549,6 +549,76 @@ int jpegx_band_planes_packed_n(const uint8_t *d_pixels, int nbands, int rows, in
 int jpegx_inflate_crop_pack_u8(const uint8_t *const *d_planes, int nbands, ptrdiff_t pitch, int rows, int cols, int bs,
                                uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
 
+/* ---- both for a STACK of equally shaped pixel-interleaved pictures, packed and stacked at once (the picture batch below) --
+ * jpegx_band_planes_packed_stacked_n (enqueue only): pictures stacked [npictures * rows][pitch], every row cols * nbands
+ * interleaved bytes, the pictures back to back (np.asarray of each, pipeline/__init__.py:98-111: `image.split()` and the bands
+ * one after another) -> float64 planes stacked [npictures * nbands * H][out_pitch], H, W from jpegx_band_shape_n, PICTURE-MAJOR:
+ * plane p * nbands + k holds band k of picture p, the order of the container.  Every plane is bit for bit what
+ * jpegx_band_plane_n makes of pixels[p][:, :, k].  Every clamp is against the picture's own last row and column: no read
+ * crosses into the neighbouring picture or into the pitch gap.  To convert pictures p0 .. p0 + k - 1 of a larger stack alone,
+ * pass d_pixels + p0 * rows * pitch and npictures = k.
+ * jpegx_inflate_crop_pack_stacked_u8 (enqueue only): uint8 planes stacked [npictures * nbands * H][pitch] in the same order
+ * -> pixels [npictures * rows][out_pitch], out[p][y][x * nbands + k] = plane (p, k)[y / bs][x / bs] (pipeline/__init__.py:113-124,
+ * the np.dstack included).  Exactly cols * nbands bytes of every output row are written; no read passes row (rows - 1) / bs or
+ * column (cols - 1) / bs of a plane.
+ * colour: 0 = the bytes as they are.  1 (nbands 3 only, else JPEGX_E_INVALID) = the pixels are RGB and the planes Pillow's
+ * YCbCr: the gather converts every pixel it reads with the forward tables of jpegx_rgb_to_ycbcr_u8 BEFORE the pixel enters
+ * the tile sum (compress.py:9, image.convert("YCbCr"), then pipeline/subsampling.py:9-11); the scatter converts each source
+ * triple once with the inverse tables and replicates the result (decompress.py:9-10, .convert("RGB") of the inflated picture).
+ * Both: nbands in 1..JPEGX_MAX_IMAGE_BANDS, npictures >= 1, rows * cols, npictures * nbands * H * W and npictures * rows each
+ * <= 2^31 - 1 (the scatter, which has no W: npictures * nbands * H; H >= ceil(rows / bs)), bs in 1..255 (else
+ * JPEGX_E_UNSUPPORTED), N in 2..32, pitches at least the row, d_out of the gather 8-byte aligned (else JPEGX_E_INVALID); the
+ * packed pointers need NO alignment.  All of this is checked before any device work.                                  */
+int jpegx_band_planes_packed_stacked_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                       int colour, int bs, int N, double *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_inflate_crop_pack_stacked_u8(const uint8_t *d_planes, int npictures, int nbands, int H, ptrdiff_t pitch, int rows,
+                                       int cols, int bs, int colour, uint8_t *d_out, ptrdiff_t out_pitch,
+                                       jpegx_stream_t stream);
+
+/* ---- batch codec for whole pictures at any DCT size: a stack of pictures -> the coded bytes of every band, picture-major,
+ * and back (csrc/jpegx_batch_n.cpp) -----------------------------------------------------------------------------------
+ * Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124) for every picture of the stack: the bytes
+ * of each band as Jpeg.compress makes them, with colour = 1 behind the conversion that compress.py:9 puts in front of it,
+ * and back the pixels of Jpeg.decompress, with colour = 1 through the conversion of decompress.py:9-10.  A stack of
+ * npictures pictures of nbands bands IS the band batch above of nplanes = nbands * npictures planes, plane p * nbands + k
+ * band k of picture p: the compress workspace is jpegx_batch_workspace_bytes_n's, the worst case jpegx_batch_max_bytes_n's,
+ * the verdicts and the plane index jpegx_batch_compress_status_n's, the small-footprint road jpegx_batch_emit_n's -- all
+ * called with that nplanes -- and the limits are theirs.  Only what differs has an entry here.  dct_size 8 is not served:
+ * its batch entries take block_size 1, 2, 4 and shapes that are multiples of 8 * block_size only.
+ * group_planes: a POSITIVE MULTIPLE of nbands (anything else is JPEGX_E_INVALID; 0 is not taken, because the band entries
+ * would place the pieces of the workspace differently for it): groups are whole pictures.
+ * jpegx_batch_group_planes_pictures_n (host arithmetic) recommends the largest multiple of nbands whose planes stay within
+ * 2^26 samples H * W, nbands at least; 0 for shapes that jpegx_band_shape_n refuses and for nbands outside
+ * 1..JPEGX_MAX_IMAGE_BANDS.                                                                                             */
+int jpegx_batch_group_planes_pictures_n(int nbands, int rows, int cols, int bs, int N);
+/* enqueue only: per group of whole pictures jpegx_band_planes_packed_stacked_n + jpegx_forward_fused_n into the group's rows
+ * of the int32 stream, then one jpegx_entropy_sizes_n, the plane index, the guarded emitter, as jpegx_batch_compress_n.
+ * d_pixels [npictures * rows][pitch], pitch >= cols * nbands, no alignment asked; it is never written.  d_out == NULL: sizes
+ * only.                                                                                                                 */
+int jpegx_batch_compress_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                    int colour, int bs, int N, int mode, double param, int group_planes, void *d_workspace,
+                                    uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+/* The cut of the way back ON PICTURE BOUNDARIES, host arithmetic only: h_plane_offsets holds nbands * npictures + 1 offsets;
+ * from the first picture not yet taken a group takes whole pictures while it holds fewer than group_planes / nbands of them
+ * and its bytes stay within 64 MiB, and one picture at least.  h_group_first (may be NULL; room for npictures + 1) counts
+ * PICTURES, h_group_first[*ngroups] = npictures.  JPEGX_E_INVALID for offsets that decrease and for a lone picture of
+ * 2^32 - 4096 bytes or more.                                                                                           */
+int jpegx_batch_groups_pictures_n(const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols,
+                                  int bs, int N, int group_planes, int *h_group_first, int *ngroups);
+/* The way back: jpegx_batch_decompress_n's steps per group of jpegx_batch_groups_pictures_n (staging copy,
+ * jpegx_entropy_decode_n, the verdict with ONE synchronisation, jpegx_inverse_fused_n with JPEGX_F_CLAMP_U8), then
+ * jpegx_inflate_crop_pack_stacked_u8 into the group's pictures of d_out [npictures * rows][out_pitch], out_pitch >= cols *
+ * nbands.  The verdict is read before the inverse is enqueued: a refused group writes nothing and is named by its first
+ * and last PICTURE; earlier groups have been written.  Refused before any device work: what jpegx_batch_decompress_n
+ * refuses there.  The workspace differs from the band entry's in its staging area, which holds a lone picture's worst case
+ * (nbands times a plane's).                                                                                             */
+size_t jpegx_batch_decompress_pictures_workspace_bytes_n(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs,
+                                                         int N, int group_planes);
+int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures,
+                                      int nbands, int rows, int cols, int bs, int N, int mode, double param, int colour,
+                                      int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
+                                      jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -938,6 +1008,19 @@ int jpegx_batch_emit_n_on(int device, void *d_workspace, int nplanes, int rows, 
 int jpegx_batch_decompress_n_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes,
                                 int rows, int cols, int bs, int N, int mode, double param, int group_planes,
                                 void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_band_planes_packed_stacked_n_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                          ptrdiff_t pitch, int colour, int bs, int N, double *d_out, ptrdiff_t out_pitch,
+                                          jpegx_stream_t stream);
+int jpegx_inflate_crop_pack_stacked_u8_on(int device, const uint8_t *d_planes, int npictures, int nbands, int H, ptrdiff_t pitch,
+                                          int rows, int cols, int bs, int colour, uint8_t *d_out, ptrdiff_t out_pitch,
+                                          jpegx_stream_t stream);
+int jpegx_batch_compress_pictures_n_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                       ptrdiff_t pitch, int colour, int bs, int N, int mode, double param, int group_planes,
+                                       void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_decompress_pictures_n_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
+                                         int npictures, int nbands, int rows, int cols, int bs, int N, int mode, double param,
+                                         int colour, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
+                                         jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
