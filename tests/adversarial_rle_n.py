@@ -148,6 +148,23 @@ def block_bytes(zz):
     return out
 
 
+def block_bytes_of_stream(zz):
+    """block_bytes for streams of hundreds of thousands of blocks: the same arithmetic over all non-zeros at once, no Python
+    loop over the blocks (tests/test_adversarial_rle_n.py holds the two against each other)."""
+    z = np.asarray(zz)
+    nblocks, block_len = z.shape
+    at = np.flatnonzero(z)                                               # row-major: block after block, index after index
+    blk, pos = at // block_len, at % block_len
+    prev = np.full(at.size, -1, np.int64)                                # the previous non-zero of the same block
+    same = blk[1:] == blk[:-1]
+    prev[1:][same] = pos[:-1][same]
+    mag = np.abs(z.reshape(-1)[at].astype(np.int64))
+    bit_length = sum(((mag >> k) > 0).astype(np.int64) for k in range(32))
+    bits = 8 * ((pos - prev - 1) // 15) + 9 + bit_length
+    total = np.bincount(blk, weights=bits, minlength=nblocks).astype(np.int64)       # sums far below 2^53: exact
+    return ((total + 8 + 7) // 8).astype(np.uint32)
+
+
 @functools.lru_cache(maxsize=None)
 def host_bytes(cls, block_len, nblocks):
     """(bytes of the whole stream, uint32 sizes of every block encoded alone) by the host coder."""

@@ -102,6 +102,17 @@ def test_mixed_and_bad(block_len):
     assert len(jpegx.entropy_encode_n(ok)) == int(adv.block_bytes(ok).sum())
 
 
+@pytest.mark.parametrize("block_len", LENGTHS)
+def test_block_bytes_of_stream_is_block_bytes(block_len):
+    nblocks = 130 if block_len <= 64 else 67
+    for cls in adv.CLASSES:
+        z = adv.build(cls, block_len, nblocks)
+        got = adv.block_bytes_of_stream(z)
+        assert got.dtype == np.uint32 and np.array_equal(got, adv.block_bytes(z)), cls
+    ok = adv.bad(-16383, block_len, nblocks)
+    assert np.array_equal(adv.block_bytes_of_stream(ok), adv.block_bytes(ok))
+
+
 def test_workspace_bytes_n():
     import jpegx
     L = jpegx.lib()
