@@ -11,6 +11,7 @@
 // one decode call can take.  Nothing is allocated here except the whole-stream decoder's scratch (level 2 of the
 // ladder), which is sized from a count read back from the device and therefore cannot be the caller's.
 #include <limits.h>
+#include <math.h>
 
 #include <mutex>
 
@@ -352,6 +353,180 @@ int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_p
         p0 = p1;
     }
     return JPEGX_OK;
+}
+
+}  // extern "C"
+
+// ---- a stack of PICTURES at dct_size 8 ---------------------------------------------------------------------------------
+// Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124) for every picture of a stack of equally
+// sized pixel-interleaved 8-bit pictures, with colour = 1 behind the conversion that compress.py:9 puts in front of the
+// first and through the one decompress.py:9-10 puts behind the second.  The stack is the batch above of nplanes = nbands *
+// npictures planes in picture-major order, so the workspace BEGINS with carve_compress's layout for (nplanes, H, W) and
+// jpegx_batch_compress_status / jpegx_batch_emit serve as they are.  What the picture entries add is the front end, chosen as
+// enqueue_front (jpegx_hostpipe.cpp) chooses: block_size 1, 2, 4 with padded rows of a multiple of 16 bytes take the fused
+// uint8 gather (jpegx_picture_u8.hip) over the whole stack and the sized uint8 forward kernel on the tall plane; every other
+// case goes group after group of whole pictures through jpegx_band_planes_packed_stacked_n at N = 8 (the mean of the
+// replicated tile in float64: exact sum, one division, as jpegx_mean_pool_f64) and jpegx_forward_fused_f64.
+namespace {
+
+struct PictureShape {
+    int nplanes, H, W, gp;   // gp: planes per group on the float64 road, a multiple of nbands, at most nplanes
+    long long nb;            // blocks per plane
+    bool u8;                 // the uint8 road
+};
+
+int picture_shape(const char *who, int npictures, int nbands, int rows, int cols, int bs, int colour, int group_planes, PictureShape *s)
+{
+    char buf[200];
+    if (npictures <= 0) {
+        snprintf(buf, sizeof(buf), "%s: the picture count must be positive", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) {
+        snprintf(buf, sizeof(buf), "%s takes 1..JPEGX_MAX_IMAGE_BANDS bands", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if ((colour != 0 && colour != 1) || (colour == 1 && nbands != 3)) {
+        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (group_planes <= 0 || group_planes % nbands) {
+        snprintf(buf, sizeof(buf), "%s: group_planes must be a positive multiple of the band count (jpegx_batch_group_planes_pictures_n)", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (rows < 1 || cols < 1) {
+        snprintf(buf, sizeof(buf), "%s: rows and cols must be at least 1", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (bs < 1 || bs > 255) {
+        snprintf(buf, sizeof(buf), "%s: block_size must be in 1..255", who);
+        return fail(JPEGX_E_UNSUPPORTED, buf);
+    }
+    int rc = jpegx_padded_shape(rows, cols, bs, &s->H, &s->W);
+    if (rc) return rc;
+    if (npictures > INT_MAX / nbands) return fail(JPEGX_E_INVALID, "batch: more than 2^31 - 64 blocks in one batch");
+    s->nplanes = npictures * nbands;
+    if ((rc = check_batch_shape(s->nplanes, s->H, s->W, &s->nb))) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) {
+        snprintf(buf, sizeof(buf), "%s: more than 2^31 - 1 samples in one band", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if ((long long)rows * npictures > INT_MAX || (long long)s->nplanes * s->H > INT_MAX / bs) {
+        snprintf(buf, sizeof(buf), "%s: the stack has more than 2^31 - 1 rows", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    s->u8 = (bs == 1 || bs == 2 || bs == 4) && ((long long)s->W * bs) % 16 == 0;
+    s->gp = group_planes > s->nplanes ? s->nplanes : group_planes;
+    if (!s->u8 && (long long)s->H * s->W > 0x7FFFFFFFLL / s->gp) {
+        snprintf(buf, sizeof(buf), "%s: more than 2^31 - 1 samples in one group of planes", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    return JPEGX_OK;
+}
+
+// what the forward kernels refuse (fill_forward_params, jpegx_internal.h; forward_u8_common, jpegx_forward.hip), with their
+// codes, before anything is launched.  The divisor's limit is the uint8 kernels' (they pack without saturating); it holds on
+// both roads, so that a quantiser is taken or refused whatever the pictures' shape.
+int check_forward_quantiser(int mode, double param)
+{
+    switch (mode) {
+    case JPEGX_Q_NONE:
+    case JPEGX_Q_QTABLE:
+        return JPEGX_OK;
+    case JPEGX_Q_DISCARD:
+        if (!(param >= 0.0) || param != (double)(int)param) return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
+        return JPEGX_OK;
+    case JPEGX_Q_DIVIDE:
+        if (!(param != 0.0) || !(fabs(param) <= 1e30)) return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
+        if (fabsf((float)(1.0 / param)) > 2.0f)
+            return fail(JPEGX_E_UNSUPPORTED, "forward_u8: a divisor below 0.5 can overflow int16; use the fp32 entry (it saturates)");
+        return JPEGX_OK;
+    default:
+        return fail(JPEGX_E_INVALID, "unknown quantiser mode");
+    }
+}
+
+// behind carve_compress's pieces: the padded raw planes of the whole stack (uint8 road) or the float64 planes of one group
+size_t picture_front_bytes(const PictureShape &s, int bs)
+{
+    return s.u8 ? up256((size_t)s.nplanes * s.H * bs * ((size_t)s.W * bs)) : up256((size_t)s.gp * s.H * s.W * 8);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpegx_batch_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes)
+{
+    PictureShape s;
+    if (picture_shape("batch_pictures_workspace_bytes", npictures, nbands, rows, cols, bs, 0, group_planes, &s)) return 0;
+    return carve_compress(nullptr, s.nplanes, s.nb * s.nplanes).bytes + picture_front_bytes(s, bs);
+}
+
+int jpegx_batch_compress_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int mode,
+                                  double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream)
+{
+    if (!d_pixels || !d_workspace) return fail(JPEGX_E_INVALID, "batch_compress_pictures: null device pointer");
+    PictureShape s;
+    int rc = picture_shape("batch_compress_pictures", npictures, nbands, rows, cols, bs, colour, group_planes, &s);
+    if (rc || (rc = check_forward_quantiser(mode, param))) return rc;
+    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_compress_pictures: pitch smaller than the row");
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_compress_pictures: workspace must be 16-byte aligned");
+    const long long nblocks = s.nb * s.nplanes;
+    const CompressWs c = carve_compress(d_workspace, s.nplanes, nblocks);
+    unsigned char *front = static_cast<unsigned char *>(d_workspace) + c.bytes;
+    if (s.u8) {
+        const ptrdiff_t WW = (ptrdiff_t)s.W * bs;
+        unsigned *block_bytes = nullptr, *wave_bytes = nullptr, *half_info = nullptr;
+        jpegx_internal_entropy_views(c.ews, nblocks, &block_bytes, &wave_bytes, &half_info);
+        if ((rc = jpegx_picture_planes_stacked_u8(d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, front, WW, stream)) ||
+            (rc = jpegx_internal_forward_u8_sized(front, s.nplanes * s.H, s.W, WW, bs, mode, param, 0, c.zz, block_bytes, wave_bytes, half_info, stream)))
+            return rc;
+    } else {
+        double *planes = reinterpret_cast<double *>(front);
+        const int gpics = s.gp / nbands;
+        for (int q0 = 0; q0 < npictures; q0 += gpics) {
+            const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
+            if ((rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, 8, planes,
+                                                         s.W, stream)) ||
+                (rc = jpegx_forward_fused_f64(planes, nq * nbands * s.H, s.W, s.W, mode, param, 0, c.zz + (size_t)q0 * nbands * (size_t)s.nb * 64, stream)))
+                return rc;
+        }
+        if ((rc = jpegx_internal_entropy_sizes_half(c.zz, nblocks, c.ews, stream))) return rc;
+    }
+    if ((rc = jpegx_internal_entropy_scan(nblocks, c.ews, stream))) return rc;
+    return enqueue_index_and_emit(c, s.nplanes, s.nb, d_out, out_cap, stream);
+}
+
+// The way back: the coded planes through jpegx_batch_decompress with block_size 1 into POOLED uint8 planes [nplanes * H][W]
+// inside the workspace, and only after it has answered JPEGX_OK the scatter jpegx_inflate_crop_pack_stacked_u8 (the
+// replication of SubSampling.invert, both crops, the np.dstack and, with colour = 1, Pillow's RGB) into d_out -- a refused
+// stream writes nothing there.  The workspace: jpegx_batch_decompress's (256-byte aligned), then the pooled planes.
+size_t jpegx_batch_decompress_pictures_workspace_bytes(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs)
+{
+    PictureShape s;
+    if (nbytes == 0 || picture_shape("batch_decompress_pictures_workspace_bytes", npictures, nbands, rows, cols, bs, 0, nbands, &s)) return 0;
+    const size_t inner = jpegx_batch_decompress_workspace_bytes(nbytes, s.nplanes, s.H, s.W);
+    return inner ? up256(inner) + up256((size_t)s.nplanes * s.H * s.W) : 0;
+}
+
+int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs,
+                                    int mode, double param, int colour, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_bytes || !h_plane_offsets || !d_workspace || !d_out) return fail(JPEGX_E_INVALID, "batch_decompress_pictures: null pointer");
+    PictureShape s;
+    int rc = picture_shape("batch_decompress_pictures", npictures, nbands, rows, cols, bs, colour, nbands, &s);
+    if (rc) return rc;
+    if (out_pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_decompress_pictures: output pitch smaller than the row");
+    const unsigned pix = (nbands == 3 ? 48u : 16u) / (unsigned)nbands;      // the scatter's lanes: refused here, not after the decoding
+    if (((unsigned long long)npictures * rows * (((unsigned)cols + pix - 1u) / pix) + 255u) / 256u > 0x7FFFFFFFull)
+        return fail(JPEGX_E_INVALID, "batch_decompress_pictures: more than 2^39 lanes in one launch");
+    if (h_plane_offsets[s.nplanes] <= h_plane_offsets[0]) return fail(JPEGX_E_INVALID, "batch_decompress_pictures: empty stream");
+    const size_t inner = jpegx_batch_decompress_workspace_bytes((size_t)(h_plane_offsets[s.nplanes] - h_plane_offsets[0]), s.nplanes, s.H, s.W);
+    uint8_t *planes = static_cast<uint8_t *>(d_workspace) + up256(inner);
+    if ((rc = jpegx_batch_decompress(d_bytes, h_plane_offsets, s.nplanes, s.H, s.W, 1, mode, param, 0, d_workspace, planes, s.W, JPEGX_OUT_U8, stream)))
+        return rc;
+    return jpegx_inflate_crop_pack_stacked_u8(planes, npictures, nbands, s.H, s.W, rows, cols, bs, colour, d_out, out_pitch, stream);
 }
 
 }  // extern "C"

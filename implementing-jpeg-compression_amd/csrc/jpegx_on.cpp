@@ -163,3 +163,9 @@ JPEGX_ON(jpegx_batch_compress_pictures_n, (int device, const uint8_t *d_pixels, 
          (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, N, mode, param, group_planes, d_workspace, d_out, out_cap, stream))
 JPEGX_ON(jpegx_batch_decompress_pictures_n, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs, int N, int mode, double param, int colour, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
          (d_bytes, h_plane_offsets, npictures, nbands, rows, cols, bs, N, mode, param, colour, group_planes, d_workspace, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_picture_planes_stacked_u8, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, d_out, out_pitch, stream))
+JPEGX_ON(jpegx_batch_compress_pictures, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, mode, param, group_planes, d_workspace, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_decompress_pictures, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs, int mode, double param, int colour, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream),
+         (d_bytes, h_plane_offsets, npictures, nbands, rows, cols, bs, mode, param, colour, d_workspace, d_out, out_pitch, stream))

@@ -204,6 +204,11 @@ SIGNATURES = {
     "jpegx_batch_groups_pictures_n": [_vp, _int, _int, _int, _int, _int, _int, _int, _vp, _c.POINTER(_int)],
     "jpegx_batch_decompress_pictures_workspace_bytes_n": [_sz, _int, _int, _int, _int, _int, _int, _int],
     "jpegx_batch_decompress_pictures_n": [_vp, _vp, _int, _int, _int, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _pd, _vp],
+    "jpegx_picture_planes_stacked_u8": [_vp, _int, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
+    "jpegx_batch_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
+    "jpegx_batch_compress_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
+    "jpegx_batch_decompress_pictures_workspace_bytes": [_sz, _int, _int, _int, _int, _int],
+    "jpegx_batch_decompress_pictures": [_vp, _vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _vp, _vp, _pd, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -232,13 +237,15 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_host_compress_image_rgb_n", "jpegx_host_decompress_image_rgb_n", "jpegx_band_planes_stacked_n",
               "jpegx_inflate_crop_stacked_u8", "jpegx_batch_compress_n", "jpegx_batch_compress_status_n", "jpegx_batch_emit_n",
               "jpegx_batch_decompress_n", "jpegx_band_planes_packed_stacked_n", "jpegx_inflate_crop_pack_stacked_u8",
-              "jpegx_batch_compress_pictures_n", "jpegx_batch_decompress_pictures_n"):
+              "jpegx_batch_compress_pictures_n", "jpegx_batch_decompress_pictures_n", "jpegx_picture_planes_stacked_u8",
+              "jpegx_batch_compress_pictures", "jpegx_batch_decompress_pictures"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz, "jpegx_batch_workspace_bytes_n": _sz,
             "jpegx_batch_max_bytes_n": _sz, "jpegx_batch_decompress_workspace_bytes_n": _sz,
-            "jpegx_batch_decompress_pictures_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_decompress_pictures_workspace_bytes_n": _sz, "jpegx_batch_pictures_workspace_bytes": _sz,
+            "jpegx_batch_decompress_pictures_workspace_bytes": _sz}   # everything else returns int
 
 
 def lib():
@@ -1745,7 +1752,7 @@ def batch_decompress_n(blobs, rows, cols, bs, n, mode="none", param=0.0, group_p
 # the batch codec for whole pictures at any DCT size: a stack of pixel-interleaved pictures -> the coded bytes of every
 # band, picture-major, and back.  A stack of k pictures of nb bands is the band batch above of nb * k planes: workspace,
 # worst case, status and emit are batch_workspace_bytes_n / batch_max_bytes_n / batch_compress_status_n / batch_emit_n_device
-# with that plane count.  dct_size 8 is not served (its batch entries take block_size 1, 2, 4 and whole tiles only).
+# with that plane count.  dct_size 8 has its own entries, at the end of this file.
 # ---------------------------------------------------------------------------------------------
 def _colour_flag(colour, nbands, what):
     """The C entries' ``colour``: None -> 0 (the bytes as they are), 'rgb' -> 1 (RGB pixels outside, Pillow's YCbCr inside)."""
@@ -1892,4 +1899,146 @@ def batch_decompress_pictures_n(blobs, rows, cols, bs, n, mode="none", param=0.0
         din, dws, dout = dev(total), dev(nws), dev(k * rows * cols * nb)
         din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
         batch_decompress_pictures_n_device(din.ptr, off, *pics, dws.ptr, dout.ptr, group_planes, None, mode, param, flag)
+        return dout.download((k, rows, cols, nb), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the batch codec for whole pictures at dct_size 8: the same stack of pictures through the 8x8 batch.  k pictures of nb bands
+# are the 8x8 batch of nb * k planes of (h, w) = padded_shape(rows, cols, block_size): verdicts, plane index and emit are
+# batch_compress_status / batch_emit_device with that plane count, the worst case batch_max_bytes.
+# ---------------------------------------------------------------------------------------------
+def batch_pictures_workspace_bytes(npictures, nbands, rows, cols, block_size, group_planes):
+    return lib().jpegx_batch_pictures_workspace_bytes(int(npictures), int(nbands), int(rows), int(cols), int(block_size), int(group_planes))
+
+
+def batch_decompress_pictures_workspace_bytes(nbytes, npictures, nbands, rows, cols, block_size):
+    return lib().jpegx_batch_decompress_pictures_workspace_bytes(int(nbytes), int(npictures), int(nbands), int(rows), int(cols),
+                                                                 int(block_size))
+
+
+def picture_planes_stacked_u8_device(d_pixels, npictures, nbands, rows, cols, block_size, d_out, out_pitch, colour=0, pitch=None,
+                                     stream=None, device=None):
+    """Enqueue jpegx_picture_planes_stacked_u8: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands) ->
+    padded raw uint8 planes stacked picture-major [npictures * nbands * H * block_size][out_pitch]."""
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(block_size), d_out, int(out_pitch), stream)
+    L = lib()
+    check(L.jpegx_picture_planes_stacked_u8(*args) if device is None else L.jpegx_picture_planes_stacked_u8_on(int(device), *args),
+          "jpegx_picture_planes_stacked_u8")
+
+
+def picture_planes_stacked_u8(pixels, block_size=1, colour=None):
+    """jpegx_picture_planes_stacked_u8 on a host array (test convenience, like pad_edges): uint8 pictures
+    [k][rows][cols][nb] -> the padded raw planes [k][nb][H * block_size][W * block_size], (H, W) = padded_shape(rows, cols,
+    block_size); with colour='rgb' of the pictures' Pillow YCbCr."""
+    src = np.ascontiguousarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    k, rows, cols, nb = src.shape
+    bs = int(block_size)
+    flag = _colour_flag(colour, nb, "picture_planes_stacked_u8")
+    h, w = padded_shape(rows, cols, bs)
+    pitch = (w * bs + 15) // 16 * 16
+    require_device()
+    with _Buffers() as dev:
+        din, dout = dev(src.nbytes), dev(k * nb * h * bs * pitch)
+        din.upload(src)
+        picture_planes_stacked_u8_device(din.ptr, k, nb, rows, cols, bs, dout.ptr, pitch, flag)
+        out = dout.download((k, nb, h * bs, pitch), np.uint8)
+        return np.ascontiguousarray(out[..., :w * bs])
+
+
+def batch_compress_pictures_device(d_pixels, npictures, nbands, rows, cols, block_size, d_workspace, d_out, out_cap, group_planes,
+                                   mode="qtable", param=0.0, colour=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_compress_pictures: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands) ->
+    coded bytes at d_out (None: sizes only).  Verdict and plane index: batch_compress_status with nbands * npictures planes
+    of padded_shape(rows, cols, block_size)."""
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(block_size), mode_of(mode), float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress_pictures(*args) if device is None else L.jpegx_batch_compress_pictures_on(int(device), *args),
+          "jpegx_batch_compress_pictures")
+
+
+def batch_decompress_pictures_device(d_bytes, plane_offsets, npictures, nbands, rows, cols, block_size, d_workspace, d_out,
+                                     out_pitch=None, mode="qtable", param=0.0, colour=0, stream=None, device=None):
+    """jpegx_batch_decompress_pictures (synchronises the stream between groups and levels); plane_offsets: nbands * npictures + 1
+    host integers; pictures stacked [npictures * rows][out_pitch] (default cols * nbands) at d_out.  Raises JpegxError for
+    whatever the entry refuses; d_out is untouched then."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(npictures) * int(nbands) + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    args = (d_bytes, off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(block_size), mode_of(mode), float(param),
+            int(colour), d_workspace, d_out, int(cols * nbands if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_batch_decompress_pictures(*args) if device is None else L.jpegx_batch_decompress_pictures_on(int(device), *args),
+          "jpegx_batch_decompress_pictures")
+
+
+def batch_compress_pictures(pixels, block_size=1, mode="qtable", param=0.0, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> a list of k lists of nb byte strings, each what compress_plane_native(band,
+    ragged=True) gives for that band of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host convenience over
+    the device entries (upload, sizes-only compress, status, emit into a buffer of exactly the total, download).  group_planes
+    None: the recommended value.  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the batch."""
+    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    k, rows, cols, nb = src.shape
+    bs = int(block_size)
+    flag = _colour_flag(colour, nb, "batch_compress_pictures")
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, 8) or nb
+    pics = (k, nb, rows, cols, bs)
+    nws = batch_pictures_workspace_bytes(*pics, group_planes)
+    if nws == 0:                                        # the entry names the refusal, before any device is touched
+        batch_compress_pictures_device(1, *pics, 16, None, 0, group_planes, mode, param, flag)
+        raise JpegxError("batch_compress_pictures: the batch was refused")
+    mode_of(mode)
+    planes = (k * nb,) + padded_shape(rows, cols, bs)
+    require_device()
+    with _Buffers() as dev:
+        din, dws = dev(src.nbytes), dev(nws)
+        din.upload(src)
+        batch_compress_pictures_device(din.ptr, *pics, dws.ptr, None, 0, group_planes, mode, param, flag)
+        rc, total, off = batch_compress_status(dws.ptr, *planes)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status")
+        dout = dev(max(1, total))
+        batch_emit_device(dws.ptr, *planes, dout.ptr, total)
+        rc, total2, off = batch_compress_status(dws.ptr, *planes)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit")
+        blob = dout.download((total,), np.uint8)
+        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(k)]
+
+
+def batch_decompress_pictures(blobs, rows, cols, block_size=1, mode="qtable", param=0.0, colour=None):
+    """k lists of nb byte strings (as batch_compress_pictures returns them) -> uint8 [k][rows][cols][nb], picture p the np.dstack
+    of its decoded bands cropped to rows x cols (with colour='rgb': Pillow's RGB of that).  JpegxError naming a plane range for a
+    stream the device refuses."""
+    blobs = [[bytes(b) for b in picture] for picture in blobs]
+    k = len(blobs)
+    nb = len(blobs[0]) if k else 0
+    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs):
+        raise JpegxError("expected at least one picture, and the same number of bands in each")
+    flag = _colour_flag(colour, nb, "batch_decompress_pictures")
+    rows, cols = int(rows), int(cols)
+    flat = [b for picture in blobs for b in picture]
+    off = np.zeros(k * nb + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in flat])
+    total = int(off[-1])
+    pics = (k, nb, rows, cols, int(block_size))
+    nws = batch_decompress_pictures_workspace_bytes(max(total, 1), *pics)
+    if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
+        batch_decompress_pictures_device(1, off, *pics, 256, 16, None, mode, param, flag)
+        raise JpegxError("batch_decompress_pictures: empty stream")
+    mode_of(mode)
+    stream_bytes = np.zeros(total + 16, dtype=np.uint8)                # 16 zero bytes behind the stream
+    stream_bytes[:total] = np.frombuffer(b"".join(flat), dtype=np.uint8)
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dout = dev(stream_bytes.nbytes), dev(max(256, nws)), dev(k * rows * cols * nb)
+        din.upload(stream_bytes)
+        batch_decompress_pictures_device(din.ptr, off, *pics, dws.ptr, dout.ptr, None, mode, param, flag)
         return dout.download((k, rows, cols, nb), np.uint8)

@@ -1071,7 +1071,8 @@ def decompress_bands_u8(compression_results, config):
 # many pictures of one size at once
 # ---------------------------------------------------------------------------------------------------------------------
 # compress_pictures / decompress_pictures_u8 take the batch road (jpegx.batch_compress_pictures_n /
-# batch_decompress_pictures_n, dct_size other than 8: one upload, one launch chain and one download for the whole stack, the
+# batch_decompress_pictures_n, dct_size other than 8; dct_size 8 has its own entries and gates, DCT8_PICTURE_BATCH_* below:
+# one upload, one launch chain and one download for the whole stack, the
 # colour conversion, the split into bands and the np.dstack inside the device's gather and scatter) from this many pictures
 # on; None: the road is off and the functions are a loop over Jpeg.compress / compress_rgb / decompress / decompress_rgb.
 # Never below 2: one picture is what those are for.  All three constants are read when the functions are called.
@@ -1106,6 +1107,33 @@ def _picture_batch_gate(count, samples, most):
     return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
 
 
+# dct_size 8 has a picture batch of its own (jpegx.batch_compress_pictures / batch_decompress_pictures: every block_size
+# 1..255 and every picture size, the padding inside the device's gather) behind its OWN three gates, with the meaning of the
+# DCTN_PICTURE_BATCH_* constants above and read when the functions are called.  The first ships as None -- the road is off and
+# dct_size 8 is the loop, as it was (tests/test_picture_batch_dispatch.py pins that with only the DCTN_* gates set; the precedent
+# is DCTN_ENTROPY_MIN_SAMPLES) -- and callers with many small pictures opt in by setting it: 2 is the measured value.
+# Measured (profiles/batch_pictures_8.json and _run2.json, the batch road against the loop alternating call by
+# call on one MI355X, block_size 4 and 1 with qtable, with colour 'rgb' and without, two runs): ONE picture loses compressing
+# (0.22-0.26 against 0.16-0.18 ms at 64 x 64 and 128 x 128: the loop's one pooled picture job against two status reads and three
+# allocations) and wins decompressing; with 2 pictures the batch wins all sixteen comparisons of either run (0.25-0.32 against
+# 0.31-0.40 ms compressing, 0.17-0.22 against 0.49-0.65 ms back), with 4 by 1.8-5.4x, with 64 by 5.1-40x.  Compressing, it is
+# 8.5-14x faster than the loop on 4096 pictures of 256 and of 4096 samples a plane and 1.03-1.24x on 256 pictures of 16 384; on 256
+# of 262 144 each run has one loss (78.4 against 75.2 ms, 83.9 against 80.7 ms), and on 16 pictures of 752 000 and 12 M samples it
+# loses 1.3-2.6x in both (np.stack and one pageable copy of 576 MB against the pooled picture jobs).  Decompressing, it wins
+# everything measured in both runs: 24-88x on the 4096 pictures, 1.7-9.5x on the 256, 10-15x on 16 of 752 000 samples and
+# 1.07-1.8x on 16 of 12 M.  Each _MAX_SAMPLES constant is the largest measured plane with no loss at or below it in either run;
+# they take effect once DCT8_PICTURE_BATCH_MIN_PICTURES is set.
+DCT8_PICTURE_BATCH_MIN_PICTURES = None
+DCT8_PICTURE_BATCH_COMPRESS_MAX_SAMPLES = 16384
+DCT8_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES = 12000000
+
+
+def _picture_batch_gate_8(count, samples, most):
+    """_picture_batch_gate for dct_size 8: ``most`` is the direction's DCT8_PICTURE_BATCH_*_MAX_SAMPLES as the caller reads it."""
+    gate = DCT8_PICTURE_BATCH_MIN_PICTURES
+    return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
+
+
 def _stacked_pixels(images, config, colour):
     """The pictures as one uint8 array [n][rows][cols][3], or None: they are not all pictures the picture jobs take
     (_picture_size: three bands, one of its four modes, the configured size -- so all of one size; _picture_pixels) or, with
@@ -1122,26 +1150,30 @@ def _stacked_pixels(images, config, colour):
 
 def _compress_picture_batch(images, config, colour):
     """The containers of the batch road, or None: the gate, the pictures or the configuration do not admit it, or libjpegx
-    refused or failed -- the loop then names the picture and the fault."""
-    most = DCTN_PICTURE_BATCH_COMPRESS_MAX_SAMPLES
+    refused or failed -- the loop then names the picture and the fault.  dct_size 8 (the accelerated configuration) goes by
+    _job_config_8, jpegx.padded_shape and the DCT8_* gates to jpegx.batch_compress_pictures, every other size by
+    _compress_job_n, _blocked_shape and the DCTN_* gates to jpegx.batch_compress_pictures_n."""
+    eight = _accelerated(config)
+    gate = _picture_batch_gate_8 if eight else _picture_batch_gate
+    most = DCT8_PICTURE_BATCH_COMPRESS_MAX_SAMPLES if eight else DCTN_PICTURE_BATCH_COMPRESS_MAX_SAMPLES
     count = len(images)
-    if not _picture_batch_gate(count, 0, most) or not _stock_registry() or not _device_usable():
+    if not gate(count, 0, most) or not _stock_registry() or not _device_usable():
         return None
     rows, cols = config.height, config.width
     if not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
             or rows * cols > 2 ** 31 - 1:
         return None
-    job = _compress_job_n(config, rows, cols, 0)
+    import jpegx
+    job = _job_config_8(config) if eight else _compress_job_n(config, rows, cols, 0)
     if job is None:
         return None
-    h, w = _blocked_shape(rows, cols, job[0], job[1])
-    if not _picture_batch_gate(count, h * w, most) or 3 * count * h * w > 2 ** 31 - 1:
+    shape = _none_on_refusal(jpegx.padded_shape, rows, cols, job[0]) if eight else _blocked_shape(rows, cols, job[0], job[1])
+    if shape is None or not gate(count, shape[0] * shape[1], most) or 3 * count * shape[0] * shape[1] > 2 ** 31 - 1:
         return None
     stack = _stacked_pixels(images, config, colour)
     if stack is None:
         return None
-    import jpegx
-    blobs = _none_on_refusal(jpegx.batch_compress_pictures_n, stack, *job, **_colour_kw(colour))
+    blobs = _none_on_refusal(jpegx.batch_compress_pictures if eight else jpegx.batch_compress_pictures_n, stack, *job, **_colour_kw(colour))
     if blobs is None:
         return None
     header = file_format.create_header(config)          # file_format.generate_data: the header, then <L length + bytes per band
@@ -1168,8 +1200,10 @@ def compress_pictures(images, config, colour=None):
     _picture_pixels; all of the configured size; with colour='rgb' all of mode RGB) whose planes hold at most
     DCTN_PICTURE_BATCH_COMPRESS_MAX_SAMPLES samples, under a configuration the device jobs admit (_compress_job_n: dct_size
     other than 8) go to the device as ONE batch; everything else, and every refusal of the batch -- a BadRleCodeError included,
-    so that the failing picture is named as before -- is that loop.  dct_size 8 is the loop: its batch entries take
-    block_size 1, 2, 4 and whole tiles only."""
+    so that the failing picture is named as before -- is that loop.  dct_size 8 has the same road (_job_config_8: every
+    block_size 1..255 and every picture size; jpegx.batch_compress_pictures) behind gates of its own,
+    DCT8_PICTURE_BATCH_MIN_PICTURES and DCT8_PICTURE_BATCH_COMPRESS_MAX_SAMPLES; the first ships as None, so dct_size 8 is the
+    loop until a caller sets it."""
     _check_colour(colour)
     if not isinstance(images, np.ndarray):
         images = list(images)
@@ -1199,11 +1233,10 @@ def _container_bands(container, header):
 
 def _decompress_picture_batch(containers, colour):
     """uint8 [n][height][width][3] by the batch road, or None (see _compress_picture_batch): all containers carry one and
-    the same header and coded bands, and _decompress_job_n admits the configuration."""
-    most = DCTN_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES
+    the same header and coded bands, and _decompress_job_n -- for dct_size 8 _decode_job_8 -- admits the configuration."""
     count = len(containers)
-    if not _picture_batch_gate(count, 0, most) or not _stock_registry() or not _device_usable():
-        return None
+    if not (_picture_batch_gate(count, 0, None) or _picture_batch_gate_8(count, 0, None)) or not _stock_registry() or not _device_usable():
+        return None                                     # neither road's count gate admits them: nothing is parsed
     first = containers[0]
     if not isinstance(first, (bytes, bytearray)) or len(first) < 2:
         return None
@@ -1215,13 +1248,26 @@ def _decompress_picture_batch(containers, colour):
         config = file_format.get_header(header)
     except Exception:
         return None                                     # the loop names the fault
+    import jpegx
+    if _accelerated(config):
+        most = DCT8_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES
+        job = _decode_job_8(config) if _picture_batch_gate_8(count, 0, most) else None
+        if job is None or not all(_is_coded(b) for picture in blobs for b in picture):
+            return None
+        bs, mode, param = job[2:]
+        shape = _none_on_refusal(jpegx.padded_shape, config.height, config.width, bs)
+        if shape is None or not _picture_batch_gate_8(count, shape[0] * shape[1], most) or 3 * count * shape[0] * shape[1] > 2 ** 31 - 1:
+            return None
+        return _none_on_refusal(jpegx.batch_decompress_pictures, blobs, config.height, config.width, bs, mode, param, **_colour_kw(colour))
+    most = DCTN_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES
+    if not _picture_batch_gate(count, 0, most):
+        return None
     job = _decompress_job_n(config, [b for picture in blobs for b in picture], 0)
     if job is None:
         return None
     h, w = _blocked_shape(*job[:4])
     if not _picture_batch_gate(count, h * w, most) or 3 * count * h * w > 2 ** 31 - 1:
         return None
-    import jpegx
     return _none_on_refusal(jpegx.batch_decompress_pictures_n, blobs, *job, **_colour_kw(colour))
 
 
@@ -1229,7 +1275,8 @@ def decompress_pictures_u8(containers, colour=None):
     """[np.asarray(Jpeg.decompress(c)) for c in containers] as uint8 arrays (height, width, 3), sample for sample; with
     colour='rgb', of Jpeg.decompress_rgb(c).  The batch road under the conditions of compress_pictures (containers that all
     carry one and the same header and coded bands in place of the pictures; DCTN_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES; a
-    whole divisor, as the decoding jobs ask), else that loop, which names the container and the fault."""
+    whole divisor, as the decoding jobs ask; dct_size 8: _decode_job_8 and DCT8_PICTURE_BATCH_DECOMPRESS_MAX_SAMPLES), else that
+    loop, which names the container and the fault."""
     _check_colour(colour)
     containers = list(containers)
     stack = _decompress_picture_batch(containers, colour) if containers else None

@@ -583,8 +583,8 @@ int jpegx_inflate_crop_pack_stacked_u8(const uint8_t *d_planes, int npictures, i
  * npictures pictures of nbands bands IS the band batch above of nplanes = nbands * npictures planes, plane p * nbands + k
  * band k of picture p: the compress workspace is jpegx_batch_workspace_bytes_n's, the worst case jpegx_batch_max_bytes_n's,
  * the verdicts and the plane index jpegx_batch_compress_status_n's, the small-footprint road jpegx_batch_emit_n's -- all
- * called with that nplanes -- and the limits are theirs.  Only what differs has an entry here.  dct_size 8 is not served:
- * its batch entries take block_size 1, 2, 4 and shapes that are multiples of 8 * block_size only.
+ * called with that nplanes -- and the limits are theirs.  Only what differs has an entry here.  dct_size 8 has entries of
+ * its own, jpegx_batch_compress_pictures / jpegx_batch_decompress_pictures below.
  * group_planes: a POSITIVE MULTIPLE of nbands (anything else is JPEGX_E_INVALID; 0 is not taken, because the band entries
  * would place the pieces of the workspace differently for it): groups are whole pictures.
  * jpegx_batch_group_planes_pictures_n (host arithmetic) recommends the largest multiple of nbands whose planes stay within
@@ -618,6 +618,51 @@ int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned lon
                                       int nbands, int rows, int cols, int bs, int N, int mode, double param, int colour,
                                       int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                       jpegx_stream_t stream);
+
+/* ---- batch codec for whole pictures at dct_size 8 (csrc/jpegx_picture_u8.hip, csrc/jpegx_batch.cpp) -------------------
+ * jpegx_picture_planes_stacked_u8 (enqueue only): pictures stacked [npictures * rows][pitch], every row cols * nbands
+ * interleaved bytes (no alignment asked; never written) -> the padded RAW uint8 planes of the 8x8 batch, stacked picture-major
+ * [npictures * nbands * H * bs][out_pitch], (H, W) = jpegx_padded_shape(rows, cols, bs), plane p * nbands + k band k of
+ * picture p:   out[(p, k)][y][x] = model_p[src(y)][src(x)][k],   src of jpegx_pad_edges per axis,
+ * model_p picture p itself or, with colour = 1 (nbands 3 only), its Pillow YCbCr (jpegx_rgb_to_ycbcr_u8's tables) -- byte for
+ * byte what jpegx_rgb_to_ycbcr_u8 -> jpegx_deinterleave_u8 -> jpegx_pad_edges make, in one pass and at any height.  Every
+ * clamp is against the picture's own last row and column; exactly W * bs bytes of every output row are written.
+ * Checked before any device work: bs in 1..255 (else JPEGX_E_UNSUPPORTED); nbands in 1..JPEGX_MAX_IMAGE_BANDS, colour,
+ * rows, cols >= 1, npictures * rows and npictures * nbands * H * bs each <= 2^31 - 1, pitch >= cols * nbands, out_pitch >=
+ * W * bs and a multiple of 16, d_out 16-byte aligned (else JPEGX_E_INVALID).                                             */
+int jpegx_picture_planes_stacked_u8(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                    int colour, int bs, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
+/* Jpeg.compress / Jpeg.decompress of the reference (pipeline/__init__.py:98-124) for every picture of a stack, with colour
+ * = 1 behind / through the conversions of compress.py:9 and decompress.py:9-10, at dct_size 8 and every block_size 1..255.
+ * The stack IS the 8x8 batch above of nplanes = nbands * npictures planes of (H, W) = jpegx_padded_shape(rows, cols, bs),
+ * picture-major: the workspace of jpegx_batch_pictures_workspace_bytes BEGINS with the layout of
+ * jpegx_batch_workspace_bytes(nplanes, H, W), so jpegx_batch_compress_status and jpegx_batch_emit, called with that
+ * nplanes, H, W, give the verdicts, the plane index and the small-footprint road (d_out == NULL: sizes only), and
+ * jpegx_batch_max_bytes(nplanes, H, W) is the worst case.  Behind it lies the front end's scratch.
+ * jpegx_batch_compress_pictures (enqueue only) takes one of two roads, chosen as the host jobs choose:
+ *   bs in {1, 2, 4} and W * bs a multiple of 16: jpegx_picture_planes_stacked_u8 over the whole stack, the sized uint8
+ *     forward kernel on the tall plane, scan, plane index, guarded emitter;
+ *   every other case, per group of whole pictures: jpegx_band_planes_packed_stacked_n at N = 8 into a float64 scratch of
+ *     group_planes planes, jpegx_forward_fused_f64 into the group's blocks of the int16 stream; after the last group one
+ *     sizing pass over all blocks, scan, index, emit.
+ * group_planes: a positive multiple of nbands on both roads (the uint8 road does not use it otherwise);
+ * jpegx_batch_group_planes_pictures_n(nbands, rows, cols, bs, 8) recommends one.  Refused before any launch, with
+ * jpegx_batch_compress's codes: an unknown quantiser, a keep that is no non-negative integer, a divisor that is zero or not
+ * finite (JPEGX_E_INVALID) or below 0.5 (JPEGX_E_UNSUPPORTED, on both roads), more than 2^31 - 64 blocks, more than
+ * 2^31 - 1 rows in the stack; and rows * cols or a float64 group's samples beyond 2^31 - 1.  The workspace function
+ * returns 0 for a shape that is refused.                                                                              */
+size_t jpegx_batch_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes);
+int jpegx_batch_compress_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                  int colour, int bs, int mode, double param, int group_planes, void *d_workspace,
+                                  uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+/* The way back, NOT enqueue-only: jpegx_batch_decompress with block_size 1 and JPEGX_OUT_U8 into nplanes POOLED planes
+ * [nplanes * H][W] inside the workspace (256-byte aligned), and only after it has answered JPEGX_OK
+ * jpegx_inflate_crop_pack_stacked_u8 into d_out [npictures * rows][out_pitch], out_pitch >= cols * nbands: the
+ * replication, both crops, the np.dstack and, with colour = 1, Pillow's RGB.  A refused stream writes NOTHING to d_out.   */
+size_t jpegx_batch_decompress_pictures_workspace_bytes(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs);
+int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures,
+                                    int nbands, int rows, int cols, int bs, int mode, double param, int colour,
+                                    void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
 
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
@@ -1021,6 +1066,16 @@ int jpegx_batch_decompress_pictures_n_on(int device, const uint8_t *d_bytes, con
                                          int npictures, int nbands, int rows, int cols, int bs, int N, int mode, double param,
                                          int colour, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                          jpegx_stream_t stream);
+int jpegx_picture_planes_stacked_u8_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                       ptrdiff_t pitch, int colour, int bs, uint8_t *d_out, ptrdiff_t out_pitch,
+                                       jpegx_stream_t stream);
+int jpegx_batch_compress_pictures_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                     ptrdiff_t pitch, int colour, int bs, int mode, double param, int group_planes,
+                                     void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_decompress_pictures_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
+                                       int npictures, int nbands, int rows, int cols, int bs, int mode, double param,
+                                       int colour, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
+                                       jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
