@@ -1,0 +1,332 @@
+// jpegx_band_set_n.hip -- steps 0-3 of the reference and their way back (jpegx_band_n.hip) for a SET of pixel-interleaved
+// pictures of UNEQUAL sizes, each at its own place in one device buffer (the table of jpegx_picture_set_table,
+// jpegx_batch_set_n.cpp): Padding (pipeline/padding.py:8-12), SubSampling (pipeline/subsampling.py:9-11), DCTPadding
+// (pipeline/dct_padding.py:8-9) and Normalization (pipeline/normalization.py:7-8) of every band of every picture as ONE gather,
+// and DCTPadding.invert (pipeline/dct_padding.py:11-21), SubSampling.invert (pipeline/subsampling.py:13-14), Padding.invert
+// (pipeline/padding.py:14-16) and the np.dstack of pipeline/__init__.py:121 as ONE scatter.
+//
+// Planes of unequal widths cannot be stacked into one tall plane.  Their BLOCKS can: the block strip [nblk * N][N] with pitch
+// N holds block g in rows g * N .. g * N + N - 1, that is in the N * N consecutive elements from g * N * N on, and
+// jpegx_forward_fused_n / jpegx_inverse_fused_n take it as a plane of width N (one block a block row).  Block order is
+// picture-major, then band, then block-row-major inside the band: plane (p, k) starts at block first_p + k * nb_p.
+//
+// The gather's lane owns VEC consecutive samples of one block row of one sample POSITION of a picture (VEC = 4, 2, 1 for N a
+// multiple of 4, even, odd) and writes them for all the picture's bands: every input byte is read once, and with VEC > 1 every
+// store is 16 bytes wide and 16-byte aligned (the strip is, and (g * N * N + i * N + j) * 8 is a multiple of 8 * VEC).
+// Consecutive lanes walk a block's N * N elements, then the next block of the band: per band a wave stores 64 * VEC
+// consecutive doubles.  The scatter's lane owns PIX consecutive pixels of one output row of a picture, as
+// k_inflate_crop_pack_stacked_u8's does.
+//
+// The picture of an item is found by a binary search over a prefix of the table (block positions for the gather, lanes for the
+// scatter): log2(k + 1) steps.  Up to SET_LDS_PICTURES pictures the prefix is copied to LDS once per workgroup and searched
+// there; beyond that the search reads the table in global memory, where its upper levels stay in the caches.
+// Part of libjpegx.so (C ABI: include/jpegx.h).
+#include <limits.h>
+
+#include "jpegx_colour_device.h"
+
+namespace {
+
+using Head = jpegx_picture_set_head;
+using Entry = jpegx_picture_set_entry;
+
+constexpr unsigned COLOUR_MAX_BLOCKS = 1024;       // k_colour_u8's: four 256-thread workgroups per CU
+constexpr int SET_LDS_PICTURES = 1023;             // the prefix of that many pictures + the end: 8 KiB of LDS
+
+template <bool INVERSE>
+__device__ __forceinline__ void fill_colour_tables(int16_t *t)
+{
+    if (threadIdx.x < (INVERSE ? INV_TABLES : FWD_TABLES) * 32)
+        reinterpret_cast<uint4 *>(t)[threadIdx.x] = reinterpret_cast<const uint4 *>(INVERSE ? g_colour_inv : g_colour_fwd)[threadIdx.x];
+}
+
+// the prefix of pictures p0 .. p0 + k (the end included), relative to picture p0: block POSITIONS (blocks of one band) for the
+// gather, lanes for the scatter
+template <bool LANES>
+__device__ __forceinline__ unsigned long long prefix_of(const Entry *e, int q, int nbands)
+{
+    return LANES ? (unsigned long long)(e[q].lanes - e[0].lanes) : (unsigned long long)(e[q].first - e[0].first) / (unsigned)nbands;
+}
+
+template <bool LANES>
+__device__ __forceinline__ void fill_prefix(unsigned long long *pre, const Entry *e, int k, int nbands)
+{
+    if (k > SET_LDS_PICTURES) return;
+    for (int q = threadIdx.x; q <= k; q += 256) pre[q] = prefix_of<LANES>(e, q, nbands);
+}
+
+// the largest q in 0 .. k - 1 whose prefix is at most v (v is below the prefix of k; the prefix rises strictly)
+template <bool LANES>
+__device__ __forceinline__ int find_picture(const unsigned long long *pre, const Entry *e, int k, int nbands, unsigned long long v,
+                                            unsigned long long *start)
+{
+    int lo = 0, hi = k;
+    unsigned long long at = 0;
+    if (k <= SET_LDS_PICTURES) {
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            const unsigned long long m = pre[mid];
+            if (m <= v) { lo = mid; at = m; } else hi = mid;
+        }
+    } else {
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            const unsigned long long m = prefix_of<LANES>(e, mid, nbands);
+            if (m <= v) { lo = mid; at = m; } else hi = mid;
+        }
+    }
+    *start = at;
+    return lo;
+}
+
+// one pixel into the NB sums, converted first where COLOUR says so (jpegx_band_n.hip's add_pixel)
+template <int NB, bool COLOUR>
+__device__ __forceinline__ void add_pixel(const int16_t *t, const uint8_t *one, unsigned (&s)[NB])
+{
+    if (COLOUR) {
+        unsigned o0, o1, o2;
+        colour_forward_px(t, one[0], one[1 % NB], one[2 % NB], o0, o1, o2);
+        s[0] += o0; s[1 % NB] += o1; s[2 % NB] += o2;
+    } else {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s[k] += one[k];
+    }
+}
+
+// The gather.  e: the table's entries from picture p0 on (k of them and the end); items = positions * N * N / VEC.  ipb: items
+// of one block, N * N / VEC.  Sample (y, x) of band b of a picture is k_band_planes_packed_stacked_n's: the tile at
+// (min(y, prows - 1) * bs, min(x, pcols - 1) * bs), its rows and columns clamped to the picture's last, the exact integer sum,
+// one division.  No read leaves [rows] x [cols * NB] bytes of the picture's rows; writes stay inside the k pictures' blocks.
+template <int NB, bool COLOUR, int VEC>
+__global__ __launch_bounds__(256) void k_picture_set_blocks_n(const uint8_t *__restrict__ px, const Entry *__restrict__ e, int k, int bs, int N,
+                                                              unsigned ipb, unsigned long long items, double *__restrict__ out)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? FWD_TABLES * 256 : 8];
+    __shared__ unsigned long long pre[SET_LDS_PICTURES + 1];
+    if (COLOUR) fill_colour_tables<false>(t);
+    fill_prefix<false>(pre, e, k, NB);
+    __syncthreads();
+    const double area = (double)(bs * bs);
+    const size_t nn = (size_t)N * N;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * 256u) {
+        const unsigned long long pos = i / ipb;                              // block position among the k pictures'
+        const unsigned el = (unsigned)(i - pos * ipb) * VEC;                 // first element of the lane inside the block
+        unsigned long long start;
+        const int q = find_picture<false>(pre, e, k, NB, pos, &start);
+        const Entry pic = e[q];
+        const unsigned b = (unsigned)(pos - start);                          // block of the band, row-major
+        const unsigned by = b / (unsigned)pic.wb, bx = b - by * (unsigned)pic.wb;
+        const unsigned bi = el / (unsigned)N, bj = el - bi * (unsigned)N;
+        const int y = (int)(by * N + bi), x0 = (int)(bx * N + bj);
+        const uint8_t *base = px + pic.offset;
+        const int r0 = min(y, pic.prows - 1) * bs, rlast = pic.rows - 1 - r0;   // r0 < rows: the tile starts inside the picture
+        unsigned s[VEC][NB];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+            for (int c = 0; c < NB; ++c) s[v][c] = 0;
+            const int c0 = min(x0 + v, pic.pcols - 1) * bs, clast = pic.cols - 1 - c0;      // c0 < cols
+            if (bs <= clast + 1) {                                           // the tile's columns are all there: no clamp per pixel
+                for (int u = 0; u < bs; ++u) {
+                    const uint8_t *row = base + (size_t)(r0 + min(u, rlast)) * (size_t)pic.pitch + (size_t)c0 * NB;
+                    for (int w = 0; w < bs; ++w) add_pixel<NB, COLOUR>(t, row + w * NB, s[v]);
+                }
+            } else {
+                for (int u = 0; u < bs; ++u) {
+                    const uint8_t *row = base + (size_t)(r0 + min(u, rlast)) * (size_t)pic.pitch + (size_t)c0 * NB;
+                    for (int w = 0; w < bs; ++w) add_pixel<NB, COLOUR>(t, row + min(w, clast) * NB, s[v]);
+                }
+            }
+        }
+        const size_t g0 = (size_t)(pic.first - e[0].first) + b;              // the block in band 0
+#pragma unroll
+        for (int c = 0; c < NB; ++c) {
+            double *dst = out + (g0 + (size_t)c * (unsigned)pic.nb) * nn + el;
+            if (VEC == 1) {
+                dst[0] = (double)s[0][c] / area;
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; v += 2)
+                    reinterpret_cast<double2 *>(dst)[v / 2] = make_double2((double)s[v][c] / area, (double)s[(v + 1) % VEC][c] / area);
+            }
+        }
+    }
+}
+
+// The scatter.  Item = lane of k_inflate_crop_pack_stacked_u8: PIX consecutive pixels of one output row, whole 16-byte units.
+// Source sample (y / bs, x / bs) of plane (q, c) lies in block (sy / N) * wb + sx / N of the plane at element (sy % N) * N + sx % N;
+// a (block column, column inside the block) pair is stepped with the (quotient, remainder) pair of x / bs.  sy <= (rows - 1) / bs < H
+// and sx <= (cols - 1) / bs < W: no read leaves plane (q, c).  Bytes are written for x < cols of rows y < rows only.
+template <int NB, bool COLOUR>
+__global__ __launch_bounds__(256) void k_picture_set_pixels_u8(const uint8_t *__restrict__ strip, const Entry *__restrict__ e, int k, unsigned bs, int N,
+                                                               unsigned long long items, uint8_t *__restrict__ out)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    constexpr int UNIT = NB == 3 ? 48 : 16, PIX = UNIT / NB;
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? INV_TABLES * 256 : 8];
+    __shared__ unsigned long long pre[SET_LDS_PICTURES + 1];
+    if (COLOUR) fill_colour_tables<true>(t);
+    fill_prefix<true>(pre, e, k, NB);
+    __syncthreads();
+    const size_t nn = (size_t)N * N;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * 256u) {
+        unsigned long long start;
+        const int q = find_picture<true>(pre, e, k, NB, i, &start);
+        const Entry pic = e[q];
+        const unsigned chunks = ((unsigned)pic.cols + PIX - 1u) / PIX;
+        const unsigned long long li = i - start;                             // below rows * chunks <= rows * cols < 2^31
+        const unsigned y = (unsigned)(li / chunks), x0 = ((unsigned)li - y * chunks) * (unsigned)PIX;
+        const unsigned sy = y / bs;
+        const unsigned by = sy / (unsigned)N, bi = sy - by * (unsigned)N;
+        // element (bi, 0) of block (by, 0) of band 0; a block on: nn, a band on: nb * nn
+        const uint8_t *src = strip + ((size_t)(pic.first - e[0].first) + (size_t)by * (unsigned)pic.wb) * nn + (size_t)bi * N;
+        const size_t band = (size_t)(unsigned)pic.nb * nn;
+        unsigned sx = x0 / bs, r = x0 - sx * bs;
+        unsigned bx = sx / (unsigned)N, bj = sx - bx * (unsigned)N;
+        const int left = pic.cols - (int)x0;                                 // >= 1: pixels of this lane inside the row
+        unsigned v[NB], w[UNIT / 4];
+#pragma unroll
+        for (int c = 0; c < NB; ++c) v[c] = 0;
+#pragma unroll
+        for (int d = 0; d < UNIT / 4; ++d) w[d] = 0;
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            if (j < left) {
+                if (j == 0 || r == 0) {
+#pragma unroll
+                    for (int c = 0; c < NB; ++c) v[c] = src[c * band + (size_t)bx * nn + bj];
+                    if (COLOUR) {
+                        unsigned o0, o1, o2;
+                        colour_inverse_px(t, v[0], v[1 % NB], v[2 % NB], o0, o1, o2);
+                        v[0] = o0; v[1 % NB] = o1; v[2 % NB] = o2;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NB; ++c) w[(j * NB + c) >> 2] |= v[c] << (8 * ((j * NB + c) & 3));
+                if (++r == bs) {
+                    r = 0;
+                    if (++bj == (unsigned)N) { bj = 0; ++bx; }
+                }
+            }
+        }
+        uint8_t *dst = out + pic.offset + (size_t)y * (size_t)pic.pitch + (size_t)x0 * NB;
+        if (left >= PIX && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+#pragma unroll
+            for (int d = 0; d < UNIT / 16; ++d) reinterpret_cast<uint4 *>(dst)[d] = make_uint4(w[4 * d], w[4 * d + 1], w[4 * d + 2], w[4 * d + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < UNIT; ++j)
+                if (j / NB < left) dst[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
+// grid of an instantiation: all the items without COLOUR, at most COLOUR_MAX_BLOCKS workgroups with it
+template <bool COLOUR>
+unsigned set_blocks(unsigned long long items)
+{
+    const unsigned long long blocks = (items + 255u) / 256u;               // below 2^31: the entries check it
+    return COLOUR && blocks > COLOUR_MAX_BLOCKS ? COLOUR_MAX_BLOCKS : (unsigned)blocks;
+}
+
+template <int NB, bool COLOUR>
+void launch_blocks(const uint8_t *px, const Entry *e, int k, int bs, int N, unsigned long long positions, double *out, hipStream_t st)
+{
+    const unsigned nn = (unsigned)(N * N);
+    if (N % 4 == 0) {
+        const unsigned long long items = positions * (nn / 4);
+        hipLaunchKernelGGL((k_picture_set_blocks_n<NB, COLOUR, 4>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn / 4, items, out);
+    } else if (N % 2 == 0) {
+        const unsigned long long items = positions * (nn / 2);
+        hipLaunchKernelGGL((k_picture_set_blocks_n<NB, COLOUR, 2>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn / 2, items, out);
+    } else {
+        const unsigned long long items = positions * nn;
+        hipLaunchKernelGGL((k_picture_set_blocks_n<NB, COLOUR, 1>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn, items, out);
+    }
+}
+
+template <int NB, bool COLOUR>
+void launch_pixels(const uint8_t *strip, const Entry *e, int k, int bs, int N, unsigned long long items, uint8_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_picture_set_pixels_u8<NB, COLOUR>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, strip, e, k, (unsigned)bs, N, items, out);
+}
+
+// what both entries check of their arguments: JPEGX_OK and the head, or the refusal
+int check_range(const char *who, const void *a, const void *h_table, const void *d_table, int p0, int k, int colour, const void *b, const Head **head)
+{
+    char buf[200];
+    if (!a || !h_table || !d_table || !b) {
+        snprintf(buf, sizeof(buf), "%s: null pointer", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    const Head *h = static_cast<const Head *>(h_table);
+    if (h->magic != JPEGX_PICTURE_SET_MAGIC) {
+        snprintf(buf, sizeof(buf), "%s: h_table is not a table of jpegx_picture_set_table", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (p0 < 0 || k < 1 || p0 > h->npictures - k) {
+        snprintf(buf, sizeof(buf), "%s: pictures %d .. %d are not pictures of the table's %d", who, p0, p0 + k - 1, h->npictures);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if ((colour != 0 && colour != 1) || (colour == 1 && h->nbands != 3)) {
+        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    if (reinterpret_cast<uintptr_t>(d_table) % 8) {
+        snprintf(buf, sizeof(buf), "%s: d_table must be 8-byte aligned", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    *head = h;
+    return JPEGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpegx_picture_set_blocks_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour, double *d_strip,
+                               jpegx_stream_t stream)
+{
+    const Head *h = nullptr;
+    const int rc = check_range("picture_set_blocks_n", d_pixels, h_table, d_table, p0, k, colour, d_strip, &h);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_strip) % 16) return fail(JPEGX_E_INVALID, "picture_set_blocks_n: the strip must be 16-byte aligned");
+    const Entry *he = reinterpret_cast<const Entry *>(h + 1) + p0;
+    const Entry *de = reinterpret_cast<const Entry *>(static_cast<const unsigned char *>(d_table) + sizeof(Head)) + p0;
+    const unsigned long long positions = (unsigned long long)(he[k].first - he[0].first) / (unsigned)h->nbands;   // * N * N <= 2^31 - 1: the table's limit
+    hipStream_t st = (hipStream_t)stream;
+    if (colour) launch_blocks<3, true>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st);
+    else switch (h->nbands) {
+    case 1: launch_blocks<1, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
+    case 2: launch_blocks<2, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
+    case 3: launch_blocks<3, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
+    default: launch_blocks<4, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_picture_set_pixels_u8(const uint8_t *d_strip, const void *h_table, const void *d_table, int p0, int k, int colour, uint8_t *d_out,
+                                jpegx_stream_t stream)
+{
+    const Head *h = nullptr;
+    const int rc = check_range("picture_set_pixels_u8", d_strip, h_table, d_table, p0, k, colour, d_out, &h);
+    if (rc) return rc;
+    const Entry *he = reinterpret_cast<const Entry *>(h + 1) + p0;
+    const Entry *de = reinterpret_cast<const Entry *>(static_cast<const unsigned char *>(d_table) + sizeof(Head)) + p0;
+    const unsigned long long items = (unsigned long long)(he[k].lanes - he[0].lanes);
+    if ((items + 255u) / 256u > 0x7FFFFFFFull) return fail(JPEGX_E_INVALID, "picture_set_pixels_u8: more than 2^39 lanes in one launch");
+    hipStream_t st = (hipStream_t)stream;
+    if (colour) launch_pixels<3, true>(d_strip, de, k, h->bs, h->N, items, d_out, st);
+    else switch (h->nbands) {
+    case 1: launch_pixels<1, false>(d_strip, de, k, h->bs, h->N, items, d_out, st); break;
+    case 2: launch_pixels<2, false>(d_strip, de, k, h->bs, h->N, items, d_out, st); break;
+    case 3: launch_pixels<3, false>(d_strip, de, k, h->bs, h->N, items, d_out, st); break;
+    default: launch_pixels<4, false>(d_strip, de, k, h->bs, h->N, items, d_out, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+}  // extern "C"

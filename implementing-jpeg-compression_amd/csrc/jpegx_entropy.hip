@@ -165,6 +165,26 @@ __global__ __launch_bounds__(64) void k_plane_index(int nplanes, int nb, const v
     plane_offsets[p] = off;
 }
 
+// The same for planes of UNEQUAL block counts (a set of pictures of unequal sizes, jpegx_batch_set_n.cpp): plane p's first
+// block is first[p], read from a device array of nplanes + 1 rising block indices with first[nplanes] = nblk, in place of
+// p nb.  Nothing else differs: a first block need not be a multiple of 64, a wave may straddle planes, and the head, the
+// offsets and the total behind the last plane are k_plane_index's.
+__global__ __launch_bounds__(64) void k_plane_index_ragged(int nplanes, const long long *__restrict__ first, const void *ws, int nblk, BatchHead *head,
+                                                           unsigned long long *plane_offsets, unsigned long long out_cap)
+{
+    const Workspace W = carve(const_cast<void *>(ws), nblk);
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p == 0) { head->out_cap = out_cap; head->pad = 0; }
+    if (p > nplanes) return;
+    if (p == nplanes) { plane_offsets[p] = *W.total; return; }
+    const long long b = first[p];
+    if (b < 0 || b >= nblk) { plane_offsets[p] = *W.total; return; }     // not a block of the stream: nothing is read for it
+    const int w = (int)(b >> 6);
+    unsigned long long off = W.chunk_off[w / SCAN_CHUNK] + W.wave_off[w];
+    for (long long k = (long long)w * 64; k < b; ++k) off += W.block_bytes[k];
+    plane_offsets[p] = off;
+}
+
 // Two-level exclusive scan of the per-wave totals.  Level 1: one workgroup per SCAN_CHUNK waves,
 // 16 bytes per thread (coalesced), wave scan by __shfl_up + a 16-entry LDS carry.  Level 2: one
 // wave walks the chunk totals (<= 128 for 2^31 blocks).
@@ -524,6 +544,19 @@ int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, 
     BatchHead *head = static_cast<BatchHead *>(d_index);
     hipLaunchKernelGGL(k_plane_index, dim3((nplanes + 1 + 63) / 64), dim3(64), 0, (hipStream_t)stream, nplanes, (int)blocks_per_plane, d_workspace,
                        (int)nblocks, head, reinterpret_cast<unsigned long long *>(head + 1), (unsigned long long)out_cap);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+// the same for planes of unequal block counts: d_first holds nplanes + 1 rising block indices, d_first[nplanes] = nblocks
+int jpegx_internal_entropy_plane_index_ragged(int nplanes, const long long *d_first, long long nblocks, const void *d_workspace, void *d_index,
+                                              size_t out_cap, jpegx_stream_t stream)
+{
+    if (!d_workspace || !d_index || !d_first || nplanes <= 0 || nblocks < nplanes || nblocks > 0x7FFFFFC0LL || reinterpret_cast<uintptr_t>(d_first) % 8)
+        return fail(JPEGX_E_INVALID, "bad plane index arguments");
+    BatchHead *head = static_cast<BatchHead *>(d_index);
+    hipLaunchKernelGGL(k_plane_index_ragged, dim3((nplanes + 1 + 63) / 64), dim3(64), 0, (hipStream_t)stream, nplanes, d_first, d_workspace, (int)nblocks,
+                       head, reinterpret_cast<unsigned long long *>(head + 1), (unsigned long long)out_cap);
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;
 }

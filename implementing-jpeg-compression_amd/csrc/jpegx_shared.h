@@ -28,6 +28,8 @@ int jpegx_internal_entropy_emit_n_guarded(const int32_t *d_zz, long long nblocks
                                           size_t out_cap, jpegx_stream_t stream);   // jpegx_entropy_n.hip: jpegx_entropy_emit_n for the batch entries
 int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, const void *d_workspace, void *d_index, size_t out_cap,
                                        jpegx_stream_t stream);
+int jpegx_internal_entropy_plane_index_ragged(int nplanes, const long long *d_first, long long nblocks, const void *d_workspace, void *d_index,
+                                              size_t out_cap, jpegx_stream_t stream);   // planes of unequal block counts (jpegx_batch_set_n.cpp)
 // jpegx_hostpipe.cpp: a job context of the current device borrowed for one call (host_roundtrip, jpegx_internal.h)
 int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream);
 void jpegx_internal_pool_release(void);

@@ -209,6 +209,18 @@ SIGNATURES = {
     "jpegx_batch_compress_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
     "jpegx_batch_decompress_pictures_workspace_bytes": [_sz, _int, _int, _int, _int, _int],
     "jpegx_batch_decompress_pictures": [_vp, _vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _vp, _vp, _pd, _vp],
+    "jpegx_picture_set_table_bytes": [_int],
+    "jpegx_picture_set_table": [_vp, _int, _int, _int, _int, _vp, _c.POINTER(_c.c_longlong)],
+    "jpegx_picture_set_blocks_n": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
+    "jpegx_picture_set_pixels_u8": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
+    "jpegx_batch_set_workspace_bytes_n": [_vp, _c.c_longlong],
+    "jpegx_batch_set_max_bytes_n": [_vp],
+    "jpegx_batch_compress_picture_set_n": [_vp, _vp, _vp, _int, _int, _dbl, _c.c_longlong, _vp, _vp, _sz, _vp],
+    "jpegx_batch_compress_status_set_n": [_vp, _vp, _c.c_longlong, _c.POINTER(_c.c_ulonglong), _vp, _vp],
+    "jpegx_batch_emit_set_n": [_vp, _vp, _vp, _c.c_longlong, _vp, _sz, _vp],
+    "jpegx_batch_groups_set_n": [_vp, _vp, _c.c_longlong, _vp, _c.POINTER(_int)],
+    "jpegx_batch_decompress_set_workspace_bytes_n": [_sz, _vp, _c.c_longlong],
+    "jpegx_batch_decompress_picture_set_n": [_vp, _vp, _vp, _vp, _int, _dbl, _int, _c.c_longlong, _vp, _vp, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -238,14 +250,18 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_inflate_crop_stacked_u8", "jpegx_batch_compress_n", "jpegx_batch_compress_status_n", "jpegx_batch_emit_n",
               "jpegx_batch_decompress_n", "jpegx_band_planes_packed_stacked_n", "jpegx_inflate_crop_pack_stacked_u8",
               "jpegx_batch_compress_pictures_n", "jpegx_batch_decompress_pictures_n", "jpegx_picture_planes_stacked_u8",
-              "jpegx_batch_compress_pictures", "jpegx_batch_decompress_pictures"):
+              "jpegx_batch_compress_pictures", "jpegx_batch_decompress_pictures", "jpegx_picture_set_blocks_n",
+              "jpegx_picture_set_pixels_u8", "jpegx_batch_compress_picture_set_n", "jpegx_batch_compress_status_set_n",
+              "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
             "jpegx_batch_max_bytes": _sz, "jpegx_batch_decompress_workspace_bytes": _sz, "jpegx_batch_workspace_bytes_n": _sz,
             "jpegx_batch_max_bytes_n": _sz, "jpegx_batch_decompress_workspace_bytes_n": _sz,
             "jpegx_batch_decompress_pictures_workspace_bytes_n": _sz, "jpegx_batch_pictures_workspace_bytes": _sz,
-            "jpegx_batch_decompress_pictures_workspace_bytes": _sz}   # everything else returns int
+            "jpegx_batch_decompress_pictures_workspace_bytes": _sz, "jpegx_picture_set_table_bytes": _sz,
+            "jpegx_batch_set_workspace_bytes_n": _sz, "jpegx_batch_set_max_bytes_n": _sz,
+            "jpegx_batch_decompress_set_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -1900,6 +1916,206 @@ def batch_decompress_pictures_n(blobs, rows, cols, bs, n, mode="none", param=0.0
         din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
         batch_decompress_pictures_n_device(din.ptr, off, *pics, dws.ptr, dout.ptr, group_planes, None, mode, param, flag)
         return dout.download((k, rows, cols, nb), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the batch codec for a SET of pictures of unequal sizes at any DCT size but 8: each picture at its own place in one device
+# buffer, described by a table (jpegx_picture_set_table) that the entries take twice, as the host blob and as its device copy.
+# ---------------------------------------------------------------------------------------------
+PICTURE_DESC_DTYPE = np.dtype([("rows", np.int32), ("cols", np.int32), ("offset", np.uint64), ("pitch", np.int64)])
+PICTURE_SET_HEAD_DTYPE = np.dtype([("magic", np.uint32), ("npictures", np.int32), ("nbands", np.int32), ("bs", np.int32), ("N", np.int32),
+                                   ("pad", np.int32), ("total_blocks", np.int64)])
+PICTURE_SET_ENTRY_DTYPE = np.dtype([("offset", np.uint64), ("pitch", np.int64), ("first", np.int64), ("lanes", np.int64), ("rows", np.int32),
+                                    ("cols", np.int32), ("H", np.int32), ("W", np.int32), ("prows", np.int32), ("pcols", np.int32),
+                                    ("wb", np.int32), ("nb", np.int32)])
+
+
+class PictureSetTable:
+    """The host blob of jpegx_picture_set_table with views of its three parts: ``head`` (one record), ``entries`` (npictures + 1
+    records, the last the end) and ``plane_first`` (nbands * npictures + 1 block indices).  ``blob`` is what is uploaded."""
+
+    def __init__(self, blob, npictures, nbands, total_blocks):
+        self.blob, self.npictures, self.nbands, self.total_blocks = blob, int(npictures), int(nbands), int(total_blocks)
+        raw = blob.view(np.uint8)
+        self.head = raw[:32].view(PICTURE_SET_HEAD_DTYPE)[0]
+        self.entries = raw[32:32 + 64 * (self.npictures + 1)].view(PICTURE_SET_ENTRY_DTYPE)
+        at = 32 + 64 * (self.npictures + 1)
+        self.plane_first = raw[at:at + 8 * (self.npictures * self.nbands + 1)].view(np.int64)
+        self.nbytes = at + 8 * (self.npictures * self.nbands + 1)       # what the kernels read; the blob may be longer
+
+    @property
+    def ptr(self):
+        return self.blob.ctypes.data
+
+
+def picture_set_table(sizes, nbands, bs, n, offsets=None, pitches=None):
+    """The table of a set of pictures (jpegx_picture_set_table; host arithmetic, no device needed).  sizes: (rows, cols) per
+    picture; offsets: the byte offset of each picture's first pixel in one device buffer (default: the pictures back to
+    back); pitches: bytes from a row to the next (default cols * nbands).  Raises JpegxError for whatever the entry refuses."""
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    k = len(sizes)
+    desc = np.zeros(max(k, 1), dtype=PICTURE_DESC_DTYPE)
+    if pitches is None:
+        pitches = [c * int(nbands) for _, c in sizes]
+    if offsets is None:
+        offsets = np.concatenate([[0], np.cumsum([r * int(p) for (r, _), p in zip(sizes, pitches)], dtype=np.int64)])[:k]
+    for p, ((r, c), o, q) in enumerate(zip(sizes, offsets, pitches)):
+        desc[p] = (r, c, int(o), int(q))
+    blob = np.zeros(max(lib().jpegx_picture_set_table_bytes(k), 8) // 8, dtype=np.uint64)
+    total = ctypes.c_longlong(0)
+    check(lib().jpegx_picture_set_table(desc.ctypes.data, k, int(nbands), int(bs), int(n), blob.ctypes.data, ctypes.byref(total)),
+          "jpegx_picture_set_table")
+    return PictureSetTable(blob, k, nbands, total.value)
+
+
+def batch_set_workspace_bytes_n(table, group_samples=0):
+    return lib().jpegx_batch_set_workspace_bytes_n(table.ptr, int(group_samples))
+
+
+def batch_set_max_bytes_n(table):
+    return lib().jpegx_batch_set_max_bytes_n(table.ptr)
+
+
+def batch_decompress_set_workspace_bytes_n(nbytes, table, group_samples=0):
+    return lib().jpegx_batch_decompress_set_workspace_bytes_n(int(nbytes), table.ptr, int(group_samples))
+
+
+def batch_groups_set_n(plane_offsets, table, group_samples=0):
+    """The cut of a coded set into decoding groups on picture boundaries (jpegx_batch_groups_set_n; host arithmetic): the first
+    PICTURE of every group and, last, npictures."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (table.npictures * table.nbands + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    first = np.zeros(table.npictures + 1, dtype=np.int32)
+    ngroups = ctypes.c_int(0)
+    check(lib().jpegx_batch_groups_set_n(off.ctypes.data, table.ptr, int(group_samples), first.ctypes.data, ctypes.byref(ngroups)),
+          "jpegx_batch_groups_set_n")
+    return first[:ngroups.value + 1].copy()
+
+
+def picture_set_blocks_n_device(d_pixels, table, d_table, p0, k, d_strip, colour=0, stream=None, device=None):
+    """Enqueue jpegx_picture_set_blocks_n: pixels of pictures p0 .. p0 + k - 1 -> their float64 block strip at d_strip."""
+    args = (d_pixels, table.ptr, d_table, int(p0), int(k), int(colour), d_strip, stream)
+    L = lib()
+    check(L.jpegx_picture_set_blocks_n(*args) if device is None else L.jpegx_picture_set_blocks_n_on(int(device), *args),
+          "jpegx_picture_set_blocks_n")
+
+
+def picture_set_pixels_u8_device(d_strip, table, d_table, p0, k, d_out, colour=0, stream=None, device=None):
+    """Enqueue jpegx_picture_set_pixels_u8: the uint8 block strip of pictures p0 .. p0 + k - 1 -> their pixels in d_out."""
+    args = (d_strip, table.ptr, d_table, int(p0), int(k), int(colour), d_out, stream)
+    L = lib()
+    check(L.jpegx_picture_set_pixels_u8(*args) if device is None else L.jpegx_picture_set_pixels_u8_on(int(device), *args),
+          "jpegx_picture_set_pixels_u8")
+
+
+def batch_compress_picture_set_n_device(d_pixels, table, d_table, d_workspace, d_out, out_cap, mode="none", param=0.0, colour=0,
+                                        group_samples=0, stream=None, device=None):
+    """Enqueue jpegx_batch_compress_picture_set_n -> coded bytes at d_out (None: sizes only).  Verdict and plane index:
+    batch_compress_status_set_n."""
+    args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), float(param), int(group_samples), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress_picture_set_n(*args) if device is None else L.jpegx_batch_compress_picture_set_n_on(int(device), *args),
+          "jpegx_batch_compress_picture_set_n")
+
+
+def batch_compress_status_set_n(d_workspace, table, group_samples=0, stream=None, device=None):
+    """Synchronises; returns (rc, total, offsets) as batch_compress_status_n does."""
+    total = ctypes.c_ulonglong(0)
+    off = np.zeros(table.npictures * table.nbands + 1, dtype=np.uint64)
+    args = (d_workspace, table.ptr, int(group_samples), ctypes.byref(total), off.ctypes.data, stream)
+    L = lib()
+    rc = L.jpegx_batch_compress_status_set_n(*args) if device is None else L.jpegx_batch_compress_status_set_n_on(int(device), *args)
+    if rc not in (0, 1, -1):
+        check(rc, "jpegx_batch_compress_status_set_n")
+    return rc, total.value, off
+
+
+def batch_emit_set_n_device(d_workspace, table, d_table, d_out, out_cap, group_samples=0, stream=None, device=None):
+    args = (d_workspace, table.ptr, d_table, int(group_samples), d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_emit_set_n(*args) if device is None else L.jpegx_batch_emit_set_n_on(int(device), *args), "jpegx_batch_emit_set_n")
+
+
+def batch_decompress_picture_set_n_device(d_bytes, plane_offsets, table, d_table, d_workspace, d_out, mode="none", param=0.0, colour=0,
+                                          group_samples=0, stream=None, device=None):
+    """jpegx_batch_decompress_picture_set_n (synchronises the stream once per group); plane_offsets: nbands * npictures + 1 host
+    integers; every picture at its offset and pitch in d_out.  Raises JpegxError for whatever the entry refuses."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (table.npictures * table.nbands + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    args = (d_bytes, off.ctypes.data, table.ptr, d_table, mode_of(mode), float(param), int(colour), int(group_samples), d_workspace, d_out, stream)
+    L = lib()
+    check(L.jpegx_batch_decompress_picture_set_n(*args) if device is None else L.jpegx_batch_decompress_picture_set_n_on(int(device), *args),
+          "jpegx_batch_decompress_picture_set_n")
+
+
+def batch_compress_picture_set_n(pictures, bs, n, mode="none", param=0.0, colour=None, group_samples=0):
+    """A sequence of uint8 pictures [rows_p][cols_p][nb], sizes as they come -> per picture the list of its nb bands' bytes, each
+    what compress_band_n gives for that band of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host
+    convenience over the device entries (ONE flat upload, sizes-only compress, status, emit into a buffer of exactly the total,
+    download).  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the set."""
+    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
+    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
+        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    nb = pics[0].shape[2]
+    flag = _colour_flag(colour, nb, "batch_compress_picture_set_n")
+    table = picture_set_table([p.shape[:2] for p in pics], nb, bs, n)      # names the refusal, before any device is touched
+    mode_of(mode)
+    nws = batch_set_workspace_bytes_n(table, group_samples)
+    if nws == 0:
+        batch_compress_picture_set_n_device(1, table, 8, 16, None, 0, mode, param, flag, group_samples)
+        raise JpegxError("batch_compress_picture_set_n: the set was refused")
+    require_device()
+    flat = np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pics])
+    with _Buffers() as dev:
+        din, dtab, dws = dev(flat.nbytes), dev(table.nbytes), dev(nws)
+        din.upload(flat)
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_compress_picture_set_n_device(din.ptr, table, dtab.ptr, dws.ptr, None, 0, mode, param, flag, group_samples)
+        rc, total, off = batch_compress_status_set_n(dws.ptr, table, group_samples)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status_set_n")
+        dout = dev(max(1, total))
+        batch_emit_set_n_device(dws.ptr, table, dtab.ptr, dout.ptr, total, group_samples)
+        rc, total2, off = batch_compress_status_set_n(dws.ptr, table, group_samples)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit_set_n")
+        blob = dout.download((total,), np.uint8)
+        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(len(pics))]
+
+
+def batch_decompress_picture_set_n(blobs, sizes, bs, n, mode="none", param=0.0, colour=None, group_samples=0):
+    """k lists of nb byte strings (as batch_compress_picture_set_n returns them) and the k (rows, cols) -> a list of uint8 arrays
+    [rows_p][cols_p][nb], picture p the np.dstack of what decompress_band_n gives for its bands (with colour='rgb': Pillow's RGB
+    of that).  JpegxError naming a picture range for a stream the device refuses."""
+    blobs = [[bytes(b) for b in picture] for picture in blobs]
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    k = len(blobs)
+    nb = len(blobs[0]) if k else 0
+    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs) or len(sizes) != k:
+        raise JpegxError("expected at least one picture, the same number of bands in each, and a size for each")
+    flag = _colour_flag(colour, nb, "batch_decompress_picture_set_n")
+    table = picture_set_table(sizes, nb, bs, n)
+    mode_of(mode)
+    flat = [b for picture in blobs for b in picture]
+    off = np.zeros(k * nb + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in flat])
+    total = int(off[-1])
+    nws = batch_decompress_set_workspace_bytes_n(max(total, 1), table, group_samples)
+    if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
+        batch_decompress_picture_set_n_device(1, off, table, 8, 16, 1, mode, param, flag, group_samples)
+        raise JpegxError("batch_decompress_picture_set_n: empty stream")
+    require_device()
+    nout = sum(r * c * nb for r, c in sizes)
+    with _Buffers() as dev:
+        din, dtab, dws, dout = dev(total), dev(table.nbytes), dev(nws), dev(nout)
+        din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_decompress_picture_set_n_device(din.ptr, off, table, dtab.ptr, dws.ptr, dout.ptr, mode, param, flag, group_samples)
+        out = dout.download((nout,), np.uint8)
+    at = np.concatenate([[0], np.cumsum([r * c * nb for r, c in sizes])])
+    return [out[int(at[p]):int(at[p + 1])].reshape(r, c, nb) for p, (r, c) in enumerate(sizes)]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1289,3 +1289,170 @@ def decompress_pictures(containers, colour=None):
     """decompress_pictures_u8 as PIL images of mode YCbCr (RGB with colour='rgb')."""
     from PIL import Image
     return [Image.fromarray(a, mode="YCbCr" if colour is None else "RGB") for a in decompress_pictures_u8(containers, colour)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# many pictures of unequal sizes at once: each under the same settings at its own size
+# ---------------------------------------------------------------------------------------------------------------------
+# compress_picture_set / decompress_picture_set_u8 send the pictures that the picture jobs admit to the device as ONE set
+# (jpegx.batch_compress_picture_set_n / batch_decompress_picture_set_n, dct_size other than 8: one flat upload, one launch chain
+# and one download whatever the sizes) from this many admitted pictures on; None: the road is off and the functions are a loop
+# over Jpeg.compress / compress_rgb / decompress / decompress_rgb with a Configuration of each picture's own size.  Never below
+# 2: one picture is what those are for.  All three constants are read when the functions are called.
+# Measured (DESIGN.md 4.21, profiles/batch_picture_set_n.json and, a second run of the same code, _run2.json; figures of the first,
+# the second agrees on every verdict here; pictures with sides between 64 and 128 at N 4 and N 16, with colour 'rgb' and
+# without, the set road against the loop, alternating call by call on one MI355X, 12 rounds): even ONE picture through the set
+# won all eight comparisons of either run (0.29-0.30 against 0.52-0.78 ms compressing, 0.23-0.31 against 0.28-0.35 ms
+# decompressing: the loop's picture jobs start at 16 384 samples a plane, most of these planes are smaller); with 2 pictures it wins
+# 2.7-3.8x / 1.6-2.0x, with 4 5.6-7.3x / 1.9-3.7x, with 16 9.2-11.8x / 5.4-5.9x, with 64 17-21x / 11-13x.  The smallest count with no
+# loss at or above it is the smallest the constant may take.
+DCTN_PICTURE_SET_MIN_PICTURES = 2
+
+# ... and only when the LARGEST plane of the set (H * W of one band of one picture after both paddings) holds at most this
+# many samples; None: no upper limit.  The set pays its launches and copies once, and copies all pixels into one flat array
+# that moves through pageable memory in one piece, while the picture jobs of the loop stream through the pool's pinned staging.
+# Measured (the same two records): compressing, the set is 18-23x faster than the loop on 4096 pictures with sides 48..96 (planes
+# of at most 9216 samples) and 7.4-10x on 256 with sides 384..640 at bs 5 N 24 (at most 20 736 samples) in both runs; on the same
+# 256 pictures at bs 1 (up to 399 360 samples) it is 1.2-1.4x faster at N 4 and lost at N 16 in both runs (100-106 against 96-97 ms,
+# 87.3 against 86.8 ms); on 16 pictures near 3000 x 4000 it is 2.4-4.2x slower at 489 600 and at 12 M samples.  Decompressing, it
+# won every comparison of either run: 12-17x on the 4096 pictures, 2.0-41x on the 256, 1.8-9.6x on the 16 (planes of up to
+# 12 032 000 samples).  Each constant is the largest measured plane with no loss at or below it in either run.
+DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES = 20736
+DCTN_PICTURE_SET_DECOMPRESS_MAX_SAMPLES = 12032000
+
+
+def _picture_set_gate(count, samples, most):
+    """What the three constants above mean, for ``count`` admitted pictures whose largest plane holds ``samples`` samples."""
+    gate = DCTN_PICTURE_SET_MIN_PICTURES
+    return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
+
+
+def _sized(config, rows, cols):
+    """``config`` with the picture's own width and height, as cli.py makes one per picture."""
+    return Configuration(width=cols, height=rows, block_size=config.block_size, dct_size=config.dct_size, transform=config.transform,
+                         quantization=config.quantization)
+
+
+def _compress_picture_set(images, config, colour):
+    """{index: container} of the pictures that went to the device as one set; empty where the gates, the configuration or
+    libjpegx say no -- the loop then names the picture and the fault."""
+    most = DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES
+    if not _picture_set_gate(len(images), 0, most) or not _stock_registry() or not _device_usable():
+        return {}
+    admitted, job = [], None                            # (index, rows, cols)
+    for at, im in enumerate(images):
+        try:
+            rows, cols = im.height, im.width
+        except Exception:
+            continue
+        if not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:
+            continue
+        sized = _sized(config, rows, cols)
+        if _picture_size(im, sized) is None or (colour is not None and im.mode != "RGB"):
+            continue
+        this = _compress_job_n(sized, rows, cols, 0)
+        if this is None:
+            continue
+        job = this                                      # (block_size, dct_size, mode, param): the same for every picture
+        admitted.append((at, rows, cols))
+    if not admitted:
+        return {}
+    shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
+    if not _picture_set_gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
+        return {}
+    pixels = [_picture_pixels(images[at]) for at, _, _ in admitted]      # the costly part of the vetting: last
+    keep = [k for k, p in enumerate(pixels) if p is not None]
+    if len(keep) != len(pixels):
+        admitted, pixels = [admitted[k] for k in keep], [pixels[k] for k in keep]
+        if not _picture_set_gate(len(admitted), 0, None):
+            return {}
+    import jpegx
+    blobs = _none_on_refusal(jpegx.batch_compress_picture_set_n, pixels, *job, **_colour_kw(colour))
+    if blobs is None:
+        return {}
+    out = {}
+    for (at, rows, cols), picture in zip(admitted, blobs):
+        header = file_format.create_header(_sized(config, rows, cols))   # file_format.generate_data: the header, then <L length + bytes per band
+        out[at] = header + b"".join(file_format.pack_long(len(b)) + b for b in picture)
+    return out
+
+
+def compress_picture_set(images, config, colour=None):
+    """[Jpeg(config_p).compress(im) for im in images], byte for byte, where config_p is ``config`` with the picture's own width
+    and height (``config``'s own are not read); with colour='rgb', compress_rgb.  The pictures that the picture jobs admit
+    (_picture_size, _picture_pixels, _compress_job_n with the picture's size -- so planes of at least DCTN_MIN_SAMPLES samples,
+    dct_size other than 8; with colour='rgb' of mode RGB) go to the device as ONE set when there are at least
+    DCTN_PICTURE_SET_MIN_PICTURES of them and the largest plane holds at most DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES samples; every
+    other picture, and every picture after a refusal of the set -- a BadRleCodeError included -- goes through the loop, which
+    names it.  Results come back in input order."""
+    _check_colour(colour)
+    images = list(images)
+    done = _compress_picture_set(images, config, colour) if images else {}
+    out = []
+    for at, im in enumerate(images):
+        if at in done:
+            out.append(done[at])
+        else:
+            codec = Jpeg(_sized(config, im.height, im.width))
+            out.append(codec.compress(im) if colour is None else codec.compress_rgb(im))
+    return out
+
+
+def _decompress_picture_set(containers, colour):
+    """{index: uint8 pixels} of the containers that went to the device as one set (see _compress_picture_set): containers whose
+    headers differ in width and height alone, with coded bands, under a configuration _decompress_job_n admits."""
+    most = DCTN_PICTURE_SET_DECOMPRESS_MAX_SAMPLES
+    if not _picture_set_gate(len(containers), 0, most) or not _stock_registry() or not _device_usable():
+        return {}
+    admitted, blobs, rest, job = [], [], None, None
+    for at, box in enumerate(containers):
+        if not isinstance(box, (bytes, bytearray)) or len(box) < 6:
+            continue
+        header = bytes(box[:file_format.unpack_integer(box[:2])])
+        if len(header) < 6 or (rest is not None and header[:2] + header[6:] != rest):
+            continue
+        bands = _container_bands(box, header)
+        if bands is None:
+            continue
+        try:
+            sized = file_format.get_header(header)
+        except Exception:
+            continue                                    # the loop names the fault
+        if _accelerated(sized):
+            continue
+        this = _decompress_job_n(sized, bands, 0)
+        if this is None:
+            continue
+        if rest is None:
+            rest, job = header[:2] + header[6:], this[2:]
+        admitted.append((at, this[0], this[1]))
+        blobs.append(bands)
+    if not admitted:
+        return {}
+    shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
+    if not _picture_set_gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
+        return {}
+    import jpegx
+    back = _none_on_refusal(jpegx.batch_decompress_picture_set_n, blobs, [(rows, cols) for _, rows, cols in admitted], *job, **_colour_kw(colour))
+    if back is None:
+        return {}
+    return {at: a for (at, _, _), a in zip(admitted, back)}
+
+
+def decompress_picture_set_u8(containers, colour=None):
+    """[np.asarray(Jpeg.decompress(c)) for c in containers] as uint8 arrays (height_p, width_p, 3), sample for sample; with
+    colour='rgb', of Jpeg.decompress_rgb(c).  The containers may differ in width and height and in nothing else of the header:
+    those that share the rest of the first admitted one's header, hold coded bands and pass _decompress_job_n go to the device
+    as ONE set under the gates of compress_picture_set (DCTN_PICTURE_SET_DECOMPRESS_MAX_SAMPLES); every other container, and all
+    of them after a refusal of the set, go through the loop, which names the container and the fault."""
+    _check_colour(colour)
+    containers = list(containers)
+    done = _decompress_picture_set(containers, colour) if containers else {}
+    return [done[at] if at in done else np.asarray(Jpeg.decompress(c) if colour is None else Jpeg.decompress_rgb(c))
+            for at, c in enumerate(containers)]
+
+
+def decompress_picture_set(containers, colour=None):
+    """decompress_picture_set_u8 as PIL images of mode YCbCr (RGB with colour='rgb')."""
+    from PIL import Image
+    return [Image.fromarray(a, mode="YCbCr" if colour is None else "RGB") for a in decompress_picture_set_u8(containers, colour)]

@@ -619,7 +619,112 @@ int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned lon
                                       int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                       jpegx_stream_t stream);
 
-/* ---- batch codec for whole pictures at dct_size 8 (csrc/jpegx_picture_u8.hip, csrc/jpegx_batch.cpp) -------------------
+/* ---- batch codec for a SET of pictures of UNEQUAL sizes at any DCT size but 8 (csrc/jpegx_batch_set_n.cpp,
+ * csrc/jpegx_band_set_n.hip) ----------------------------------------------------------------------------------------------
+ * Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124; with colour = 1 behind compress.py:9 and in
+ * front of decompress.py:9-10) for every picture of a set, each under the same settings AT ITS OWN SIZE, as cli.py:46 makes a
+ * Configuration per picture: the bytes of every band are those of jpegx_batch_compress_pictures_n on that picture alone.
+ * Planes of unequal widths cannot be stacked into one tall plane, their blocks can: the BLOCK STRIP [nblocks * N][N] with
+ * pitch N holds block g in rows g * N .. g * N + N - 1.  jpegx_forward_fused_n and jpegx_inverse_fused_n take it as a plane of
+ * width N, and a block's arithmetic does not depend on where the block lies, so the int32 stream is bit for bit what the
+ * per-picture road writes; the entropy stage works on a flat list of blocks both ways.  Block order is picture-major, then
+ * band, then block-row-major inside the band (the order of the container and of the picture batch above).
+ *
+ * THE TABLE (host arithmetic, no device).  The caller describes picture p by a jpegx_picture_desc: rows, cols, the byte offset
+ * of its first pixel in ONE device buffer and its row pitch in bytes (>= cols * nbands, no alignment asked).
+ * jpegx_picture_set_table writes into h_table (room for jpegx_picture_set_table_bytes(npictures) bytes, 8-byte aligned):
+ *     jpegx_picture_set_head                     32 bytes
+ *     jpegx_picture_set_entry [npictures + 1]    64 bytes each; the last is the END: first = total blocks, lanes = all lanes
+ *     long long plane_first [nbands * npictures + 1]   first block of plane (p, k) = first_p + k * nb_p; the last = total blocks
+ * and the total block count into *total_blocks (may be NULL).  The caller uploads the blob as it is (jpegx_memcpy_h2d, the
+ * device copy 8-byte aligned) and hands the entries below BOTH copies: the host copy for shapes and groups, the device copy
+ * for the kernels -- so every compute entry stays "enqueue only, allocates nothing".  jpegx_picture_set_table_bytes is the room
+ * for JPEGX_MAX_IMAGE_BANDS bands, 0 for npictures < 1.
+ * Refused before anything else: null pointers, npictures < 1, nbands outside 1..JPEGX_MAX_IMAGE_BANDS, N outside 2..32, a
+ * picture with rows or cols < 1 or rows * cols > 2^31 - 1, a pitch below cols * nbands, a sum over the pictures of nbands * H_p *
+ * W_p above 2^31 - 1 (JPEGX_E_INVALID); bs outside 1..255 (JPEGX_E_UNSUPPORTED).  Overlapping pictures are the caller's
+ * business: the gather only reads, the scatter writes each picture's own bytes.                                         */
+#define JPEGX_PICTURE_SET_MAGIC 0x4A505354u
+typedef struct jpegx_picture_desc {
+    int rows, cols;
+    unsigned long long offset; /* bytes from the buffer's start to pixel (0, 0) */
+    long long pitch;           /* bytes from a row to the next */
+} jpegx_picture_desc;
+typedef struct jpegx_picture_set_head {
+    unsigned magic; /* JPEGX_PICTURE_SET_MAGIC */
+    int npictures, nbands, bs, N, pad;
+    long long total_blocks;
+} jpegx_picture_set_head;
+typedef struct jpegx_picture_set_entry {
+    unsigned long long offset;
+    long long pitch;
+    long long first; /* index of the picture's first block: the sum of nbands * nb over the pictures before it */
+    long long lanes; /* first lane of the scatter: the sum of rows * ceil(cols / PIX) before it, PIX = 16, 8, 16, 4 for 1..4 bands */
+    int rows, cols;
+    int H, W;         /* jpegx_band_shape_n(rows, cols, bs, N) */
+    int prows, pcols; /* ceil(rows / bs), ceil(cols / bs): the pooled band */
+    int wb, nb;       /* blocks per block row W / N, blocks per band (H / N) * (W / N) */
+} jpegx_picture_set_entry;
+size_t jpegx_picture_set_table_bytes(int npictures);
+int jpegx_picture_set_table(const jpegx_picture_desc *pictures, int npictures, int nbands, int bs, int N, void *h_table,
+                            long long *total_blocks);
+/* The gather (enqueue only): pixels of pictures p0 .. p0 + k - 1 of the table -> their blocks as a float64 block strip
+ * [nblk * N][N] at d_strip (16-byte aligned), block 0 of the strip the first block of picture p0.  Sample (i, j) of block
+ * (p, band, by, bx) is bit for bit what jpegx_band_plane_n writes at (by * N + i, bx * N + j) of that band of picture p
+ * (pipeline/padding.py:8-12, subsampling.py:9-11, dct_padding.py:8-9, normalization.py:7-8): the clamped gather against the
+ * picture's OWN last row, column and pooled sizes, the exact integer tile sum, one division.  colour as in
+ * jpegx_band_planes_packed_stacked_n.  No read leaves [rows_p] x [cols_p * nbands] bytes of a picture's rows; no write leaves
+ * the k pictures' blocks.  One launch takes at most 2^31 - 1 samples (the table's limit).
+ * The scatter (enqueue only): a uint8 block strip of pictures p0 .. p0 + k - 1 (the clamped output of jpegx_inverse_fused_n on
+ * the strip) -> their pixels at d_out + offset_p, rows pitch_p apart: out_p[y][x * nbands + band] = the strip's sample of plane
+ * (p, band) at (y / bs, x / bs) for y < rows_p, x < cols_p (pipeline/dct_padding.py:11-21, subsampling.py:13-14, padding.py:14-16,
+ * the np.dstack of pipeline/__init__.py:121).  Exactly cols_p * nbands bytes of each of the rows_p rows are written: nothing in
+ * the pitch slack or between pictures.  With colour = 1 each source triple is converted once and replicated.
+ * Both: JPEGX_E_INVALID for null pointers, a blob that is no table, a range outside the table, a bad colour.            */
+int jpegx_picture_set_blocks_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour,
+                               double *d_strip, jpegx_stream_t stream);
+int jpegx_picture_set_pixels_u8(const uint8_t *d_strip, const void *h_table, const void *d_table, int p0, int k, int colour,
+                                uint8_t *d_out, jpegx_stream_t stream);
+/* The codec entries mirror the picture entries above with "nplanes planes of one shape" replaced by the table.
+ * group_samples: a group is whole pictures whose blocks stay within that many samples (0 = 2^26), one picture at least; a
+ * forward or inverse launch covers one group, gblocks * N <= 2^31 - 1 rows, which the table's limit implies.  Every workspace
+ * must be 16-byte aligned.  nplanes = nbands * npictures throughout.
+ * jpegx_batch_set_workspace_bytes_n / jpegx_batch_set_max_bytes_n: the compress workspace and the worst-case stream (0 for a
+ * blob that is no table or a negative group_samples).
+ * jpegx_batch_compress_picture_set_n (enqueue only): per group the gather and jpegx_forward_fused_n(strip, gblocks * N, N, N, ...)
+ * into the group's blocks of the int32 stream; then one jpegx_entropy_sizes_n over all blocks, the plane index (nplanes + 1
+ * offsets; planes start at block indices that need not be multiples of 64) and the guarded emitter.  d_out == NULL (out_cap
+ * must be 0): sizes only.  Nothing is written to d_out when the stream does not fit or an amplitude is beyond 15 bits.
+ * jpegx_batch_compress_status_set_n (synchronises): total, plane offsets (may be NULL; nplanes + 1) and the verdicts of
+ * jpegx_batch_compress_status_n -- JPEGX_OK, 1 (did not fit; nothing written), JPEGX_E_INVALID naming BadRleCodeError.
+ * jpegx_batch_emit_set_n (enqueue only): the plane index and the guarded emitter again, for a destination of the size that
+ * a sizes-only compress reported.
+ * jpegx_batch_groups_set_n (host arithmetic): the cut of the way back on picture boundaries -- from the first picture not yet
+ * taken a group takes whole pictures while its samples stay within group_samples and its bytes within 64 MiB, one picture at
+ * least; h_group_first (may be NULL; room for npictures + 1) counts pictures, h_group_first[*ngroups] = npictures.
+ * JPEGX_E_INVALID for offsets that decrease and a lone picture of 2^32 - 4096 bytes or more.
+ * jpegx_batch_decompress_picture_set_n (NOT enqueue only): per group the staging copy with 16 zero bytes behind it,
+ * jpegx_entropy_decode_n, ONE synchronisation for the verdict, jpegx_inverse_fused_n with JPEGX_F_CLAMP_U8 onto a uint8 strip,
+ * the scatter.  A refused group writes nothing and is named by its first and last picture; earlier groups have been
+ * written.  Refused before any device work: what jpegx_batch_groups_set_n refuses, and a group whose bytes cannot be its
+ * blocks.  Its workspace: jpegx_batch_decompress_set_workspace_bytes_n(nbytes of the whole stream, ...).                 */
+size_t jpegx_batch_set_workspace_bytes_n(const void *h_table, long long group_samples);
+size_t jpegx_batch_set_max_bytes_n(const void *h_table);
+int jpegx_batch_compress_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
+                                       double param, long long group_samples, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                                       jpegx_stream_t stream);
+int jpegx_batch_compress_status_set_n(const void *d_workspace, const void *h_table, long long group_samples,
+                                      unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+int jpegx_batch_emit_set_n(void *d_workspace, const void *h_table, const void *d_table, long long group_samples, uint8_t *d_out,
+                           size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_groups_set_n(const unsigned long long *h_plane_offsets, const void *h_table, long long group_samples,
+                             int *h_group_first, int *ngroups);
+size_t jpegx_batch_decompress_set_workspace_bytes_n(size_t nbytes, const void *h_table, long long group_samples);
+int jpegx_batch_decompress_picture_set_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table,
+                                         const void *d_table, int mode, double param, int colour, long long group_samples,
+                                         void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+
+/* ---- batch codec for whole pictures at dct_size 8(csrc/jpegx_picture_u8.hip, csrc/jpegx_batch.cpp) -------------------
  * jpegx_picture_planes_stacked_u8 (enqueue only): pictures stacked [npictures * rows][pitch], every row cols * nbands
  * interleaved bytes (no alignment asked; never written) -> the padded RAW uint8 planes of the 8x8 batch, stacked picture-major
  * [npictures * nbands * H * bs][out_pitch], (H, W) = jpegx_padded_shape(rows, cols, bs), plane p * nbands + k band k of
@@ -1076,6 +1181,21 @@ int jpegx_batch_decompress_pictures_on(int device, const uint8_t *d_bytes, const
                                        int npictures, int nbands, int rows, int cols, int bs, int mode, double param,
                                        int colour, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                        jpegx_stream_t stream);
+int jpegx_picture_set_blocks_n_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k,
+                                  int colour, double *d_strip, jpegx_stream_t stream);
+int jpegx_picture_set_pixels_u8_on(int device, const uint8_t *d_strip, const void *h_table, const void *d_table, int p0, int k,
+                                   int colour, uint8_t *d_out, jpegx_stream_t stream);
+int jpegx_batch_compress_picture_set_n_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table,
+                                          int colour, int mode, double param, long long group_samples, void *d_workspace,
+                                          uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_compress_status_set_n_on(int device, const void *d_workspace, const void *h_table, long long group_samples,
+                                         unsigned long long *h_total, unsigned long long *h_plane_offsets,
+                                         jpegx_stream_t stream);
+int jpegx_batch_emit_set_n_on(int device, void *d_workspace, const void *h_table, const void *d_table, long long group_samples,
+                              uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_decompress_picture_set_n_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
+                                            const void *h_table, const void *d_table, int mode, double param, int colour,
+                                            long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
