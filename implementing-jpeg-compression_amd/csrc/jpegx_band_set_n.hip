@@ -17,67 +17,14 @@
 // consecutive doubles.  The scatter's lane owns PIX consecutive pixels of one output row of a picture, as
 // k_inflate_crop_pack_stacked_u8's does.
 //
-// The picture of an item is found by a binary search over a prefix of the table (block positions for the gather, lanes for the
-// scatter): log2(k + 1) steps.  Up to SET_LDS_PICTURES pictures the prefix is copied to LDS once per workgroup and searched
-// there; beyond that the search reads the table in global memory, where its upper levels stay in the caches.
+// The picture of an item is found by the binary search of jpegx_picture_set_device.h (block positions for the gather, lanes
+// for the scatter), which the raw uint8 gather of dct_size 8 (jpegx_picture_set_u8.hip) shares.
 // Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
-#include "jpegx_colour_device.h"
+#include "jpegx_picture_set_device.h"
 
 namespace {
-
-using Head = jpegx_picture_set_head;
-using Entry = jpegx_picture_set_entry;
-
-constexpr unsigned COLOUR_MAX_BLOCKS = 1024;       // k_colour_u8's: four 256-thread workgroups per CU
-constexpr int SET_LDS_PICTURES = 1023;             // the prefix of that many pictures + the end: 8 KiB of LDS
-
-template <bool INVERSE>
-__device__ __forceinline__ void fill_colour_tables(int16_t *t)
-{
-    if (threadIdx.x < (INVERSE ? INV_TABLES : FWD_TABLES) * 32)
-        reinterpret_cast<uint4 *>(t)[threadIdx.x] = reinterpret_cast<const uint4 *>(INVERSE ? g_colour_inv : g_colour_fwd)[threadIdx.x];
-}
-
-// the prefix of pictures p0 .. p0 + k (the end included), relative to picture p0: block POSITIONS (blocks of one band) for the
-// gather, lanes for the scatter
-template <bool LANES>
-__device__ __forceinline__ unsigned long long prefix_of(const Entry *e, int q, int nbands)
-{
-    return LANES ? (unsigned long long)(e[q].lanes - e[0].lanes) : (unsigned long long)(e[q].first - e[0].first) / (unsigned)nbands;
-}
-
-template <bool LANES>
-__device__ __forceinline__ void fill_prefix(unsigned long long *pre, const Entry *e, int k, int nbands)
-{
-    if (k > SET_LDS_PICTURES) return;
-    for (int q = threadIdx.x; q <= k; q += 256) pre[q] = prefix_of<LANES>(e, q, nbands);
-}
-
-// the largest q in 0 .. k - 1 whose prefix is at most v (v is below the prefix of k; the prefix rises strictly)
-template <bool LANES>
-__device__ __forceinline__ int find_picture(const unsigned long long *pre, const Entry *e, int k, int nbands, unsigned long long v,
-                                            unsigned long long *start)
-{
-    int lo = 0, hi = k;
-    unsigned long long at = 0;
-    if (k <= SET_LDS_PICTURES) {
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            const unsigned long long m = pre[mid];
-            if (m <= v) { lo = mid; at = m; } else hi = mid;
-        }
-    } else {
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            const unsigned long long m = prefix_of<LANES>(e, mid, nbands);
-            if (m <= v) { lo = mid; at = m; } else hi = mid;
-        }
-    }
-    *start = at;
-    return lo;
-}
 
 // one pixel into the NB sums, converted first where COLOUR says so (jpegx_band_n.hip's add_pixel)
 template <int NB, bool COLOUR>
@@ -222,14 +169,6 @@ __global__ __launch_bounds__(256) void k_picture_set_pixels_u8(const uint8_t *__
     }
 }
 
-// grid of an instantiation: all the items without COLOUR, at most COLOUR_MAX_BLOCKS workgroups with it
-template <bool COLOUR>
-unsigned set_blocks(unsigned long long items)
-{
-    const unsigned long long blocks = (items + 255u) / 256u;               // below 2^31: the entries check it
-    return COLOUR && blocks > COLOUR_MAX_BLOCKS ? COLOUR_MAX_BLOCKS : (unsigned)blocks;
-}
-
 template <int NB, bool COLOUR>
 void launch_blocks(const uint8_t *px, const Entry *e, int k, int bs, int N, unsigned long long positions, double *out, hipStream_t st)
 {
@@ -250,35 +189,6 @@ template <int NB, bool COLOUR>
 void launch_pixels(const uint8_t *strip, const Entry *e, int k, int bs, int N, unsigned long long items, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL((k_picture_set_pixels_u8<NB, COLOUR>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, strip, e, k, (unsigned)bs, N, items, out);
-}
-
-// what both entries check of their arguments: JPEGX_OK and the head, or the refusal
-int check_range(const char *who, const void *a, const void *h_table, const void *d_table, int p0, int k, int colour, const void *b, const Head **head)
-{
-    char buf[200];
-    if (!a || !h_table || !d_table || !b) {
-        snprintf(buf, sizeof(buf), "%s: null pointer", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
-    const Head *h = static_cast<const Head *>(h_table);
-    if (h->magic != JPEGX_PICTURE_SET_MAGIC) {
-        snprintf(buf, sizeof(buf), "%s: h_table is not a table of jpegx_picture_set_table", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
-    if (p0 < 0 || k < 1 || p0 > h->npictures - k) {
-        snprintf(buf, sizeof(buf), "%s: pictures %d .. %d are not pictures of the table's %d", who, p0, p0 + k - 1, h->npictures);
-        return fail(JPEGX_E_INVALID, buf);
-    }
-    if ((colour != 0 && colour != 1) || (colour == 1 && h->nbands != 3)) {
-        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
-    if (reinterpret_cast<uintptr_t>(d_table) % 8) {
-        snprintf(buf, sizeof(buf), "%s: d_table must be 8-byte aligned", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
-    *head = h;
-    return JPEGX_OK;
 }
 
 }  // namespace

@@ -181,3 +181,13 @@ JPEGX_ON(jpegx_batch_emit_set_n, (int device, void *d_workspace, const void *h_t
          (d_workspace, h_table, d_table, group_samples, d_out, out_cap, stream))
 JPEGX_ON(jpegx_batch_decompress_picture_set_n, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table, const void *d_table, int mode, double param, int colour, long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream),
          (d_bytes, h_plane_offsets, h_table, d_table, mode, param, colour, group_samples, d_workspace, d_out, stream))
+JPEGX_ON(jpegx_picture_set_blocks_u8, (int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour, uint8_t *d_strip, jpegx_stream_t stream),
+         (d_pixels, h_table, d_table, p0, k, colour, d_strip, stream))
+JPEGX_ON(jpegx_batch_compress_picture_set, (int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode, double param, long long group_samples, void *d_workspace, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_pixels, h_table, d_table, colour, mode, param, group_samples, d_workspace, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_compress_status_set, (int device, const void *d_workspace, const void *h_table, long long group_samples, unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream),
+         (d_workspace, h_table, group_samples, h_total, h_plane_offsets, stream))
+JPEGX_ON(jpegx_batch_emit_set, (int device, void *d_workspace, const void *h_table, const void *d_table, long long group_samples, uint8_t *d_out, size_t out_cap, jpegx_stream_t stream),
+         (d_workspace, h_table, d_table, group_samples, d_out, out_cap, stream))
+JPEGX_ON(jpegx_batch_decompress_picture_set, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table, const void *d_table, int mode, double param, int colour, long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream),
+         (d_bytes, h_plane_offsets, h_table, d_table, mode, param, colour, group_samples, d_workspace, d_out, stream))

@@ -30,6 +30,9 @@ int jpegx_internal_entropy_plane_index(int nplanes, long long blocks_per_plane, 
                                        jpegx_stream_t stream);
 int jpegx_internal_entropy_plane_index_ragged(int nplanes, const long long *d_first, long long nblocks, const void *d_workspace, void *d_index,
                                               size_t out_cap, jpegx_stream_t stream);   // planes of unequal block counts (jpegx_batch_set_n.cpp)
+// jpegx_picture_set_u8.hip: takes the bytes of the pad block (block nblocks, nblocks odd) out of its wave's total after a
+// forward kernel has sized nblocks + 1 blocks (jpegx_batch_set.cpp)
+int jpegx_internal_picture_set_pad_fixup(void *d_workspace, long long nblocks, jpegx_stream_t stream);
 // jpegx_hostpipe.cpp: a job context of the current device borrowed for one call (host_roundtrip, jpegx_internal.h)
 int jpegx_internal_pool_acquire(size_t in_bytes, size_t out_bytes, void **d_in, void **d_out, void **stream);
 void jpegx_internal_pool_release(void);

@@ -221,6 +221,15 @@ SIGNATURES = {
     "jpegx_batch_groups_set_n": [_vp, _vp, _c.c_longlong, _vp, _c.POINTER(_int)],
     "jpegx_batch_decompress_set_workspace_bytes_n": [_sz, _vp, _c.c_longlong],
     "jpegx_batch_decompress_picture_set_n": [_vp, _vp, _vp, _vp, _int, _dbl, _int, _c.c_longlong, _vp, _vp, _vp],
+    "jpegx_picture_set_blocks_u8": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
+    "jpegx_batch_set_workspace_bytes": [_vp, _c.c_longlong],
+    "jpegx_batch_set_max_bytes": [_vp],
+    "jpegx_batch_compress_picture_set": [_vp, _vp, _vp, _int, _int, _dbl, _c.c_longlong, _vp, _vp, _sz, _vp],
+    "jpegx_batch_compress_status_set": [_vp, _vp, _c.c_longlong, _c.POINTER(_c.c_ulonglong), _vp, _vp],
+    "jpegx_batch_emit_set": [_vp, _vp, _vp, _c.c_longlong, _vp, _sz, _vp],
+    "jpegx_batch_groups_set": [_vp, _vp, _c.c_longlong, _vp, _c.POINTER(_int)],
+    "jpegx_batch_decompress_set_workspace_bytes": [_sz, _vp, _c.c_longlong],
+    "jpegx_batch_decompress_picture_set": [_vp, _vp, _vp, _vp, _int, _dbl, _int, _c.c_longlong, _vp, _vp, _vp],
     "jpegx_comm_available": [],
     "jpegx_comm_unique_id": [_vp],
     "jpegx_comm_create": [_c.POINTER(_vp), _int, _int, _vp],
@@ -252,7 +261,9 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_batch_compress_pictures_n", "jpegx_batch_decompress_pictures_n", "jpegx_picture_planes_stacked_u8",
               "jpegx_batch_compress_pictures", "jpegx_batch_decompress_pictures", "jpegx_picture_set_blocks_n",
               "jpegx_picture_set_pixels_u8", "jpegx_batch_compress_picture_set_n", "jpegx_batch_compress_status_set_n",
-              "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n"):
+              "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n", "jpegx_picture_set_blocks_u8",
+              "jpegx_batch_compress_picture_set", "jpegx_batch_compress_status_set", "jpegx_batch_emit_set",
+              "jpegx_batch_decompress_picture_set"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -261,7 +272,8 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_decompress_pictures_workspace_bytes_n": _sz, "jpegx_batch_pictures_workspace_bytes": _sz,
             "jpegx_batch_decompress_pictures_workspace_bytes": _sz, "jpegx_picture_set_table_bytes": _sz,
             "jpegx_batch_set_workspace_bytes_n": _sz, "jpegx_batch_set_max_bytes_n": _sz,
-            "jpegx_batch_decompress_set_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_decompress_set_workspace_bytes_n": _sz, "jpegx_batch_set_workspace_bytes": _sz,
+            "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz}   # everything else returns int
 
 
 def lib():
@@ -2258,3 +2270,180 @@ def batch_decompress_pictures(blobs, rows, cols, block_size=1, mode="qtable", pa
         din.upload(stream_bytes)
         batch_decompress_pictures_device(din.ptr, off, *pics, dws.ptr, dout.ptr, None, mode, param, flag)
         return dout.download((k, rows, cols, nb), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the batch codec for a SET of pictures of unequal sizes at dct_size 8: the set entries above with the table of N = 8
+# (picture_set_table(sizes, nbands, bs, 8)), the int16 stream and the 8x8 stage, so qtable is taken.
+# ---------------------------------------------------------------------------------------------
+def batch_set_workspace_bytes(table, group_samples=0):
+    return lib().jpegx_batch_set_workspace_bytes(table.ptr, int(group_samples))
+
+
+def batch_set_max_bytes(table):
+    return lib().jpegx_batch_set_max_bytes(table.ptr)
+
+
+def batch_decompress_set_workspace_bytes(nbytes, table, group_samples=0):
+    return lib().jpegx_batch_decompress_set_workspace_bytes(int(nbytes), table.ptr, int(group_samples))
+
+
+def batch_groups_set(plane_offsets, table, group_samples=0):
+    """The cut of a coded set into decoding groups on picture boundaries (jpegx_batch_groups_set; host arithmetic): the first
+    PICTURE of every group and, last, npictures."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (table.npictures * table.nbands + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    first = np.zeros(table.npictures + 1, dtype=np.int32)
+    ngroups = ctypes.c_int(0)
+    check(lib().jpegx_batch_groups_set(off.ctypes.data, table.ptr, int(group_samples), first.ctypes.data, ctypes.byref(ngroups)),
+          "jpegx_batch_groups_set")
+    return first[:ngroups.value + 1].copy()
+
+
+def picture_set_strip_bytes_u8(table, p0=0, k=None):
+    """Bytes of the raw uint8 block strip of pictures p0 .. p0 + k - 1 (jpegx_picture_set_blocks_u8): 64 * bs * bs a block, at
+    block_size 1 with the pad block behind an odd count."""
+    k = table.npictures - p0 if k is None else k
+    blocks = int(table.entries["first"][p0 + k] - table.entries["first"][p0])
+    bs = int(table.head["bs"])
+    return (blocks + (blocks & 1 if bs == 1 else 0)) * 64 * bs * bs
+
+
+def picture_set_blocks_u8_device(d_pixels, table, d_table, p0, k, d_strip, colour=0, stream=None, device=None):
+    """Enqueue jpegx_picture_set_blocks_u8: pixels of pictures p0 .. p0 + k - 1 -> their raw uint8 block strip at d_strip."""
+    args = (d_pixels, table.ptr, d_table, int(p0), int(k), int(colour), d_strip, stream)
+    L = lib()
+    check(L.jpegx_picture_set_blocks_u8(*args) if device is None else L.jpegx_picture_set_blocks_u8_on(int(device), *args),
+          "jpegx_picture_set_blocks_u8")
+
+
+def picture_set_blocks_u8(pictures, block_size=1, colour=None):
+    """jpegx_picture_set_blocks_u8 on host arrays (test convenience, like picture_planes_stacked_u8): a sequence of uint8
+    pictures [rows_p][cols_p][nb] -> the raw uint8 strip as the forward kernel sees it, [T * 8 bs][8 bs] at block_size 2 and 4,
+    [ceil(T / 2) * 8][16] at block_size 1 (an odd T: with the pad block of zeros)."""
+    pics = [np.ascontiguousarray(p) for p in pictures]
+    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
+        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    nb, bs = pics[0].shape[2], int(block_size)
+    flag = _colour_flag(colour, nb, "picture_set_blocks_u8")
+    table = picture_set_table([p.shape[:2] for p in pics], nb, bs, 8)
+    if bs not in (1, 2, 4):
+        picture_set_blocks_u8_device(1, table, 8, 0, len(pics), 16, flag)
+    nbytes = picture_set_strip_bytes_u8(table)
+    require_device()
+    flat = np.concatenate([p.reshape(-1) for p in pics])
+    with _Buffers() as dev:
+        din, dtab, dout = dev(flat.nbytes), dev(table.nbytes), dev(nbytes)
+        din.upload(flat)
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        picture_set_blocks_u8_device(din.ptr, table, dtab.ptr, 0, len(pics), dout.ptr, flag)
+        return dout.download((nbytes // (16 if bs == 1 else 8 * bs), 16 if bs == 1 else 8 * bs), np.uint8)
+
+
+def batch_compress_picture_set_device(d_pixels, table, d_table, d_workspace, d_out, out_cap, mode="qtable", param=0.0, colour=0,
+                                      group_samples=0, stream=None, device=None):
+    """Enqueue jpegx_batch_compress_picture_set -> coded bytes at d_out (None: sizes only).  Verdict and plane index:
+    batch_compress_status_set."""
+    args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), float(param), int(group_samples), d_workspace, d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_compress_picture_set(*args) if device is None else L.jpegx_batch_compress_picture_set_on(int(device), *args),
+          "jpegx_batch_compress_picture_set")
+
+
+def batch_compress_status_set(d_workspace, table, group_samples=0, stream=None, device=None):
+    """Synchronises; returns (rc, total, offsets) as batch_compress_status does."""
+    total = ctypes.c_ulonglong(0)
+    off = np.zeros(table.npictures * table.nbands + 1, dtype=np.uint64)
+    args = (d_workspace, table.ptr, int(group_samples), ctypes.byref(total), off.ctypes.data, stream)
+    L = lib()
+    rc = L.jpegx_batch_compress_status_set(*args) if device is None else L.jpegx_batch_compress_status_set_on(int(device), *args)
+    if rc not in (0, 1, -1):
+        check(rc, "jpegx_batch_compress_status_set")
+    return rc, total.value, off
+
+
+def batch_emit_set_device(d_workspace, table, d_table, d_out, out_cap, group_samples=0, stream=None, device=None):
+    args = (d_workspace, table.ptr, d_table, int(group_samples), d_out, int(out_cap), stream)
+    L = lib()
+    check(L.jpegx_batch_emit_set(*args) if device is None else L.jpegx_batch_emit_set_on(int(device), *args), "jpegx_batch_emit_set")
+
+
+def batch_decompress_picture_set_device(d_bytes, plane_offsets, table, d_table, d_workspace, d_out, mode="qtable", param=0.0, colour=0,
+                                        group_samples=0, stream=None, device=None):
+    """jpegx_batch_decompress_picture_set (synchronises the stream per group and level); plane_offsets: nbands * npictures + 1
+    host integers; every picture at its offset and pitch in d_out.  Raises JpegxError for whatever the entry refuses."""
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (table.npictures * table.nbands + 1,):
+        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    args = (d_bytes, off.ctypes.data, table.ptr, d_table, mode_of(mode), float(param), int(colour), int(group_samples), d_workspace, d_out, stream)
+    L = lib()
+    check(L.jpegx_batch_decompress_picture_set(*args) if device is None else L.jpegx_batch_decompress_picture_set_on(int(device), *args),
+          "jpegx_batch_decompress_picture_set")
+
+
+def batch_compress_picture_set(pictures, block_size=1, mode="qtable", param=0.0, colour=None, group_samples=0):
+    """A sequence of uint8 pictures [rows_p][cols_p][nb], sizes as they come -> per picture the list of its nb bands' bytes, each
+    what compress_plane_native(band, ragged=True) gives for that band of that picture (with colour='rgb': of the picture's
+    Pillow YCbCr).  Host convenience over the device entries, as batch_compress_picture_set_n."""
+    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
+    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
+        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    nb = pics[0].shape[2]
+    flag = _colour_flag(colour, nb, "batch_compress_picture_set")
+    table = picture_set_table([p.shape[:2] for p in pics], nb, block_size, 8)      # names the refusal, before any device is touched
+    mode_of(mode)
+    nws = batch_set_workspace_bytes(table, group_samples)
+    if nws == 0:
+        batch_compress_picture_set_device(1, table, 8, 16, None, 0, mode, param, flag, group_samples)
+        raise JpegxError("batch_compress_picture_set: the set was refused")
+    require_device()
+    flat = np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pics])
+    with _Buffers() as dev:
+        din, dtab, dws = dev(flat.nbytes), dev(table.nbytes), dev(nws)
+        din.upload(flat)
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_compress_picture_set_device(din.ptr, table, dtab.ptr, dws.ptr, None, 0, mode, param, flag, group_samples)
+        rc, total, off = batch_compress_status_set(dws.ptr, table, group_samples)
+        if rc != 0:
+            check(rc, "jpegx_batch_compress_status_set")
+        dout = dev(max(1, total))
+        batch_emit_set_device(dws.ptr, table, dtab.ptr, dout.ptr, total, group_samples)
+        rc, total2, off = batch_compress_status_set(dws.ptr, table, group_samples)
+        if rc != 0 or total2 != total:
+            check(rc if rc else -1, "jpegx_batch_emit_set")
+        blob = dout.download((total,), np.uint8)
+        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(len(pics))]
+
+
+def batch_decompress_picture_set(blobs, sizes, block_size=1, mode="qtable", param=0.0, colour=None, group_samples=0):
+    """k lists of nb byte strings (as batch_compress_picture_set returns them) and the k (rows, cols) -> a list of uint8 arrays
+    [rows_p][cols_p][nb], picture p the np.dstack of its decoded bands cropped to its size (with colour='rgb': Pillow's RGB of
+    that).  JpegxError naming a picture range for a stream the device refuses."""
+    blobs = [[bytes(b) for b in picture] for picture in blobs]
+    sizes = [(int(r), int(c)) for r, c in sizes]
+    k = len(blobs)
+    nb = len(blobs[0]) if k else 0
+    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs) or len(sizes) != k:
+        raise JpegxError("expected at least one picture, the same number of bands in each, and a size for each")
+    flag = _colour_flag(colour, nb, "batch_decompress_picture_set")
+    table = picture_set_table(sizes, nb, block_size, 8)
+    mode_of(mode)
+    flat = [b for picture in blobs for b in picture]
+    off = np.zeros(k * nb + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in flat])
+    total = int(off[-1])
+    nws = batch_decompress_set_workspace_bytes(max(total, 1), table, group_samples)
+    if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
+        batch_decompress_picture_set_device(1, off, table, 8, 256, 1, mode, param, flag, group_samples)
+        raise JpegxError("batch_decompress_picture_set: empty stream")
+    require_device()
+    nout = sum(r * c * nb for r, c in sizes)
+    with _Buffers() as dev:
+        din, dtab, dws, dout = dev(total), dev(table.nbytes), dev(max(256, nws)), dev(nout)
+        din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_decompress_picture_set_device(din.ptr, off, table, dtab.ptr, dws.ptr, dout.ptr, mode, param, flag, group_samples)
+        out = dout.download((nout,), np.uint8)
+    at = np.concatenate([[0], np.cumsum([r * c * nb for r, c in sizes])])
+    return [out[int(at[p]):int(at[p + 1])].reshape(r, c, nb) for p, (r, c) in enumerate(sizes)]

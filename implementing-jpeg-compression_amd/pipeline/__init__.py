@@ -1327,6 +1327,36 @@ def _picture_set_gate(count, samples, most):
     return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
 
 
+# dct_size 8 has a picture set of its own (jpegx.batch_compress_picture_set / batch_decompress_picture_set: every block_size
+# 1..255, the qtable quantiser included; block_size 1, 2, 4 through the raw uint8 block strip and the sized uint8 forward kernel)
+# behind its OWN three gates, with the meaning of the DCTN_PICTURE_SET_* constants above and read when the functions are
+# called.  The first ships as None -- the road is off and dct_size 8 is the loop, as it was (tests/test_picture_set_dispatch.py
+# pins that with only the DCTN_* gates set; the precedent is DCT8_PICTURE_BATCH_MIN_PICTURES) -- and callers with many small
+# pictures opt in by setting it: 4 is the measured value.
+# Measured (profiles/batch_picture_set_8.json and, a second run of the same code, _run2.json; the set road
+# against the loop alternating call by call on one MI355X, colour 'rgb', qtable, block_size 4 and 1, 3 rounds, both size gates
+# lifted): with 2 pictures of sides 64..128 the set lost compressing once in four comparisons (0.382 against 0.379 ms at
+# block_size 1 in the second run; 0.34-0.35 against 0.35-0.37 ms in the others) and won decompressing 7.3-8.1x; with 4 it wins
+# 1.77-2.06x / 8.0-8.6x, with 16 3.9-4.1x / 16-23x, with 64 4.4-5.3x / 22-29x; 4096 pictures of sides 48..96 go 5.7-6.3x /
+# 19-28x faster (101-127 against 634-751 ms, 101-148 against 2800-2870 ms).  Compressing 256 pictures of sides 384..640 the
+# set LOSES in both runs at block_size 4 (102-108 against 77-79 ms; planes of up to 25 600 samples) and at block_size 1 (115-120
+# against 101-103 ms; up to 404 480 samples): one flat pageable copy against the pooled picture jobs.  Compressing 16 pictures
+# near 3000 x 4000 it wins at block_size 4 (286-287 against 304-365 ms; 752 000 samples) and loses 6.5-6.9x at block_size 1
+# (734-753 against 109-112 ms; 11 976 000 samples).  Decompressing, it won every comparison of either run from 2 pictures on:
+# 8.8-45x on the 256 pictures, 18-23x (block_size 4) and 2.6-3.0x (block_size 1) on the 16 large ones.  Each _MAX_SAMPLES
+# constant is the largest measured plane with no loss at or below it in either run, from 4 pictures on.  They take effect once
+# DCT8_PICTURE_SET_MIN_PICTURES is set.
+DCT8_PICTURE_SET_MIN_PICTURES = None
+DCT8_PICTURE_SET_COMPRESS_MAX_SAMPLES = 15360
+DCT8_PICTURE_SET_DECOMPRESS_MAX_SAMPLES = 11976000
+
+
+def _picture_set_gate_8(count, samples, most):
+    """_picture_set_gate for dct_size 8: ``most`` is the direction's DCT8_PICTURE_SET_*_MAX_SAMPLES as the caller reads it."""
+    gate = DCT8_PICTURE_SET_MIN_PICTURES
+    return gate is not None and count >= max(gate, 2) and (most is None or samples <= most)
+
+
 def _sized(config, rows, cols):
     """``config`` with the picture's own width and height, as cli.py makes one per picture."""
     return Configuration(width=cols, height=rows, block_size=config.block_size, dct_size=config.dct_size, transform=config.transform,
@@ -1335,10 +1365,17 @@ def _sized(config, rows, cols):
 
 def _compress_picture_set(images, config, colour):
     """{index: container} of the pictures that went to the device as one set; empty where the gates, the configuration or
-    libjpegx say no -- the loop then names the picture and the fault."""
-    most = DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES
-    if not _picture_set_gate(len(images), 0, most) or not _stock_registry() or not _device_usable():
+    libjpegx say no -- the loop then names the picture and the fault.  dct_size 8 (the accelerated configuration) goes by
+    _job_config_8, jpegx.padded_shape and the DCT8_* gates to jpegx.batch_compress_picture_set, every other size by
+    _compress_job_n, _blocked_shape and the DCTN_* gates to jpegx.batch_compress_picture_set_n."""
+    eight = _accelerated(config)
+    gate = _picture_set_gate_8 if eight else _picture_set_gate
+    most = DCT8_PICTURE_SET_COMPRESS_MAX_SAMPLES if eight else DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES
+    if not gate(len(images), 0, most) or not _stock_registry() or not _device_usable():
         return {}
+    if eight and not isinstance(config.block_size, (int, np.integer)):
+        return {}                                       # the table takes whole block sizes; 2.0 is the loop's
+    import jpegx
     admitted, job = [], None                            # (index, rows, cols)
     for at, im in enumerate(images):
         try:
@@ -1350,24 +1387,28 @@ def _compress_picture_set(images, config, colour):
         sized = _sized(config, rows, cols)
         if _picture_size(im, sized) is None or (colour is not None and im.mode != "RGB"):
             continue
-        this = _compress_job_n(sized, rows, cols, 0)
+        this = _job_config_8(sized) if eight else _compress_job_n(sized, rows, cols, 0)
         if this is None:
             continue
-        job = this                                      # (block_size, dct_size, mode, param): the same for every picture
+        job = this                                      # (block_size, [dct_size,] mode, param): the same for every picture
         admitted.append((at, rows, cols))
     if not admitted:
         return {}
-    shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
-    if not _picture_set_gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
+    if eight:
+        shapes = [_none_on_refusal(jpegx.padded_shape, rows, cols, job[0]) for _, rows, cols in admitted]
+        if any(s is None for s in shapes):
+            return {}
+    else:
+        shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
+    if not gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
         return {}
     pixels = [_picture_pixels(images[at]) for at, _, _ in admitted]      # the costly part of the vetting: last
     keep = [k for k, p in enumerate(pixels) if p is not None]
     if len(keep) != len(pixels):
         admitted, pixels = [admitted[k] for k in keep], [pixels[k] for k in keep]
-        if not _picture_set_gate(len(admitted), 0, None):
+        if not gate(len(admitted), 0, None):
             return {}
-    import jpegx
-    blobs = _none_on_refusal(jpegx.batch_compress_picture_set_n, pixels, *job, **_colour_kw(colour))
+    blobs = _none_on_refusal(jpegx.batch_compress_picture_set if eight else jpegx.batch_compress_picture_set_n, pixels, *job, **_colour_kw(colour))
     if blobs is None:
         return {}
     out = {}
@@ -1384,7 +1425,9 @@ def compress_picture_set(images, config, colour=None):
     dct_size other than 8; with colour='rgb' of mode RGB) go to the device as ONE set when there are at least
     DCTN_PICTURE_SET_MIN_PICTURES of them and the largest plane holds at most DCTN_PICTURE_SET_COMPRESS_MAX_SAMPLES samples; every
     other picture, and every picture after a refusal of the set -- a BadRleCodeError included -- goes through the loop, which
-    names it.  Results come back in input order."""
+    names it.  Results come back in input order.  dct_size 8 has the same road (_job_config_8: every block_size 1..255;
+    jpegx.batch_compress_picture_set) behind gates of its own, DCT8_PICTURE_SET_MIN_PICTURES and
+    DCT8_PICTURE_SET_COMPRESS_MAX_SAMPLES; the first ships as None, so dct_size 8 is the loop until a caller sets it."""
     _check_colour(colour)
     images = list(images)
     done = _compress_picture_set(images, config, colour) if images else {}
@@ -1400,11 +1443,12 @@ def compress_picture_set(images, config, colour=None):
 
 def _decompress_picture_set(containers, colour):
     """{index: uint8 pixels} of the containers that went to the device as one set (see _compress_picture_set): containers whose
-    headers differ in width and height alone, with coded bands, under a configuration _decompress_job_n admits."""
-    most = DCTN_PICTURE_SET_DECOMPRESS_MAX_SAMPLES
-    if not _picture_set_gate(len(containers), 0, most) or not _stock_registry() or not _device_usable():
-        return {}
-    admitted, blobs, rest, job = [], [], None, None
+    headers differ in width and height alone, with coded bands, under a configuration _decompress_job_n -- for dct_size 8
+    _decode_job_8 -- admits, each kind behind its own gates."""
+    count = len(containers)
+    if not (_picture_set_gate(count, 0, None) or _picture_set_gate_8(count, 0, None)) or not _stock_registry() or not _device_usable():
+        return {}                                       # neither road's count gate admits them: nothing is parsed
+    admitted, blobs, rest, job, eight = [], [], None, None, False
     for at, box in enumerate(containers):
         if not isinstance(box, (bytes, bytearray)) or len(box) < 6:
             continue
@@ -1418,22 +1462,38 @@ def _decompress_picture_set(containers, colour):
             sized = file_format.get_header(header)
         except Exception:
             continue                                    # the loop names the fault
-        if _accelerated(sized):
-            continue
-        this = _decompress_job_n(sized, bands, 0)
-        if this is None:
-            continue
+        if _accelerated(sized):                         # the rest of the header is shared: one kind per set
+            if not _picture_set_gate_8(count, 0, None) or not isinstance(sized.block_size, (int, np.integer)):
+                continue
+            this = _decode_job_8(sized)
+            if this is None or not all(_is_coded(b) for b in bands):
+                continue
+            this = (sized.height, sized.width) + tuple(this[2:])
+        else:
+            if not _picture_set_gate(count, 0, None):
+                continue
+            this = _decompress_job_n(sized, bands, 0)
+            if this is None:
+                continue
         if rest is None:
-            rest, job = header[:2] + header[6:], this[2:]
+            rest, job, eight = header[:2] + header[6:], this[2:], _accelerated(sized)
         admitted.append((at, this[0], this[1]))
         blobs.append(bands)
     if not admitted:
         return {}
-    shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
-    if not _picture_set_gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
-        return {}
     import jpegx
-    back = _none_on_refusal(jpegx.batch_decompress_picture_set_n, blobs, [(rows, cols) for _, rows, cols in admitted], *job, **_colour_kw(colour))
+    gate = _picture_set_gate_8 if eight else _picture_set_gate
+    most = DCT8_PICTURE_SET_DECOMPRESS_MAX_SAMPLES if eight else DCTN_PICTURE_SET_DECOMPRESS_MAX_SAMPLES
+    if eight:
+        shapes = [_none_on_refusal(jpegx.padded_shape, rows, cols, job[0]) for _, rows, cols in admitted]
+        if any(s is None for s in shapes):
+            return {}
+    else:
+        shapes = [_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted]
+    if not gate(len(admitted), max(h * w for h, w in shapes), most) or 3 * sum(h * w for h, w in shapes) > 2 ** 31 - 1:
+        return {}
+    entry = jpegx.batch_decompress_picture_set if eight else jpegx.batch_decompress_picture_set_n
+    back = _none_on_refusal(entry, blobs, [(rows, cols) for _, rows, cols in admitted], *job, **_colour_kw(colour))
     if back is None:
         return {}
     return {at: a for (at, _, _), a in zip(admitted, back)}

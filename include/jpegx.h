@@ -769,6 +769,54 @@ int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long 
                                     int nbands, int rows, int cols, int bs, int mode, double param, int colour,
                                     void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch, jpegx_stream_t stream);
 
+/* ---- batch codec for a SET of pictures of UNEQUAL sizes at dct_size 8 (csrc/jpegx_picture_set_u8.hip,
+ * csrc/jpegx_batch_set.cpp) -------------------------------------------------------------------------------------------------
+ * The set entries above at dct_size 8: the table is jpegx_picture_set_table's with N = 8 as it is (its H, W are
+ * jpegx_padded_shape's), the stream is the int16 one and the stage the 8 x 8 one, so qtable is taken and the bytes of every
+ * band are those of jpegx_batch_compress_pictures on that picture alone.  Block order is the table's.
+ * jpegx_picture_set_blocks_u8 (enqueue only): pixels of pictures p0 .. p0 + k - 1 -> their blocks as the RAW uint8 block strip
+ * that the uint8 forward kernels (jpegx_forward_fused_u8) read unchanged, block 0 the first block of picture p0, T blocks.
+ * Block g holds its R x R unpooled samples, R = 8 * bs, sample (r, j) of block (p, band, by, bx) = model_p[src(by * R + r)][
+ * src(bx * R + j)][band] with src of jpegx_pad_edges per axis against the picture's OWN rows and cols and model_p as in
+ * jpegx_picture_planes_stacked_u8 (colour = 1: Pillow's YCbCr):
+ *   bs 2, 4: [T * R][R] with pitch R (16, 32 bytes), one block a block row -- a plane of W = 8;
+ *   bs 1:    [ceil(T / 2) * 8][16], block g at block row g / 2, column g % 2 -- a plane of W = 16; an odd T is followed by
+ *            ONE PAD BLOCK OF ZEROS, written by this entry, so the strip holds T + 1 blocks.
+ * d_strip 16-byte aligned with room for that.  JPEGX_E_INVALID for what jpegx_picture_set_blocks_n refuses and a table whose N
+ * is not 8; JPEGX_E_UNSUPPORTED for a table whose bs is not 1, 2 or 4.  No read leaves [rows_p] x [cols_p * nbands] bytes of a
+ * picture's rows; no write leaves the strip.
+ * The codec entries are jpegx_batch_*_set_n's, argument for argument, with these differences.  Compress (enqueue only): bs 1,
+ * 2, 4 run jpegx_picture_set_blocks_u8 over the WHOLE set and the sized uint8 forward kernel on the strip (with the pad block:
+ * on T + 1 blocks, whose bytes a one-lane kernel then takes out of the sizes -- the pad leaves no byte in the output, nothing
+ * in a plane offset and nothing in the total); every other bs goes per group of group_samples through
+ * jpegx_picture_set_blocks_n at N = 8 and jpegx_forward_fused_f64, then one sizing pass.  Both: scan, the plane index of planes
+ * of unequal block counts, the guarded emitter.  Refused before any launch with jpegx_batch_compress_pictures's codes: an
+ * unknown quantiser, a keep that is no non-negative integer, a divisor that is zero or not finite (JPEGX_E_INVALID) or below 0.5
+ * (JPEGX_E_UNSUPPORTED, on both roads); a table whose N is not 8 (JPEGX_E_INVALID).  The worst case is 188 bytes a block + 64.
+ * Decompress (NOT enqueue only; workspace 256-byte aligned): per group of jpegx_batch_groups_set (whole pictures within
+ * group_samples samples and 64 MiB, one at least; a lone picture above 2^32 - 17 bytes is JPEGX_E_INVALID) jpegx_batch_decompress
+ * on the group's bytes as ONE plane [gblocks * 8][8] with JPEGX_OUT_U8 onto a uint8 strip of pitch 8 and, only after it has
+ * answered JPEGX_OK, jpegx_picture_set_pixels_u8.  A refused group writes nothing and is named by its first and last picture;
+ * earlier groups have been written.  Refused before any device work: what jpegx_batch_groups_set refuses, an empty stream,
+ * and a group whose bytes cannot be its blocks (1 .. 185 bytes each).                                                     */
+int jpegx_picture_set_blocks_u8(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour,
+                                uint8_t *d_strip, jpegx_stream_t stream);
+size_t jpegx_batch_set_workspace_bytes(const void *h_table, long long group_samples);
+size_t jpegx_batch_set_max_bytes(const void *h_table);
+int jpegx_batch_compress_picture_set(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
+                                     double param, long long group_samples, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                                     jpegx_stream_t stream);
+int jpegx_batch_compress_status_set(const void *d_workspace, const void *h_table, long long group_samples,
+                                    unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+int jpegx_batch_emit_set(void *d_workspace, const void *h_table, const void *d_table, long long group_samples, uint8_t *d_out,
+                         size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_groups_set(const unsigned long long *h_plane_offsets, const void *h_table, long long group_samples,
+                           int *h_group_first, int *ngroups);
+size_t jpegx_batch_decompress_set_workspace_bytes(size_t nbytes, const void *h_table, long long group_samples);
+int jpegx_batch_decompress_picture_set(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table,
+                                       const void *d_table, int mode, double param, int colour, long long group_samples,
+                                       void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+
 /* Inverse of the entropy stage, ON THE HOST (sequential parse, as in the reference):
  * RleBytestream.invert (pipeline/rle_byte_stream.py:61-88) + RunLengthEncoding.invert
  * (pipeline/run_length_encoding.py:66-97) for dct_size 8: bytes -> int16 [nblocks][64].        */
@@ -1196,6 +1244,18 @@ int jpegx_batch_emit_set_n_on(int device, void *d_workspace, const void *h_table
 int jpegx_batch_decompress_picture_set_n_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
                                             const void *h_table, const void *d_table, int mode, double param, int colour,
                                             long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+int jpegx_picture_set_blocks_u8_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k,
+                                   int colour, uint8_t *d_strip, jpegx_stream_t stream);
+int jpegx_batch_compress_picture_set_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table,
+                                        int colour, int mode, double param, long long group_samples, void *d_workspace,
+                                        uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_compress_status_set_on(int device, const void *d_workspace, const void *h_table, long long group_samples,
+                                       unsigned long long *h_total, unsigned long long *h_plane_offsets, jpegx_stream_t stream);
+int jpegx_batch_emit_set_on(int device, void *d_workspace, const void *h_table, const void *d_table, long long group_samples,
+                            uint8_t *d_out, size_t out_cap, jpegx_stream_t stream);
+int jpegx_batch_decompress_picture_set_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
+                                          const void *h_table, const void *d_table, int mode, double param, int colour,
+                                          long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
