@@ -21,55 +21,11 @@
 #include <mutex>
 
 #include "jpegx_internal.h"
+#include "jpegx_dctn_device.h"
 
 namespace {
 
-constexpr int DCTN_THREADS = 256;
-constexpr int DCTN_MIN = 2, DCTN_MAX = 32;
 constexpr int DCTN_MAX_DEVICES = 64;
-
-__host__ __device__ inline int dctn_blocks_per_wg(int N)
-{
-    const int nn = N * N;
-    return nn >= DCTN_THREADS ? 1 : DCTN_THREADS / nn;
-}
-
-__device__ inline double dctn_quant(double y, int k, int l, int mode, double param, double inv_param, int use_mul)
-{
-    if (mode == JPEGX_QM_DIVIDE) return rint(use_mul ? y * inv_param : y / param);
-    if (mode == JPEGX_QM_DISCARD) {
-        const int keep = (int)param;
-        return (k >= keep || l >= keep) ? 0.0 : rint(y);
-    }
-    return rint(y);
-}
-
-__device__ inline int dctn_to_i32(double r)
-{
-    return r >= 2147483647.0 ? 2147483647 : (r <= -2147483648.0 ? (int)(-2147483647 - 1) : (int)r);
-}
-
-// plane element of the workgroup's blocks for load / store index e: consecutive e walk one plane row across the blocks
-struct PlaneSpot {
-    int lds;        // index into the staged blocks [b][i][j]
-    int i;          // row inside the block
-    size_t glob;    // element offset into the plane
-    bool live;      // block exists (the last workgroup may hold fewer than bpw)
-};
-
-__device__ inline PlaneSpot plane_spot(int e, int N, int bpw, long long first, int wb, int nblk, size_t pitch)
-{
-    const int rowlen = bpw * N;
-    const int i = e / rowlen, r = e - i * rowlen, b = r / N, j = r - b * N;
-    const long long g = first + b;
-    PlaneSpot s;
-    s.lds = b * N * N + i * N + j;
-    s.i = i;
-    s.live = g < nblk;
-    const long long by = g / wb, bx = g - by * wb;
-    s.glob = (size_t)(by * N + i) * pitch + (size_t)bx * N + j;
-    return s;
-}
 
 // COEF_OUT false: quantised int32 zigzag stream [nblk][N*N]; true: the unquantised float64 coefficients in place of
 // their block in the plane `fout` (BasisChange.execute alone).
@@ -355,6 +311,17 @@ int jpegx_dct_tables_n(int N, double *C, double *Cn, double *Dinv, uint16_t *zig
     if (N < DCTN_MIN || N > DCTN_MAX) return fail(JPEGX_E_INVALID, "dct_size must be 2 .. 32");
     if (!C || !Cn || !Dinv || !zigzag) return fail(JPEGX_E_INVALID, "null host pointer");
     build_tables(N, C, Cn, Dinv, zigzag);
+    return JPEGX_OK;
+}
+
+// the cached forward tables of the current device for the size probe (jpegx_probe_n.hip): N checked by the caller
+int jpegx_internal_dctn_forward_tables(int N, const double **d_ct, const uint16_t **d_zig)
+{
+    DeviceTables t;
+    const int rc = device_tables(N, &t);
+    if (rc) return rc;
+    *d_ct = t.ct;
+    *d_zig = t.zig;
     return JPEGX_OK;
 }
 

@@ -191,3 +191,7 @@ JPEGX_ON(jpegx_batch_emit_set, (int device, void *d_workspace, const void *h_tab
          (d_workspace, h_table, d_table, group_samples, d_out, out_cap, stream))
 JPEGX_ON(jpegx_batch_decompress_picture_set, (int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table, const void *d_table, int mode, double param, int colour, long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream),
          (d_bytes, h_plane_offsets, h_table, d_table, mode, param, colour, group_samples, d_workspace, d_out, stream))
+JPEGX_ON(jpegx_probe_sizes_n, (int device, const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int N, int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_planes, nplanes, H, W, pitch, N, mode, h_params, K, d_totals, stream))
+JPEGX_ON(jpegx_batch_probe_pictures_n, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N, int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, N, mode, h_params, K, group_planes, d_workspace, d_totals, stream))

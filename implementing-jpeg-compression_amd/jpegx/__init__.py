@@ -204,6 +204,9 @@ SIGNATURES = {
     "jpegx_batch_groups_pictures_n": [_vp, _int, _int, _int, _int, _int, _int, _int, _vp, _c.POINTER(_int)],
     "jpegx_batch_decompress_pictures_workspace_bytes_n": [_sz, _int, _int, _int, _int, _int, _int, _int],
     "jpegx_batch_decompress_pictures_n": [_vp, _vp, _int, _int, _int, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _pd, _vp],
+    "jpegx_probe_sizes_n": [_vp, _int, _int, _int, _pd, _int, _int, _vp, _int, _vp, _vp],
+    "jpegx_batch_probe_pictures_workspace_bytes_n": [_int, _int, _int, _int, _int, _int, _int],
+    "jpegx_batch_probe_pictures_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
     "jpegx_picture_planes_stacked_u8": [_vp, _int, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
     "jpegx_batch_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
     "jpegx_batch_compress_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
@@ -263,7 +266,7 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_picture_set_pixels_u8", "jpegx_batch_compress_picture_set_n", "jpegx_batch_compress_status_set_n",
               "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n", "jpegx_picture_set_blocks_u8",
               "jpegx_batch_compress_picture_set", "jpegx_batch_compress_status_set", "jpegx_batch_emit_set",
-              "jpegx_batch_decompress_picture_set"):
+              "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -273,7 +276,8 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_decompress_pictures_workspace_bytes": _sz, "jpegx_picture_set_table_bytes": _sz,
             "jpegx_batch_set_workspace_bytes_n": _sz, "jpegx_batch_set_max_bytes_n": _sz,
             "jpegx_batch_decompress_set_workspace_bytes_n": _sz, "jpegx_batch_set_workspace_bytes": _sz,
-            "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz}   # everything else returns int
+            "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz,
+            "jpegx_batch_probe_pictures_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -1928,6 +1932,77 @@ def batch_decompress_pictures_n(blobs, rows, cols, bs, n, mode="none", param=0.0
         din.upload(np.frombuffer(b"".join(flat), dtype=np.uint8))
         batch_decompress_pictures_n_device(din.ptr, off, *pics, dws.ptr, dout.ptr, group_planes, None, mode, param, flag)
         return dout.download((k, rows, cols, nb), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the size probe: what every plane would weigh under each of K candidate quantiser parameters, in one pass over the planes
+# (csrc/jpegx_probe_n.hip) -- no coefficient stream, no per-candidate compression.  dct_size 2..32 through the run-time-N kernels.
+# ---------------------------------------------------------------------------------------------
+PROBE_MAX_CANDIDATES = 32
+PROBE_BAD = 1 << 63                                     # bit 63 of a total: an amplitude beyond 15 bits (BadRleCodeError)
+
+
+def _probe_params(params):
+    """The candidates as a host float64 array (kept alive by the caller for the length of the call) and their count."""
+    h = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)).ravel())
+    return h, int(h.size)
+
+
+def probe_sizes_n_device(d_planes, nplanes, height, width, n, mode, params, d_totals, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_probe_sizes_n: nplanes float64 planes stacked [nplanes * height][pitch] (elements, default width) ->
+    uint64 d_totals [nplanes][K]: bits 0..62 the coded bytes of the plane under candidate q, bit 63 the bad-amplitude flag.
+    ``params``: the K candidates (host numbers)."""
+    h, k = _probe_params(params)
+    args = (d_planes, int(nplanes), int(height), int(width), int(width if pitch is None else pitch), int(n), mode_of(mode),
+            h.ctypes.data, k, d_totals, stream)
+    L = lib()
+    check(L.jpegx_probe_sizes_n(*args) if device is None else L.jpegx_probe_sizes_n_on(int(device), *args), "jpegx_probe_sizes_n")
+
+
+def batch_probe_pictures_workspace_bytes_n(npictures, nbands, rows, cols, bs, n, group_planes):
+    return lib().jpegx_batch_probe_pictures_workspace_bytes_n(int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n),
+                                                              int(group_planes))
+
+
+def batch_probe_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, mode, params, group_planes, d_workspace, d_totals,
+                                  colour=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_probe_pictures_n: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands) ->
+    uint64 d_totals [nbands * npictures][K], plane-major in the batch's picture-major plane order."""
+    h, k = _probe_params(params)
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), int(n), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
+    L = lib()
+    check(L.jpegx_batch_probe_pictures_n(*args) if device is None else L.jpegx_batch_probe_pictures_n_on(int(device), *args),
+          "jpegx_batch_probe_pictures_n")
+
+
+def batch_probe_pictures_n(pixels, bs, n, mode, params, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> (sizes, bad): sizes uint64 [k][nb][K], the length of band b of picture p as
+    batch_compress_pictures_n would code it under candidate q; bad bool [k][nb][K], True where that band holds an amplitude
+    beyond 15 bits under that candidate (its size is then meaningless).  Host convenience: upload, probe, one download.
+    group_planes None: the recommended value."""
+    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    k, rows, cols, nb = src.shape
+    flag = _colour_flag(colour, nb, "batch_probe_pictures_n")
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, n) or nb
+    h, nk = _probe_params(params)
+    pics = (k, nb, rows, cols, int(bs), int(n))
+    nws = batch_probe_pictures_workspace_bytes_n(*pics, group_planes)
+    if nws == 0 or not 1 <= nk <= PROBE_MAX_CANDIDATES:     # the entry names the refusal, before any device is touched
+        batch_probe_pictures_n_device(1, *pics, mode, h, group_planes, 16, 8, flag)
+        raise JpegxError("batch_probe_pictures_n: the batch was refused")
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dtot = dev(src.nbytes), dev(nws), dev(k * nb * nk * 8)
+        din.upload(src)
+        batch_probe_pictures_n_device(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
+        raw = dtot.download((k, nb, nk), np.uint64)
+    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1516,3 +1516,220 @@ def decompress_picture_set(containers, colour=None):
     """decompress_picture_set_u8 as PIL images of mode YCbCr (RGB with colour='rgb')."""
     from PIL import Image
     return [Image.fromarray(a, mode="YCbCr" if colour is None else "RGB") for a in decompress_picture_set_u8(containers, colour)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what a divisor costs in bytes, and compressing to a byte budget
+# ---------------------------------------------------------------------------------------------------------------------
+# probe_picture_sizes takes the device road (jpegx.batch_probe_pictures_n: one upload, one gather and one forward pass per
+# group of pictures, every candidate divisor quantised and sized from the coefficients in LDS, one download of the sums) from
+# this many divisors on; None: the road is off and the function is the loop over Jpeg.compress.  Read when the function is
+# called.  Never below 1.
+# Measured (DESIGN.md 4.23, profiles/probe_sizes_n.json and, a second run of the same code, _run2.json; 1 and 8 pictures of
+# 64 x 64 and 512 x 512 at N 4 and N 16, the probe against the loop alternating call by call on one MI355X): with ONE divisor
+# the probe loses on one 512 x 512 picture in both runs (0.50-0.54 against 0.36 ms: the loop's pooled picture job against three
+# allocations and a pageable copy) and wins the other comparisons; with 2 divisors it wins all of them in both runs (1.26-34x),
+# with 4 by 2.4-50x, with 16 by 7.9-151x.  On device buffers the probe is 1.6-1.9x faster than 2 sizes-only compressions at
+# every measured shape (4096 pictures of 64 x 64, 256 of 512 x 512, 16 of 3000 x 4000; N 4, 16, 24) and 0.85-1.16x with one
+# candidate.  The smallest measured count with no loss at or above it; no plane size lost at every count, so there is no size
+# gate beyond DCTN_MIN_SAMPLES.
+DCTN_PROBE_MIN_CANDIDATES = 2
+
+
+class TargetSizeError(ValueError):
+    """No candidate divisor brings the picture within the byte budget."""
+
+
+def _checked_divisors(config, divisors):
+    """The candidate divisors as plain Python numbers; ValueError for a configuration that is not 'divide' and for a divisor
+    that is not a whole positive number (_whole_divisor: the device jobs restore such a one as the reference does)."""
+    if getattr(config.quantization, "name", None) != "divide":
+        raise ValueError("the size probe varies the divisor: config.quantization must be 'divide', got %r"
+                         % (getattr(config.quantization, "name", None),))
+    out = []
+    for d in divisors:
+        whole = isinstance(d, (int, float, np.integer, np.floating)) and not isinstance(d, (bool, np.bool_)) \
+            and np.isfinite(d) and d > 0 and _whole_divisor(("divide", float(d)))
+        if not whole:
+            raise ValueError("a candidate divisor must be a whole positive number, got %r" % (d,))
+        out.append(d.item() if isinstance(d, np.generic) else d)
+    return out
+
+
+def _divide_config(config, divisor):
+    """``config`` with QuantizationMethod('divide', divisor=divisor)."""
+    return Configuration(width=config.width, height=config.height, block_size=config.block_size, dct_size=config.dct_size,
+                         transform=config.transform, quantization=QuantizationMethod("divide", divisor=divisor))
+
+
+def _compress_one(image, config, colour):
+    codec = Jpeg(config)
+    return codec.compress(image) if colour is None else codec.compress_rgb(image)
+
+
+def _probe_loop(images, config, divisors, colour):
+    """The literal loop: len(Jpeg(config_j).compress(image_i)), -1 where it raises the reference's BadRleCodeError."""
+    import util
+    images = _as_images(images, colour)
+    out = np.empty((len(images), len(divisors)), dtype=np.int64)
+    for j, d in enumerate(divisors):
+        cfg = _divide_config(config, d)
+        for i, im in enumerate(images):
+            try:
+                out[i, j] = len(_compress_one(im, cfg, colour))
+            except util.BadRleCodeError:
+                out[i, j] = -1
+    return out
+
+
+def _probe_device(images, config, divisors, colour):
+    """The sizes from jpegx.batch_probe_pictures_n, or None: the gate, the configuration or the pictures do not admit the road,
+    or libjpegx refused or failed."""
+    gate = DCTN_PROBE_MIN_CANDIDATES
+    count = len(images)
+    if gate is None or len(divisors) < max(gate, 1) or count < 1 or not _stock_registry():
+        return None
+    sizes = _job_sizes(config)                           # transform 'DCT', dct_size 2..32 but 8, a usable device
+    rows, cols = config.height, config.width
+    if sizes is None or not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
+            or rows * cols > 2 ** 31 - 1:
+        return None
+    bs, n = sizes
+    h, w = _blocked_shape(rows, cols, bs, n)
+    if not dctn_on_device(config, h * w) or 3 * count * h * w > 2 ** 31 - 1:
+        return None
+    stack = _stacked_pixels(images, config, colour)
+    if stack is None:
+        return None
+    import jpegx
+    out = np.empty((count, len(divisors)), dtype=np.int64)
+    for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
+        some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
+        got = _none_on_refusal(jpegx.batch_probe_pictures_n, stack, bs, n, "divide", [float(d) for d in some], **_colour_kw(colour))
+        if got is None:
+            return None
+        coded, bad = got
+        # file_format.generate_data: the header, whose JSON changes length with the divisor's digits, then <L length + bytes per band
+        heads = np.array([len(file_format.create_header(_divide_config(config, d))) for d in some], dtype=np.int64)
+        part = coded.sum(axis=1).astype(np.int64) + heads[None, :] + 3 * 4
+        part[bad.any(axis=1)] = -1
+        out[:, at:at + len(some)] = part
+    return out
+
+
+def probe_picture_sizes(images, config, divisors, colour=None):
+    """int64 [len(images)][len(divisors)]: entry [i][j] is len(Jpeg(config_j).compress(images[i])) -- with colour='rgb', of
+    compress_rgb -- where config_j is ``config`` with QuantizationMethod('divide', divisor=divisors[j]); -1 where that call
+    raises BadRleCodeError.  The header and the 12 bytes of length prefixes are counted.  ``images`` as compress_pictures takes
+    them.  ValueError for a configuration that is not 'divide' and for a divisor that is not a whole positive number.
+    With at least DCTN_PROBE_MIN_CANDIDATES divisors, dct_size other than 8 with transform 'DCT', the stock steps, a usable
+    device, pictures that _stacked_pixels accepts and planes of at least DCTN_MIN_SAMPLES samples, all divisors are sized on the
+    device in one pass per 32 of them (jpegx.batch_probe_pictures_n); everything else, and every refusal, is the loop."""
+    _check_colour(colour)
+    divisors = _checked_divisors(config, divisors)
+    if not isinstance(images, np.ndarray):
+        images = list(images)
+    sizes = _probe_device(images, config, divisors, colour) if len(divisors) else None
+    return sizes if sizes is not None else _probe_loop(images, config, divisors, colour)
+
+
+def _geometric(lo, hi, probes):
+    """``probes`` whole numbers spaced geometrically from lo to hi inclusive, deduplicated and ascending."""
+    if probes < 2 or lo == hi:
+        return sorted({lo, hi})
+    ratio = float(hi) / float(lo)
+    return sorted({lo, hi} | {min(hi, max(lo, int(round(lo * ratio ** (i / (probes - 1.0)))))) for i in range(1, probes - 1)})
+
+
+def _between(g, f, probes):
+    """Up to ``probes`` of the whole numbers strictly between g and f, evenly spaced by index; all of them if that many or fewer."""
+    m = f - g - 1
+    if m <= probes:
+        return list(range(g + 1, f))
+    if probes < 2:
+        return [g + 1 + (m - 1) // 2]
+    return sorted({g + 1 + (i * (m - 1)) // (probes - 1) for i in range(probes)})
+
+
+def _fits(size, max_bytes):
+    return size != -1 and size <= max_bytes
+
+
+def compress_to_size(image, config, max_bytes, colour=None, lo=1, hi=4096, probes=16, rounds=3):
+    """(container, divisor): ``image`` compressed under ``config`` with the smallest 'divide' divisor the search below finds
+    whose container holds at most ``max_bytes`` bytes; the container is Jpeg(config_divisor).compress(image) (compress_rgb with
+    colour='rgb').  The search is deterministic and costs 1 + ``rounds`` calls of probe_picture_sizes at most:
+      1. candidates: ``probes`` whole numbers spaced geometrically from ``lo`` to ``hi`` inclusive;
+      2. f = the smallest candidate whose size is neither -1 (BadRleCodeError) nor above max_bytes -- none: TargetSizeError;
+         g = the candidate just below f, or lo - 1;
+      3. while rounds remain and whole numbers lie strictly between g and f: up to ``probes`` of them, evenly spaced, are
+         probed; f becomes the smallest of them that fits (it stays if none does), g the probed number just below the new f (the
+         old g if there is none);
+      4. compress with f; RuntimeError if the container's length is not the probed one.
+    Sizes need not fall monotonically with the divisor: f is the smallest FITTING number the search has seen above a number
+    that does not fit, not a global minimum."""
+    _check_colour(colour)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lo, hi, probes, rounds)) \
+            or lo < 1 or hi < lo or probes < 1 or rounds < 0:
+        raise ValueError("compress_to_size: lo, hi, probes and rounds must be whole numbers with 1 <= lo <= hi, probes >= 1, rounds >= 0")
+    lo, hi, probes, rounds = int(lo), int(hi), int(probes), int(rounds)
+    seen = {}                                            # divisor -> probed size
+
+    def probe(candidates):
+        sizes = probe_picture_sizes([image], config, candidates, colour)[0]
+        seen.update((d, int(s)) for d, s in zip(candidates, sizes))
+
+    candidates = _geometric(lo, hi, probes)
+    probe(candidates)
+    fitting = [d for d in candidates if _fits(seen[d], max_bytes)]
+    if not fitting:
+        coded = [(s, d) for d, s in seen.items() if s != -1]
+        if not coded:
+            raise TargetSizeError("no divisor in %d..%d codes the picture at all (BadRleCodeError at every candidate)" % (lo, hi))
+        raise TargetSizeError("no divisor in %d..%d brings the picture within %d bytes: the smallest size seen is %d bytes, at divisor %d"
+                              % ((lo, hi, max_bytes) + min(coded)))
+    f = fitting[0]
+    g = max([d for d in candidates if d < f], default=lo - 1)
+    for _ in range(rounds):
+        inner = _between(g, f, probes)
+        if not inner:
+            break
+        probe(inner)
+        fitting = [d for d in inner if _fits(seen[d], max_bytes)]
+        if fitting:
+            f = fitting[0]
+        g = max([d for d in inner if d < f], default=g)
+    container = _compress_one(image, _divide_config(config, f), colour)
+    if len(container) != seen[f]:
+        raise RuntimeError("compress_to_size: divisor %d was probed at %d bytes, its container holds %d" % (f, seen[f], len(container)))
+    return container, f
+
+
+def compress_pictures_to_size(images, config, max_bytes, divisors, colour=None):
+    """(containers, chosen): every picture compressed with the smallest divisor of the ascending ladder ``divisors`` (at most
+    32 rungs) that brings its container within ``max_bytes`` bytes; chosen[i] is picture i's divisor and containers[i] equals
+    Jpeg(config_chosen[i]).compress(images[i]) (compress_rgb with colour='rgb'), byte for byte.  ONE probe_picture_sizes call
+    sizes the whole batch on every rung; the pictures of a rung are then one compress_pictures call.  TargetSizeError names
+    the first picture that fits no rung."""
+    _check_colour(colour)
+    ladder = _checked_divisors(config, divisors)
+    if not 1 <= len(ladder) <= 32 or any(b <= a for a, b in zip(ladder, ladder[1:])):
+        raise ValueError("compress_pictures_to_size: divisors must be 1..32 ascending rungs")
+    if not isinstance(images, np.ndarray):
+        images = list(images)
+    sizes = probe_picture_sizes(images, config, ladder, colour)
+    rung = []
+    for i, row in enumerate(sizes):
+        fitting = [j for j, s in enumerate(row) if _fits(int(s), max_bytes)]
+        if not fitting:
+            coded = [(int(s), ladder[j]) for j, s in enumerate(row) if s != -1]
+            raise TargetSizeError("picture %d fits no rung within %d bytes%s" % (
+                i, max_bytes, ": its smallest size is %d bytes, at divisor %d" % min(coded) if coded else " (BadRleCodeError at every rung)"))
+        rung.append(fitting[0])
+    containers = [None] * len(rung)
+    for j in sorted(set(rung)):
+        members = [i for i, r in enumerate(rung) if r == j]
+        group = images[members] if isinstance(images, np.ndarray) else [images[i] for i in members]
+        for i, c in zip(members, compress_pictures(group, _divide_config(config, ladder[j]), colour)):
+            containers[i] = c
+    return containers, [ladder[j] for j in rung]

@@ -619,6 +619,42 @@ int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned lon
                                       int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                       jpegx_stream_t stream);
 
+/* ---- size probe: what the coded bands would weigh under each of K candidate quantiser parameters, in one pass
+ * (csrc/jpegx_probe_n.hip; dct_size 2..32 through the run-time-N kernels) --------------------------------------------------
+ * For every plane p and candidate q: the length of the band's stream after Quantization with candidate q
+ * (pipeline/quantization.py, quantizers.py:23-31: `divide` rounds block / divisor, `discard` keeps the top-left keep x keep
+ * coefficients), RunLengthEncoding.execute (pipeline/run_length_encoding.py:47-64) and RleBytestream.execute
+ * (pipeline/rle_byte_stream.py:48-59) -- the sum over the plane's blocks of what jpegx_forward_fused_n + jpegx_entropy_sizes_n
+ * give per block when they are run once per candidate, from the SAME integers: the kernel runs the forward kernel's two
+ * passes, keeps the float64 coefficients in LDS and quantises them K times with the forward kernel's own functions.  No
+ * coefficient stream is written.
+ * d_totals [nplanes][K], 8-byte aligned: bits 0..62 the length in bytes; bit 63 = an amplitude beyond 15 bits (|a| > 16383,
+ * the reference's BadRleCodeError) somewhere in plane p under candidate q -- the low bits are then unspecified.
+ * jpegx_probe_sizes_n (enqueue only: one memset of d_totals, one kernel): d_planes holds nplanes float64 planes of whole
+ * blocks stacked as one tall plane [nplanes * H][pitch] (what jpegx_band_planes_packed_stacked_n and
+ * jpegx_band_planes_stacked_n write).  mode JPEGX_Q_DIVIDE: h_params are K divisors; JPEGX_Q_DISCARD: K keep values;
+ * JPEGX_Q_NONE: K must be 1 and h_params is not read; JPEGX_Q_QTABLE is refused (it needs dct_size 8).  h_params is a HOST
+ * array, copied into the launch.  Refused before any device work (JPEGX_E_INVALID, the message names the argument): null
+ * pointers, N outside 2..32, nplanes < 1, H or W no positive multiple of N, pitch < W, nplanes * H * W > 2^31 - 1, K outside
+ * 1..JPEGX_PROBE_MAX_CANDIDATES, a parameter that jpegx_forward_fused_n would refuse (a zero, NaN or infinite divisor; a
+ * fractional or negative keep).                                                                                          */
+#define JPEGX_PROBE_MAX_CANDIDATES 32
+int jpegx_probe_sizes_n(const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int N, int mode,
+                        const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+/* The same for a stack of pictures (or, with nbands = 1 and colour = 0, of bands) from their 8-bit pixels: group by group
+ * of whole pictures -- groups, limits and group_planes as jpegx_batch_compress_pictures_n has them --
+ * jpegx_band_planes_packed_stacked_n into the scratch, then jpegx_probe_sizes_n on the group's planes into the group's rows
+ * of d_totals [nbands * npictures][K], plane p * nbands + k band k of picture p.  Entry [p * nbands + k][q] is what plane
+ * p * nbands + k weighs in the plane index of jpegx_batch_compress_pictures_n(..., mode, h_params[q], ...).  Enqueue only:
+ * read d_totals after synchronising the stream.  d_pixels is never written.  The workspace (16-byte aligned) is ONE group
+ * of float64 planes: up256(min(group_planes, nbands * npictures) * H * W * 8) bytes with H, W from jpegx_band_shape_n and
+ * up256 rounding up to 256; jpegx_batch_probe_pictures_workspace_bytes_n returns 0 for a shape the entry refuses.        */
+size_t jpegx_batch_probe_pictures_workspace_bytes_n(int npictures, int nbands, int rows, int cols, int bs, int N,
+                                                    int group_planes);
+int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                 int colour, int bs, int N, int mode, const double *h_params, int K, int group_planes,
+                                 void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
+
 /* ---- batch codec for a SET of pictures of UNEQUAL sizes at any DCT size but 8 (csrc/jpegx_batch_set_n.cpp,
  * csrc/jpegx_band_set_n.hip) ----------------------------------------------------------------------------------------------
  * Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124; with colour = 1 behind compress.py:9 and in
@@ -1219,6 +1255,11 @@ int jpegx_batch_decompress_pictures_n_on(int device, const uint8_t *d_bytes, con
                                          int npictures, int nbands, int rows, int cols, int bs, int N, int mode, double param,
                                          int colour, int group_planes, void *d_workspace, uint8_t *d_out, ptrdiff_t out_pitch,
                                          jpegx_stream_t stream);
+int jpegx_probe_sizes_n_on(int device, const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int N, int mode,
+                           const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_pictures_n_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                    ptrdiff_t pitch, int colour, int bs, int N, int mode, const double *h_params, int K,
+                                    int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
 int jpegx_picture_planes_stacked_u8_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
                                        ptrdiff_t pitch, int colour, int bs, uint8_t *d_out, ptrdiff_t out_pitch,
                                        jpegx_stream_t stream);
