@@ -19,9 +19,16 @@
 // d_totals, with 64-bit integer atomics, only when the run leaves the plane or ends -- a few hundred atomics per
 // (plane, candidate) for the largest plane instead of one per turn.  Integer adds and ORs commute (the sums stay far below
 // 2^63), so the totals do not depend on the order in which workgroups run.
+//
+// Planes of unequal block counts (jpegx_probe_sizes_set_n: the block strip of a set of pictures, jpegx_band_set_n.hip) go
+// through the same kernel as k_probe_n<true>: the one thing that differs is which plane a block belongs to.  Equal planes
+// divide (g / blocks per plane); ragged planes are looked up in the table's ascending array of first blocks, once per turn
+// and block, by a binary search whose results sit in LDS for the turn (rowtab).  The plane index is monotone in g either way,
+// which is all the carried sums need: a turn whose successor starts in the turn's own first plane lies inside that plane.
 #include "jpegx_internal.h"
 #include "jpegx_dctn_device.h"
 #include "jpegx_entropy_n_device.h"
+#include "jpegx_picture_set_device.h"      // check_range and the table's views, for the ragged entry
 
 namespace {
 
@@ -37,11 +44,27 @@ struct ProbeParams {
     int use_mul[PROBE_MAX_K];
 };
 
-// bpp: blocks per plane; nturns: ceil(nblk / bpw); run: turns per workgroup
+// the plane of block g among nplanes planes whose first blocks are pf[0] < pf[1] < ... < pf[nplanes] = pf[0] + nblk: the p
+// with pf[p] - pf[0] <= g < pf[p + 1] - pf[0], for 0 <= g < nblk
+__device__ inline int plane_of_block(const long long *__restrict__ pf, int nplanes, long long g)
+{
+    const long long v = g + pf[0];
+    int lo = 0, hi = nplanes;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pf[mid] <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// bpp: blocks per plane; nturns: ceil(nblk / bpw); run: turns per workgroup.  RAGGED: the planes' block counts differ, block g
+// belongs to plane_of_block(pf, bpp, g) -- bpp then holds the PLANE COUNT and pf points at the first plane's entry of the
+// table's device array of first blocks; without RAGGED pf is not read
+template <bool RAGGED>
 __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restrict__ in, size_t pitch, int N, int wb, int nblk, int bpp,
                                                          const double *__restrict__ g_ct, const uint16_t *__restrict__ g_zig, int mode,
                                                          int K, ProbeParams pp, int nturns, int run,
-                                                         unsigned long long *__restrict__ totals)
+                                                         unsigned long long *__restrict__ totals, const long long *__restrict__ pf)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int nn = N * N, bpw = dctn_blocks_per_wg(N), nelem = bpw * nn;
@@ -49,7 +72,9 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restri
     double *A = T + nn;            // [b][i][j]: the samples, later the coefficients
     double *M = A + nelem;         // [b][i][k]: after the row pass
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(M + nelem);      // [plane - first plane of the turn][K]
-    uint16_t *Z = reinterpret_cast<uint16_t *>(acc + bpw * K);
+    // RAGGED: rowtab[b] = the plane of the turn's block b, rowtab[bpw] = the plane of the next turn's first block (-1: none)
+    int *rowtab = reinterpret_cast<int *>(acc + bpw * K);
+    uint16_t *Z = reinterpret_cast<uint16_t *>(RAGGED ? static_cast<void *>(rowtab + bpw + 2) : static_cast<void *>(rowtab));
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -63,8 +88,12 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restri
     for (int turn = turn0; turn < turn1; ++turn) {
         const long long first = (long long)turn * bpw;
         const int nlive = (int)min((long long)bpw, (long long)nblk - first);
-        const int plane0 = (int)(first / bpp);
-        __syncthreads();                                       // the tables; the units of the turn before are done with A
+        int plane0 = RAGGED ? 0 : (int)(first / bpp);
+        __syncthreads();                                       // the tables; the units of the turn before are done with A and rowtab
+        if (RAGGED && tid <= bpw) {
+            const long long g = first + tid;
+            rowtab[tid] = g < nblk ? plane_of_block(pf, bpp, g) : -1;
+        }
         for (int e = tid; e < nelem; e += DCTN_THREADS) {
             const PlaneSpot s = plane_spot(e, N, bpw, first, wb, nblk, pitch);
             A[s.lds] = s.live ? in[s.glob] : 0.0;
@@ -92,7 +121,8 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restri
             const int src = Z[pos], k = src / N, l = src - k * N;
             return dctn_to_i32(dctn_quant(A[b * nn + src], k, l, mode, pp.param[q], pp.inv[q], pp.use_mul[q]));
         };
-        auto row_of = [&](int b) { return (int)((first + b) / bpp) - plane0; };
+        if (RAGGED) plane0 = rowtab[0];
+        auto row_of = [&](int b) { return RAGGED ? rowtab[b] - plane0 : (int)((first + b) / bpp) - plane0; };
 
         if (nn < 64) {
             const int per = 64 / nn, ngrp = (nlive + per - 1) / per;
@@ -140,7 +170,7 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restri
 
         // the sums leave when the run leaves the turn's first plane or ends; otherwise the turn lay inside one plane and its
         // row 0 is the next turn's row 0
-        const bool leave = turn + 1 == turn1 || (int)(((long long)(turn + 1) * bpw) / bpp) != plane0;
+        const bool leave = turn + 1 == turn1 || (RAGGED ? rowtab[bpw] : (int)(((long long)(turn + 1) * bpw) / bpp)) != plane0;
         if (leave) {
             const int rows = row_of(nlive - 1) + 1;
             for (int e = tid; e < rows * K; e += DCTN_THREADS) {
@@ -155,10 +185,50 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_probe_n(const double *__restri
     }
 }
 
-size_t probe_lds_bytes(int N, int K)
+size_t probe_lds_bytes(int N, int K, bool ragged)
 {
     const size_t nn = (size_t)N * N, bpw = dctn_blocks_per_wg(N), nelem = nn * bpw;
-    return (nn + 2 * nelem + bpw * K) * 8 + nn * 2;
+    return (nn + 2 * nelem + bpw * K) * 8 + nn * 2 + (ragged ? (bpw + 2) * 4 : 0);
+}
+
+// the candidates as the kernel takes them (checked by jpegx_internal_probe_check_params)
+ProbeParams probe_params(int mode, const double *h_params, int K)
+{
+    ProbeParams pp;
+    for (int q = 0; q < PROBE_MAX_K; ++q) {
+        const double param = q < K && mode != JPEGX_Q_NONE ? h_params[q] : 1.0;
+        int e2 = 0;
+        const double mant = frexp(fabs(param), &e2);
+        pp.param[q] = param;
+        pp.use_mul[q] = mode == JPEGX_Q_DIVIDE && mant == 0.5;        // d = +-2^e: y * (1 / d) is the same double as y / d
+        pp.inv[q] = mode == JPEGX_Q_DIVIDE ? 1.0 / param : 1.0;
+    }
+    return pp;
+}
+
+// one memset of the totals' rows and one launch over nblk blocks: planes of bpp blocks each, or (pf) nplanes ragged planes
+int probe_launch(const double *d_in, size_t pitch, int N, int wb, int nblk, int nplanes, int bpp, const long long *pf, int mode,
+                 const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const ProbeParams pp = probe_params(mode, h_params, K);
+    const double *ct = nullptr;
+    const uint16_t *zig = nullptr;
+    const int rc = jpegx_internal_dctn_forward_tables(N, &ct, &zig);
+    if (rc) return rc;
+    const int bpw = dctn_blocks_per_wg(N);
+    const int nturns = (nblk + bpw - 1) / bpw;
+    const int run = (nturns + PROBE_MAX_WORKGROUPS - 1) / PROBE_MAX_WORKGROUPS;
+    const unsigned grid = (unsigned)((nturns + run - 1) / run);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)nplanes * K * 8, st));
+    if (pf)
+        hipLaunchKernelGGL(k_probe_n<true>, dim3(grid), dim3(DCTN_THREADS), probe_lds_bytes(N, K, true), st, d_in, pitch, N, wb, nblk, nplanes, ct,
+                           zig, mode, K, pp, nturns, run, d_totals, pf);
+    else
+        hipLaunchKernelGGL(k_probe_n<false>, dim3(grid), dim3(DCTN_THREADS), probe_lds_bytes(N, K, false), st, d_in, pitch, N, wb, nblk, bpp, ct,
+                           zig, mode, K, pp, nturns, run, d_totals, pf);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
 }
 
 int probe_fail(const char *who, const char *what)
@@ -210,28 +280,28 @@ int jpegx_probe_sizes_n(const double *d_planes, int nplanes, int H, int W, ptrdi
     int rc = jpegx_internal_probe_check_params(who, mode, h_params, K);
     if (rc) return rc;
 
-    ProbeParams pp;
-    for (int q = 0; q < PROBE_MAX_K; ++q) {
-        const double param = q < K && mode != JPEGX_Q_NONE ? h_params[q] : 1.0;
-        int e2 = 0;
-        const double mant = frexp(fabs(param), &e2);
-        pp.param[q] = param;
-        pp.use_mul[q] = mode == JPEGX_Q_DIVIDE && mant == 0.5;        // d = +-2^e: y * (1 / d) is the same double as y / d
-        pp.inv[q] = mode == JPEGX_Q_DIVIDE ? 1.0 / param : 1.0;
-    }
-    const double *ct = nullptr;
-    const uint16_t *zig = nullptr;
-    if ((rc = jpegx_internal_dctn_forward_tables(N, &ct, &zig))) return rc;
-    const int wb = W / N, bpp = (H / N) * wb, nblk = nplanes * bpp, bpw = dctn_blocks_per_wg(N);
-    const int nturns = (nblk + bpw - 1) / bpw;
-    const int run = (nturns + PROBE_MAX_WORKGROUPS - 1) / PROBE_MAX_WORKGROUPS;
-    const unsigned grid = (unsigned)((nturns + run - 1) / run);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)nplanes * K * 8, st));
-    hipLaunchKernelGGL(k_probe_n, dim3(grid), dim3(DCTN_THREADS), probe_lds_bytes(N, K), st, d_planes, (size_t)pitch, N, wb, nblk, bpp, ct, zig,
-                       mode, K, pp, nturns, run, d_totals);
-    HIP_TRY(hipGetLastError());
-    return JPEGX_OK;
+    const int wb = W / N, bpp = (H / N) * wb;
+    return probe_launch(d_planes, (size_t)pitch, N, wb, nplanes * bpp, nplanes, bpp, nullptr, mode, h_params, K, d_totals, stream);
+}
+
+int jpegx_probe_sizes_set_n(const double *d_strip, const void *h_table, const void *d_table, int p0, int k, int mode, const double *h_params, int K,
+                            unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const char *who = "probe_sizes_set_n";
+    const Head *h = nullptr;
+    int rc = check_range(who, d_strip, h_table, d_table, p0, k, 0, d_totals, &h);
+    if (rc) return rc;
+    if (h->N < DCTN_MIN || h->N > DCTN_MAX) return probe_fail(who, "h_table is not a table of jpegx_picture_set_table");
+    if ((reinterpret_cast<uintptr_t>(d_strip) & 7u) || (reinterpret_cast<uintptr_t>(d_totals) & 7u))
+        return probe_fail(who, "d_strip / d_totals must be 8-byte aligned");
+    if ((rc = jpegx_internal_probe_check_params(who, mode, h_params, K))) return rc;
+    const Entry *he = reinterpret_cast<const Entry *>(h + 1) + p0;
+    const long long nblk = he[k].first - he[0].first;                      // nblk * N * N <= 2^31 - 1: the table's limit
+    if (nblk < 1 || nblk * h->N * h->N > 0x7FFFFFFFLL) return probe_fail(who, "h_table is not a table of jpegx_picture_set_table");
+    // the device array of first blocks behind the npictures + 1 entries, at plane (p0, 0); the strip is a plane of width N
+    const long long *pf = reinterpret_cast<const long long *>(static_cast<const unsigned char *>(d_table) + sizeof(Head) +
+                                                              ((size_t)h->npictures + 1) * sizeof(Entry)) + (size_t)p0 * h->nbands;
+    return probe_launch(d_strip, (size_t)h->N, h->N, 1, (int)nblk, k * h->nbands, 0, pf, mode, h_params, K, d_totals, stream);
 }
 
 }  // extern "C"

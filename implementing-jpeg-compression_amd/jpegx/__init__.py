@@ -224,6 +224,9 @@ SIGNATURES = {
     "jpegx_batch_groups_set_n": [_vp, _vp, _c.c_longlong, _vp, _c.POINTER(_int)],
     "jpegx_batch_decompress_set_workspace_bytes_n": [_sz, _vp, _c.c_longlong],
     "jpegx_batch_decompress_picture_set_n": [_vp, _vp, _vp, _vp, _int, _dbl, _int, _c.c_longlong, _vp, _vp, _vp],
+    "jpegx_probe_sizes_set_n": [_vp, _vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp],
+    "jpegx_batch_probe_picture_set_workspace_bytes_n": [_vp, _c.c_longlong],
+    "jpegx_batch_probe_picture_set_n": [_vp, _vp, _vp, _int, _int, _vp, _int, _c.c_longlong, _vp, _vp, _vp],
     "jpegx_picture_set_blocks_u8": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
     "jpegx_batch_set_workspace_bytes": [_vp, _c.c_longlong],
     "jpegx_batch_set_max_bytes": [_vp],
@@ -266,7 +269,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_picture_set_pixels_u8", "jpegx_batch_compress_picture_set_n", "jpegx_batch_compress_status_set_n",
               "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n", "jpegx_picture_set_blocks_u8",
               "jpegx_batch_compress_picture_set", "jpegx_batch_compress_status_set", "jpegx_batch_emit_set",
-              "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n"):
+              "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n",
+              "jpegx_probe_sizes_set_n", "jpegx_batch_probe_picture_set_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -277,7 +281,8 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_set_workspace_bytes_n": _sz, "jpegx_batch_set_max_bytes_n": _sz,
             "jpegx_batch_decompress_set_workspace_bytes_n": _sz, "jpegx_batch_set_workspace_bytes": _sz,
             "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz,
-            "jpegx_batch_probe_pictures_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_probe_pictures_workspace_bytes_n": _sz,
+            "jpegx_batch_probe_picture_set_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -2203,6 +2208,61 @@ def batch_decompress_picture_set_n(blobs, sizes, bs, n, mode="none", param=0.0, 
         out = dout.download((nout,), np.uint8)
     at = np.concatenate([[0], np.cumsum([r * c * nb for r, c in sizes])])
     return [out[int(at[p]):int(at[p + 1])].reshape(r, c, nb) for p, (r, c) in enumerate(sizes)]
+
+
+# the size probe over a set: planes of unequal block counts through the probe's kernel, which looks a block's plane up in the
+# table's device array of first blocks (csrc/jpegx_probe_n.hip, k_probe_n<true>)
+def probe_sizes_set_n_device(d_strip, table, d_table, p0, k, mode, params, d_totals, stream=None, device=None):
+    """Enqueue jpegx_probe_sizes_set_n: the float64 block strip of pictures p0 .. p0 + k - 1 (picture_set_blocks_n_device) ->
+    uint64 d_totals [k * nbands][K] in the table's plane order: bits 0..62 the coded bytes of the plane under candidate q, bit
+    63 the bad-amplitude flag.  ``params``: the K candidates (host numbers)."""
+    h, nk = _probe_params(params)
+    args = (d_strip, table.ptr, d_table, int(p0), int(k), mode_of(mode), h.ctypes.data, nk, d_totals, stream)
+    L = lib()
+    check(L.jpegx_probe_sizes_set_n(*args) if device is None else L.jpegx_probe_sizes_set_n_on(int(device), *args), "jpegx_probe_sizes_set_n")
+
+
+def batch_probe_picture_set_workspace_bytes_n(table, group_samples=0):
+    return lib().jpegx_batch_probe_picture_set_workspace_bytes_n(table.ptr, int(group_samples))
+
+
+def batch_probe_picture_set_n_device(d_pixels, table, d_table, mode, params, d_workspace, d_totals, colour=0, group_samples=0, stream=None,
+                                     device=None):
+    """Enqueue jpegx_batch_probe_picture_set_n: every picture at its offset in d_pixels -> uint64 d_totals
+    [npictures * nbands][K] in the table's plane order."""
+    h, nk = _probe_params(params)
+    args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), h.ctypes.data, nk, int(group_samples), d_workspace, d_totals, stream)
+    L = lib()
+    check(L.jpegx_batch_probe_picture_set_n(*args) if device is None else L.jpegx_batch_probe_picture_set_n_on(int(device), *args),
+          "jpegx_batch_probe_picture_set_n")
+
+
+def batch_probe_picture_set_n(pictures, bs, n, mode, params, colour=None, group_samples=0):
+    """A sequence of uint8 pictures [rows_p][cols_p][nb], sizes as they come -> (sizes, bad): sizes uint64 [npictures][nb][K],
+    the length of band b of picture p as batch_compress_picture_set_n would code it under candidate q; bad bool of the same
+    shape, True where that band holds an amplitude beyond 15 bits under that candidate (its size is then meaningless).  Host
+    convenience: ONE flat upload, the probe, one download.  JpegxError for more than 32 candidates."""
+    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
+    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
+        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    nb = pics[0].shape[2]
+    flag = _colour_flag(colour, nb, "batch_probe_picture_set_n")
+    table = picture_set_table([p.shape[:2] for p in pics], nb, bs, n)      # names the refusal, before any device is touched
+    h, nk = _probe_params(params)
+    nws = batch_probe_picture_set_workspace_bytes_n(table, group_samples)
+    if nws == 0 or not 1 <= nk <= PROBE_MAX_CANDIDATES:     # the entry names the refusal, before any device is touched
+        batch_probe_picture_set_n_device(1, table, 8, mode, h, 16, 8, flag, group_samples)
+        raise JpegxError("batch_probe_picture_set_n: the set was refused")
+    mode_of(mode)
+    require_device()
+    flat = np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pics])
+    with _Buffers() as dev:
+        din, dtab, dws, dtot = dev(flat.nbytes), dev(table.nbytes), dev(nws), dev(len(pics) * nb * nk * 8)
+        din.upload(flat)
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_probe_picture_set_n_device(din.ptr, table, dtab.ptr, mode, h, dws.ptr, dtot.ptr, flag, group_samples)
+        raw = dtot.download((len(pics), nb, nk), np.uint64)
+    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1733,3 +1733,143 @@ def compress_pictures_to_size(images, config, max_bytes, divisors, colour=None):
         for i, c in zip(members, compress_pictures(group, _divide_config(config, ladder[j]), colour)):
             containers[i] = c
     return containers, [ladder[j] for j in rung]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the same for a SET of pictures of unequal sizes, each under the configuration at its own size (compress_picture_set)
+# ---------------------------------------------------------------------------------------------------------------------
+# probe_picture_set_sizes takes the device road (jpegx.batch_probe_picture_set_n: one flat upload, per group of pictures one
+# gather into the block strip and one pass of the probe's kernel with the planes looked up in the set's table, one download)
+# from DCTN_PROBE_MIN_CANDIDATES divisors and this many ADMITTED pictures on; None: the road is off and the function is the
+# loop.  Read when the function is called.  Never below 1.
+# Measured (profiles/probe_set_n.json and, a second run of the same code, _run2.json; pictures with sides between
+# 64 and 128 at N 4 and N 16, 2 and 16 divisors, the set probe against the loop and against one probe_picture_sizes call per
+# distinct size, alternating call by call on one MI355X; figures of the first run, the second agrees on every verdict here):
+# the set probe beat the loop at every count (6-96x).  With ONE admitted picture it lost to probe_picture_sizes on that
+# picture in all four comparisons of either run (0.18 against 0.14 ms with 2 divisors, 0.26 against 0.21-0.23 ms with 16:
+# the table and its upload on top of the same work); with 2 pictures of 2 sizes it won all of them (0.20-0.21 against
+# 0.26-0.27 ms, 0.34-0.35 against 0.41-0.43 ms), with 4 by 1.4-1.6x, with 16 by 1.8-2.4x, with 64 by 2.1-3.8x.  The smallest count with no
+# loss at or above it; no plane size lost at every count, so there is no size gate.  A lone admitted picture is the loop here:
+# callers with one picture have probe_picture_sizes.
+DCTN_PROBE_SET_MIN_PICTURES = 2
+
+
+def _probe_set_row(image, config, divisors, colour):
+    """One row of the literal loop: len(Jpeg(config_ij).compress(image)) under the configuration at the picture's own size,
+    -1 where it raises the reference's BadRleCodeError."""
+    import util
+    sized = _sized(config, image.height, image.width)
+    row = np.empty(len(divisors), dtype=np.int64)
+    for j, d in enumerate(divisors):
+        try:
+            row[j] = len(_compress_one(image, _divide_config(sized, d), colour))
+        except util.BadRleCodeError:
+            row[j] = -1
+    return row
+
+
+def _probe_set_device(images, config, divisors, colour):
+    """{index: int64 row of sizes} of the pictures that were sized on the device as one set; empty where the gates, the
+    configuration or libjpegx say no.  The vetting is _compress_picture_set's without its size ceiling."""
+    gate, least = DCTN_PROBE_MIN_CANDIDATES, DCTN_PROBE_SET_MIN_PICTURES
+    if gate is None or least is None or len(divisors) < max(gate, 1) or len(images) < max(least, 1) \
+            or not _stock_registry() or not _device_usable():
+        return {}
+    import jpegx
+    admitted, job = [], None                            # (index, rows, cols)
+    for at, im in enumerate(images):
+        try:
+            rows, cols = im.height, im.width
+        except Exception:
+            continue
+        if not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 or rows * cols > 2 ** 31 - 1:
+            continue
+        sized = _sized(config, rows, cols)
+        if _picture_size(im, sized) is None or (colour is not None and im.mode != "RGB"):
+            continue
+        this = _compress_job_n(sized, rows, cols, 0)
+        if this is None:
+            continue
+        job = this                                      # (block_size, dct_size, mode, param): the same for every picture
+        admitted.append((at, rows, cols))
+    if len(admitted) < max(least, 1):
+        return {}
+    if 3 * sum(h * w for h, w in (_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted)) > 2 ** 31 - 1:
+        return {}
+    pixels = [_picture_pixels(images[at]) for at, _, _ in admitted]      # the costly part of the vetting: last
+    keep = [k for k, p in enumerate(pixels) if p is not None]
+    if len(keep) != len(pixels):
+        admitted, pixels = [admitted[k] for k in keep], [pixels[k] for k in keep]
+        if len(admitted) < max(least, 1):
+            return {}
+    out = np.empty((len(admitted), len(divisors)), dtype=np.int64)
+    heads = {}                                           # (rows, cols, divisor) -> the header's length
+    for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
+        some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
+        got = _none_on_refusal(jpegx.batch_probe_picture_set_n, pixels, job[0], job[1], "divide", [float(d) for d in some], **_colour_kw(colour))
+        if got is None:
+            return {}
+        coded, bad = got
+        # file_format.generate_data: the header of the picture's OWN configuration, then <L length + bytes per band
+        for (_, rows, cols) in admitted:
+            for d in some:
+                if (rows, cols, d) not in heads:
+                    heads[(rows, cols, d)] = len(file_format.create_header(_divide_config(_sized(config, rows, cols), d)))
+        lengths = np.array([[heads[(rows, cols, d)] for d in some] for _, rows, cols in admitted], dtype=np.int64)
+        part = coded.sum(axis=1).astype(np.int64) + lengths + 3 * 4
+        part[bad.any(axis=1)] = -1
+        out[:, at:at + len(some)] = part
+    return {at: out[k] for k, (at, _, _) in enumerate(admitted)}
+
+
+def probe_picture_set_sizes(images, config, divisors, colour=None):
+    """int64 [len(images)][len(divisors)]: entry [i][j] is len(Jpeg(config_ij).compress(images[i])) -- with colour='rgb', of
+    compress_rgb -- where config_ij is ``config`` with picture i's own width and height (``config``'s own are not read) and
+    QuantizationMethod('divide', divisor=divisors[j]); -1 where that call raises BadRleCodeError.  The header of config_ij and
+    the 12 bytes of length prefixes are counted.  ``images``: a sequence of PIL images, sizes as they come.  ValueError as
+    probe_picture_sizes raises it.
+    The pictures that compress_picture_set admits (_picture_size, _compress_job_n with the picture's own size, _picture_pixels;
+    with colour='rgb' of mode RGB; no ceiling on the plane) are sized on the device as ONE set, 32 divisors to a pass
+    (jpegx.batch_probe_picture_set_n), when there are at least DCTN_PROBE_SET_MIN_PICTURES of them and at least
+    DCTN_PROBE_MIN_CANDIDATES divisors; every other picture, and all of them after a refusal, are the loop.  Rows come back
+    in input order."""
+    _check_colour(colour)
+    divisors = _checked_divisors(config, divisors)
+    images = list(images)
+    done = _probe_set_device(images, config, divisors, colour) if images and divisors else {}
+    out = np.empty((len(images), len(divisors)), dtype=np.int64)
+    for at, im in enumerate(images):
+        out[at] = done[at] if at in done else _probe_set_row(im, config, divisors, colour)
+    return out
+
+
+def compress_picture_set_to_size(images, config, max_bytes, divisors, colour=None):
+    """compress_pictures_to_size for a set of pictures of unequal sizes: (containers, chosen), every picture compressed under
+    the configuration at its own size with the smallest divisor of the ascending ladder ``divisors`` (at most 32 rungs) that
+    brings its container within ``max_bytes`` bytes; containers[i] equals Jpeg(config_i with chosen[i]).compress(images[i])
+    (compress_rgb with colour='rgb'), byte for byte.  ONE probe_picture_set_sizes call sizes the set on every rung; the
+    pictures of a rung are then one compress_picture_set call.  TargetSizeError names the first picture that fits no rung;
+    RuntimeError if a container's length is not the probed one."""
+    _check_colour(colour)
+    ladder = _checked_divisors(config, divisors)
+    if not 1 <= len(ladder) <= 32 or any(b <= a for a, b in zip(ladder, ladder[1:])):
+        raise ValueError("compress_picture_set_to_size: divisors must be 1..32 ascending rungs")
+    images = list(images)
+    sizes = probe_picture_set_sizes(images, config, ladder, colour)
+    rung = []
+    for i, row in enumerate(sizes):
+        fitting = [j for j, s in enumerate(row) if _fits(int(s), max_bytes)]
+        if not fitting:
+            coded = [(int(s), ladder[j]) for j, s in enumerate(row) if s != -1]
+            raise TargetSizeError("picture %d fits no rung within %d bytes%s" % (
+                i, max_bytes, ": its smallest size is %d bytes, at divisor %d" % min(coded) if coded else " (BadRleCodeError at every rung)"))
+        rung.append(fitting[0])
+    containers = [None] * len(rung)
+    for j in sorted(set(rung)):
+        members = [i for i, r in enumerate(rung) if r == j]
+        for i, c in zip(members, compress_picture_set([images[i] for i in members], _divide_config(config, ladder[j]), colour)):
+            if len(c) != int(sizes[i][j]):
+                raise RuntimeError("compress_picture_set_to_size: picture %d was probed at %d bytes under divisor %s, its container holds %d"
+                                   % (i, int(sizes[i][j]), ladder[j], len(c)))
+            containers[i] = c
+    return containers, [ladder[j] for j in rung]

@@ -759,6 +759,26 @@ size_t jpegx_batch_decompress_set_workspace_bytes_n(size_t nbytes, const void *h
 int jpegx_batch_decompress_picture_set_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table,
                                          const void *d_table, int mode, double param, int colour, long long group_samples,
                                          void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+/* The size probe (above) for a set: planes of unequal block counts through the same kernel, which finds a block's plane in
+ * the table's device array of first blocks instead of dividing by one block count (csrc/jpegx_probe_n.hip).
+ * jpegx_probe_sizes_set_n (enqueue only: one memset of its rows of d_totals, one kernel): d_strip is the float64 block strip of
+ * pictures p0 .. p0 + k - 1 as jpegx_picture_set_blocks_n writes it; d_totals [k * nbands][K] in the table's plane order
+ * (picture-major, then band), row 0 band 0 of picture p0.  Bits 0..62 the coded bytes of the plane under candidate q, bit 63 the
+ * bad-amplitude flag; modes, candidates and their meaning as jpegx_probe_sizes_n.  Refused before any device work
+ * (JPEGX_E_INVALID): null pointers, a blob that is no table, a range outside the table, d_strip, d_table or d_totals not
+ * 8-byte aligned, and whatever jpegx_probe_sizes_n refuses of mode, h_params and K.
+ * jpegx_batch_probe_picture_set_n (enqueue only): group by group with the cut of jpegx_batch_compress_picture_set_n (whole
+ * pictures within group_samples, one at least) the gather into the workspace and the probe into the group's rows of
+ * d_totals [npictures * nbands][K]: entry [p * nbands + b][q] is what plane (p, b) weighs in the plane index of
+ * jpegx_batch_compress_picture_set_n(..., mode, h_params[q], ...).  The workspace (16-byte aligned) is ONE group's strip:
+ * jpegx_batch_probe_picture_set_workspace_bytes_n = up256(8 * samples of the largest group), 0 for what the entry refuses of
+ * the table and group_samples.  Refused as the compress entry refuses, plus the candidates and d_totals' alignment.       */
+int jpegx_probe_sizes_set_n(const double *d_strip, const void *h_table, const void *d_table, int p0, int k, int mode,
+                            const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+size_t jpegx_batch_probe_picture_set_workspace_bytes_n(const void *h_table, long long group_samples);
+int jpegx_batch_probe_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
+                                    const double *h_params, int K, long long group_samples, void *d_workspace,
+                                    unsigned long long *d_totals, jpegx_stream_t stream);
 
 /* ---- batch codec for whole pictures at dct_size 8(csrc/jpegx_picture_u8.hip, csrc/jpegx_batch.cpp) -------------------
  * jpegx_picture_planes_stacked_u8 (enqueue only): pictures stacked [npictures * rows][pitch], every row cols * nbands
@@ -1297,6 +1317,11 @@ int jpegx_batch_emit_set_on(int device, void *d_workspace, const void *h_table, 
 int jpegx_batch_decompress_picture_set_on(int device, const uint8_t *d_bytes, const unsigned long long *h_plane_offsets,
                                           const void *h_table, const void *d_table, int mode, double param, int colour,
                                           long long group_samples, void *d_workspace, uint8_t *d_out, jpegx_stream_t stream);
+int jpegx_probe_sizes_set_n_on(int device, const double *d_strip, const void *h_table, const void *d_table, int p0, int k,
+                               int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_picture_set_n_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table,
+                                       int colour, int mode, const double *h_params, int K, long long group_samples,
+                                       void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
