@@ -30,6 +30,9 @@
 // jpegx_band_plane_n makes of pixels[p][:, :, k]; jpegx_inflate_crop_pack_stacked_u8 is the way back.  With colour = 1 the
 // pixels are RGB and the planes Pillow's YCbCr (compress.py:9, decompress.py:9-10): the conversion of jpegx_colour.hip on
 // every pixel the gather reads and on every source triple the scatter replicates.
+// And, for the distortion probe (jpegx_distort_n.hip), the MOMENTS of the tiles behind the samples of such a stack:
+// jpegx_band_moments_packed_stacked_n writes, per sample, the sum and the sum of squares of the pixels that the decoded sample
+// will stand for after steps 2-0 inverted, from which a squared error follows without any decoded picture.
 // Part of libjpegx.so (C ABI: include/jpegx.h).
 #include <limits.h>
 
@@ -559,6 +562,63 @@ unsigned stacked_blocks(unsigned long long items)
     return COLOUR && blocks > COLOUR_MAX_BLOCKS ? COLOUR_MAX_BLOCKS : (unsigned)blocks;
 }
 
+// ---- the moments of the same tiles, for the distortion probe (jpegx_distort_n.hip) --------------------------------------------
+// After DCTPadding.invert, SubSampling.invert and Padding.invert (pipeline/dct_padding.py:11-21, pipeline/subsampling.py:13-14,
+// pipeline/padding.py:14-16) a decoded sample s of plane (p, k) at (y, x) stands for the pixels of its bs x bs tile that lie inside
+// rows x cols: rows y * bs .. min((y + 1) * bs, rows) - 1, columns likewise -- the LIVE pixels, none for a sample of either
+// padding.  Over them sum (v - s)^2 = S2 - 2 s S1 + cnt s^2 with S1 = sum v, S2 = sum v^2: this kernel writes S2 << 32 | S1
+// per sample (bs <= 255: S1 <= 255 * 65025 < 2^24, S2 <= 65025^2 < 2^32), 0 where no pixel is live.  The lane is
+// k_band_planes_packed_stacked_n's, one sample of every band; only live pixels are read, so every read lies inside picture p.
+template <int NB, bool COLOUR>
+__global__ __launch_bounds__(256) void k_band_moments_packed_stacked_n(const uint8_t *__restrict__ px, size_t pitch, int rows, int cols, int bs, int H, int W,
+                                                                       long long items, unsigned long long *__restrict__ out, size_t opitch)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? FWD_TABLES * 256 : 8];
+    if (COLOUR) fill_colour_tables<false>(t);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int tt = (int)(i / W), x = (int)(i - (long long)tt * W);
+        const int p = tt / H, y = tt - p * H;
+        const long long r0 = (long long)y * bs, c0 = (long long)x * bs;
+        const int nr = r0 < rows ? (int)min((long long)bs, rows - r0) : 0, nc = c0 < cols ? (int)min((long long)bs, cols - c0) : 0;
+        const uint8_t *pic = px + (size_t)p * rows * pitch;                 // picture p's first row
+        unsigned s1[NB], s2[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s1[k] = s2[k] = 0;
+        if (nc > 0) {
+            for (int u = 0; u < nr; ++u) {
+                const uint8_t *q = pic + (size_t)(r0 + u) * pitch + (size_t)c0 * NB;
+                for (int w = 0; w < nc; ++w) {
+                    unsigned v[NB];
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) v[k] = q[w * NB + k];
+                    if (COLOUR) {
+                        unsigned o0, o1, o2;
+                        colour_forward_px(t, v[0], v[1 % NB], v[2 % NB], o0, o1, o2);
+                        v[0] = o0; v[1 % NB] = o1; v[2 % NB] = o2;
+                    }
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) {
+                        s1[k] += v[k];
+                        s2[k] += v[k] * v[k];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) out[((size_t)(p * NB + k) * H + y) * opitch + x] = ((unsigned long long)s2[k] << 32) | s1[k];
+    }
+}
+
+template <int NB, bool COLOUR>
+void launch_band_moments_packed_stacked_n(const uint8_t *px, size_t pitch, int npictures, int rows, int cols, int bs, int H, int W,
+                                          unsigned long long *out, size_t opitch, hipStream_t st)
+{
+    const long long items = (long long)npictures * H * W;                   // below 2^31: npictures * NB * H * W is
+    hipLaunchKernelGGL((k_band_moments_packed_stacked_n<NB, COLOUR>), dim3(stacked_blocks<COLOUR>((unsigned long long)items)), dim3(256), 0, st, px, pitch,
+                       rows, cols, bs, H, W, items, out, opitch);
+}
+
 template <int NB, bool COLOUR>
 void launch_band_planes_packed_stacked_n(const uint8_t *px, size_t pitch, int npictures, int rows, int cols, int bs, int H, int W, double *out, size_t opitch,
                                          hipStream_t st)
@@ -767,6 +827,35 @@ int jpegx_band_planes_packed_stacked_n(const uint8_t *d_pixels, int npictures, i
     case 2: launch_band_planes_packed_stacked_n<2, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
     case 3: launch_band_planes_packed_stacked_n<3, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
     default: launch_band_planes_packed_stacked_n<4, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_out, op, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_band_moments_packed_stacked_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N,
+                                        unsigned long long *d_moments, ptrdiff_t out_pitch, jpegx_stream_t stream)
+{
+    if (!d_pixels || !d_moments) return fail(JPEGX_E_INVALID, "null device pointer");
+    if (npictures < 1) return fail(JPEGX_E_INVALID, "band_moments_packed_stacked_n: the picture count must be positive");
+    if (nbands < 1 || nbands > JPEGX_MAX_IMAGE_BANDS) return fail(JPEGX_E_INVALID, "band_moments_packed_stacked_n takes 1..JPEGX_MAX_IMAGE_BANDS bands");
+    if (colour != 0 && colour != 1) return fail(JPEGX_E_INVALID, "band_moments_packed_stacked_n: colour must be 0 (as they are) or 1 (RGB pixels, YCbCr moments)");
+    if (colour == 1 && nbands != 3) return fail(JPEGX_E_INVALID, "band_moments_packed_stacked_n: the colour conversion needs three bands");
+    int H = 0, W = 0;
+    const int rc = jpegx_band_shape_n(rows, cols, bs, N, &H, &W);
+    if (rc) return rc;
+    if ((long long)rows * cols > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one band");
+    if ((long long)H * W > 0x7FFFFFFFLL / nbands / npictures) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 samples in one stack of planes");
+    if ((long long)rows * npictures > INT_MAX) return fail(JPEGX_E_INVALID, "more than 2^31 - 1 rows in one stack of pictures");
+    if (pitch < (ptrdiff_t)cols * nbands || out_pitch < (ptrdiff_t)W) return fail(JPEGX_E_INVALID, "pitch smaller than the row");
+    if (reinterpret_cast<uintptr_t>(d_moments) % 8) return fail(JPEGX_E_INVALID, "band_moments_packed_stacked_n: misaligned output pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ip = (size_t)pitch, op = (size_t)out_pitch;
+    if (colour) launch_band_moments_packed_stacked_n<3, true>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_moments, op, st);
+    else switch (nbands) {
+    case 1: launch_band_moments_packed_stacked_n<1, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_moments, op, st); break;
+    case 2: launch_band_moments_packed_stacked_n<2, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_moments, op, st); break;
+    case 3: launch_band_moments_packed_stacked_n<3, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_moments, op, st); break;
+    default: launch_band_moments_packed_stacked_n<4, false>(d_pixels, ip, npictures, rows, cols, bs, H, W, d_moments, op, st); break;
     }
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;

@@ -468,4 +468,40 @@ int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nba
     return JPEGX_OK;
 }
 
+// ---- the distortion probe over a stack of pictures (jpegx_distort_n.hip): one group of float64 planes and one of moments ------
+size_t jpegx_batch_probe_distortion_pictures_workspace_bytes_n(int npictures, int nbands, int rows, int cols, int bs, int N, int group_planes)
+{
+    Shape s;
+    if (picture_shape("batch_probe_distortion_pictures_n", npictures, nbands, rows, cols, bs, N, 0, group_planes, &s)) return 0;
+    return 2 * up256((size_t)s.gp * s.samples * 8);
+}
+
+int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs,
+                                            int N, int mode, const double *h_params, int K, int group_planes, void *d_workspace,
+                                            unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const char *who = "batch_probe_distortion_pictures_n";
+    if (!d_pixels || !d_workspace || !d_totals)
+        return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_pixels / d_workspace / d_totals: null device pointer");
+    Shape s;
+    int rc = picture_shape(who, npictures, nbands, rows, cols, bs, N, colour, group_planes, &s);
+    if (rc || (rc = jpegx_internal_probe_check_params(who, mode, h_params, K))) return rc;
+    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: pitch smaller than the row");
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_totals) & 7u) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_totals must be 8-byte aligned");
+    double *planes = static_cast<double *>(d_workspace);
+    unsigned long long *moments = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(d_workspace) + up256((size_t)s.gp * s.samples * 8));
+    const int gpics = s.gp / nbands;
+    for (int q0 = 0; q0 < npictures; q0 += gpics) {
+        const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
+        const uint8_t *px = d_pixels + (size_t)q0 * rows * (size_t)pitch;
+        if ((rc = jpegx_band_planes_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, planes, s.W, stream)) ||
+            (rc = jpegx_band_moments_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, moments, s.W, stream)) ||
+            (rc = jpegx_probe_distortion_n(planes, moments, nq * nbands, s.H, s.W, s.W, s.W, N, bs, rows, cols, mode, h_params, K,
+                                           d_totals + (size_t)q0 * nbands * K, stream)))
+            return rc;
+    }
+    return JPEGX_OK;
+}
+
 }  // extern "C"

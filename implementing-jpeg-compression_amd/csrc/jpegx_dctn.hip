@@ -325,6 +325,17 @@ int jpegx_internal_dctn_forward_tables(int N, const double **d_ct, const uint16_
     return JPEGX_OK;
 }
 
+// the cached inverse tables of the current device for the distortion probe (jpegx_distort_n.hip): N checked by the caller
+int jpegx_internal_dctn_inverse_tables(int N, const double **d_cn, const double **d_dinv)
+{
+    DeviceTables t;
+    const int rc = device_tables(N, &t);
+    if (rc) return rc;
+    *d_cn = t.cn;
+    *d_dinv = t.dinv;
+    return JPEGX_OK;
+}
+
 int jpegx_forward_fused_n(const double *d_in, int H, int W, ptrdiff_t pitch, int N, int mode, double param, int32_t *d_out,
                           jpegx_stream_t stream)
 {

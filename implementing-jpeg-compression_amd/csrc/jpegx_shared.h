@@ -42,6 +42,7 @@ int jpegx_internal_decode_phase_n(const uint8_t *d_bytes, size_t nbytes, long lo
                                   int phase, jpegx_stream_t stream);         // one phase of jpegx_entropy_decode_n (microbench/dctn_decode.py)
 int jpegx_internal_decode_verdict_n(unsigned bits);   // jpegx_entropy_decode_n.hip: status word 1 of its workspace -> JPEGX_OK / JPEGX_E_INVALID + message
 int jpegx_internal_dctn_forward_tables(int N, const double **d_ct, const uint16_t **d_zig);   // jpegx_dctn.hip: the current device's cached tables
+int jpegx_internal_dctn_inverse_tables(int N, const double **d_cn, const double **d_dinv);   // jpegx_dctn.hip: the same cache, Cn and Dinv
 // jpegx_probe_n.hip: the checks of jpegx_probe_sizes_n on the quantiser and its K candidates (`who` leads the message), no device touched
 int jpegx_internal_probe_check_params(const char *who, int mode, const double *h_params, int K);
 int jpegx_internal_last_decode_level(void);         // jpegx_decode_ladder.cpp: the scheme that took this thread's last stream (tests)

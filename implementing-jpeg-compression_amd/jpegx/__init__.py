@@ -207,6 +207,10 @@ SIGNATURES = {
     "jpegx_probe_sizes_n": [_vp, _int, _int, _int, _pd, _int, _int, _vp, _int, _vp, _vp],
     "jpegx_batch_probe_pictures_workspace_bytes_n": [_int, _int, _int, _int, _int, _int, _int],
     "jpegx_batch_probe_pictures_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
+    "jpegx_band_moments_packed_stacked_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _vp, _pd, _vp],
+    "jpegx_probe_distortion_n": [_vp, _vp, _int, _int, _int, _pd, _pd, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp],
+    "jpegx_batch_probe_distortion_pictures_workspace_bytes_n": [_int, _int, _int, _int, _int, _int, _int],
+    "jpegx_batch_probe_distortion_pictures_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
     "jpegx_picture_planes_stacked_u8": [_vp, _int, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
     "jpegx_batch_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
     "jpegx_batch_compress_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
@@ -270,7 +274,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_batch_emit_set_n", "jpegx_batch_decompress_picture_set_n", "jpegx_picture_set_blocks_u8",
               "jpegx_batch_compress_picture_set", "jpegx_batch_compress_status_set", "jpegx_batch_emit_set",
               "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n",
-              "jpegx_probe_sizes_set_n", "jpegx_batch_probe_picture_set_n"):
+              "jpegx_probe_sizes_set_n", "jpegx_batch_probe_picture_set_n", "jpegx_band_moments_packed_stacked_n",
+              "jpegx_probe_distortion_n", "jpegx_batch_probe_distortion_pictures_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -282,6 +287,7 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_decompress_set_workspace_bytes_n": _sz, "jpegx_batch_set_workspace_bytes": _sz,
             "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz,
             "jpegx_batch_probe_pictures_workspace_bytes_n": _sz,
+            "jpegx_batch_probe_distortion_pictures_workspace_bytes_n": _sz,
             "jpegx_batch_probe_picture_set_workspace_bytes_n": _sz}   # everything else returns int
 
 
@@ -2006,6 +2012,82 @@ def batch_probe_pictures_n(pixels, bs, n, mode, params, colour=None, group_plane
         din, dws, dtot = dev(src.nbytes), dev(nws), dev(k * nb * nk * 8)
         din.upload(src)
         batch_probe_pictures_n_device(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
+        raw = dtot.download((k, nb, nk), np.uint64)
+    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
+
+
+# ---------------------------------------------------------------------------------------------
+# the distortion probe: what every decoded band would lose (sum of squared differences over its pixels) under each of K
+# candidate quantiser parameters, in one pass over the planes (csrc/jpegx_distort_n.hip) -- no coefficient stream, no decoded
+# plane, no per-candidate round trip.  dct_size 2..32 through the run-time-N kernels, stacks of pictures of one size.
+# ---------------------------------------------------------------------------------------------
+def band_moments_packed_stacked_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, d_moments, colour=0, pitch=None, out_pitch=None,
+                                         stream=None, device=None):
+    """Enqueue jpegx_band_moments_packed_stacked_n: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands)
+    -> uint64 words stacked picture-major [npictures * nbands * H][out_pitch] (default W), S2 << 32 | S1 of every sample's live
+    pixels; colour 0 or 1 as in the header."""
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), int(n), d_moments, int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
+    L = lib()
+    check(L.jpegx_band_moments_packed_stacked_n(*args) if device is None else L.jpegx_band_moments_packed_stacked_n_on(int(device), *args),
+          "jpegx_band_moments_packed_stacked_n")
+
+
+def probe_distortion_n_device(d_planes, d_moments, nplanes, height, width, n, bs, rows, cols, mode, params, d_totals, pitch=None, mpitch=None,
+                              stream=None, device=None):
+    """Enqueue jpegx_probe_distortion_n: nplanes float64 planes stacked [nplanes * height][pitch] and their moments
+    [nplanes * height][mpitch] (elements, default width), every plane a rows x cols band pooled bs x bs -> uint64 d_totals
+    [nplanes][K]: bits 0..62 the sum of squared differences of the band under candidate q, bit 63 the bad-amplitude flag."""
+    h, k = _probe_params(params)
+    args = (d_planes, d_moments, int(nplanes), int(height), int(width), int(width if pitch is None else pitch),
+            int(width if mpitch is None else mpitch), int(n), int(bs), int(rows), int(cols), mode_of(mode), h.ctypes.data, k, d_totals, stream)
+    L = lib()
+    check(L.jpegx_probe_distortion_n(*args) if device is None else L.jpegx_probe_distortion_n_on(int(device), *args), "jpegx_probe_distortion_n")
+
+
+def batch_probe_distortion_pictures_workspace_bytes_n(npictures, nbands, rows, cols, bs, n, group_planes):
+    return lib().jpegx_batch_probe_distortion_pictures_workspace_bytes_n(int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n),
+                                                                         int(group_planes))
+
+
+def batch_probe_distortion_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, mode, params, group_planes, d_workspace, d_totals,
+                                             colour=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_probe_distortion_pictures_n: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands)
+    -> uint64 d_totals [nbands * npictures][K], plane-major in the batch's picture-major plane order."""
+    h, k = _probe_params(params)
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), int(n), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
+    L = lib()
+    check(L.jpegx_batch_probe_distortion_pictures_n(*args) if device is None
+          else L.jpegx_batch_probe_distortion_pictures_n_on(int(device), *args), "jpegx_batch_probe_distortion_pictures_n")
+
+
+def batch_probe_distortion_pictures_n(pixels, bs, n, mode, params, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> (sse, bad): sse uint64 [k][nb][K], the sum of squared differences between band b of
+    picture p and what batch_decompress_pictures_n gives back of batch_compress_pictures_n's bytes under candidate q (with
+    colour='rgb': in the coded YCbCr bands); bad bool [k][nb][K], True where that band holds an amplitude beyond 15 bits under
+    that candidate (it cannot be coded; its sum is then meaningless).  Host convenience: upload, probe, one download.
+    group_planes None: the recommended value."""
+    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    k, rows, cols, nb = src.shape
+    flag = _colour_flag(colour, nb, "batch_probe_distortion_pictures_n")
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, n) or nb
+    h, nk = _probe_params(params)
+    pics = (k, nb, rows, cols, int(bs), int(n))
+    nws = batch_probe_distortion_pictures_workspace_bytes_n(*pics, group_planes)
+    if nws == 0 or not 1 <= nk <= PROBE_MAX_CANDIDATES:     # the entry names the refusal, before any device is touched
+        batch_probe_distortion_pictures_n_device(1, *pics, mode, h, group_planes, 16, 8, flag)
+        raise JpegxError("batch_probe_distortion_pictures_n: the batch was refused")
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dtot = dev(src.nbytes), dev(nws), dev(k * nb * nk * 8)
+        din.upload(src)
+        batch_probe_distortion_pictures_n_device(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
         raw = dtot.download((k, nb, nk), np.uint64)
     return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
 

@@ -1736,6 +1736,207 @@ def compress_pictures_to_size(images, config, max_bytes, divisors, colour=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# what a divisor costs in quality, and compressing to a PSNR floor
+# ---------------------------------------------------------------------------------------------------------------------
+# probe_picture_distortion takes the device road (jpegx.batch_probe_distortion_pictures_n: one upload, two gathers and one pass
+# of the distortion kernel per group of pictures, every candidate divisor quantised, restored, inverted and compared from the
+# coefficients in LDS, one download of the sums) from this many divisors on; None: the road is off and the function is the
+# loop over Jpeg.compress and Jpeg.decompress.  Read when the function is called.  Never below 1.
+# Measured (profiles/probe_distortion_n.json and, a second run of the same code, _run2.json; 1 and 8 pictures
+# of 64 x 64 and 512 x 512 at N 4 and N 16, the probe against the loop alternating call by call on one MI355X): the probe won
+# every comparison of both runs, with ONE divisor already (0.12-0.13 against 0.59-0.61 ms on one 64 x 64 picture, 0.74-0.82
+# against 5.7-6.0 ms on one 512 x 512 picture, 2.5-2.6 against 38-40 ms on eight: 4.7-28x), with 2 by 9-49x, with 16 by 52-310x:
+# the loop pays a compression, a decompression and a NumPy comparison per divisor.  On device buffers, against K bare
+# forward-plus-inverse kernel pairs without gather, way back or comparison (a lower bound no caller of pipeline has), one
+# candidate loses (0.39-0.78x) and the probe wins from 2 on at block_size 1 (1.04-1.22x; 2.0-2.7x at 32) and from 4-16 on at bs
+# 5 N 24.  The smallest measured count with no loss against the loop at or above it; no plane size lost at any count, so there
+# is no size gate beyond DCTN_MIN_SAMPLES.
+DCTN_DISTORTION_MIN_CANDIDATES = 1
+
+
+class TargetQualityError(ValueError):
+    """No candidate divisor keeps the picture at or above the PSNR floor."""
+
+
+def _distortion_loop(images, config, divisors, colour):
+    """The literal loop: per band the squared differences between the picture as the codec is handed it and
+    Jpeg(config_j).decompress(Jpeg(config_j).compress(picture)), -1 where compressing raises the reference's BadRleCodeError."""
+    import util
+    images = _as_images(images, colour)
+    out = np.empty((len(images), 3, len(divisors)), dtype=np.int64)
+    for i, im in enumerate(images):
+        x = im if colour is None else im.convert("YCbCr")
+        ref = np.asarray(x).astype(np.int64)
+        for j, d in enumerate(divisors):
+            codec = Jpeg(_divide_config(config, d))
+            try:
+                back = np.asarray(codec.decompress(codec.compress(x))).astype(np.int64)
+            except util.BadRleCodeError:
+                out[i, :, j] = -1
+                continue
+            out[i, :, j] = ((back - ref) ** 2).sum(axis=(0, 1))
+    return out
+
+
+def _distortion_device(images, config, divisors, colour):
+    """The sums from jpegx.batch_probe_distortion_pictures_n, or None: the gate, the configuration or the pictures do not admit
+    the road, or libjpegx refused or failed."""
+    gate = DCTN_DISTORTION_MIN_CANDIDATES
+    count = len(images)
+    if gate is None or len(divisors) < max(gate, 1) or count < 1 or not _stock_registry():
+        return None
+    sizes = _job_sizes(config)                           # transform 'DCT', dct_size 2..32 but 8, a usable device
+    rows, cols = config.height, config.width
+    if sizes is None or not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
+            or rows * cols > 2 ** 31 - 1:
+        return None
+    bs, n = sizes
+    h, w = _blocked_shape(rows, cols, bs, n)
+    if not dctn_on_device(config, h * w) or 3 * count * h * w > 2 ** 31 - 1:
+        return None
+    stack = _stacked_pixels(images, config, colour)
+    if stack is None:
+        return None
+    import jpegx
+    out = np.empty((count, 3, len(divisors)), dtype=np.int64)
+    for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
+        some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
+        got = _none_on_refusal(jpegx.batch_probe_distortion_pictures_n, stack, bs, n, "divide", [float(d) for d in some], **_colour_kw(colour))
+        if got is None:
+            return None
+        sse, bad = got
+        part = np.asarray(sse).astype(np.int64)
+        # Jpeg.compress raises for the whole picture when any band does
+        part[np.broadcast_to(np.asarray(bad).any(axis=1, keepdims=True), part.shape)] = -1
+        out[:, :, at:at + len(some)] = part
+    return out
+
+
+def probe_picture_distortion(images, config, divisors, colour=None):
+    """int64 [len(images)][3][len(divisors)]: entry [i][b][j] is the sum over the picture's pixels of
+    (band b of Jpeg(config_j).decompress(Jpeg(config_j).compress(x_i)) - band b of x_i) ** 2, where config_j is ``config`` with
+    QuantizationMethod('divide', divisor=divisors[j]) and x_i is picture i as the codec is handed it -- with colour='rgb' that
+    is images[i].convert('YCbCr'): the error is measured in the coded bands, where compress_rgb equals compress of the converted
+    picture.  -1 (in all three bands) where compressing raises BadRleCodeError.  ``images`` as compress_pictures takes them.
+    ValueError for a configuration that is not 'divide' and for a divisor that is not a whole positive number.
+    With at least DCTN_DISTORTION_MIN_CANDIDATES divisors, dct_size other than 8 with transform 'DCT', the stock steps, a usable
+    device, pictures that _stacked_pixels accepts and planes of at least DCTN_MIN_SAMPLES samples, all divisors are measured on
+    the device in one pass per 32 of them (jpegx.batch_probe_distortion_pictures_n); everything else, and every refusal, is the
+    loop."""
+    _check_colour(colour)
+    divisors = _checked_divisors(config, divisors)
+    if not isinstance(images, np.ndarray):
+        images = list(images)
+    sse = _distortion_device(images, config, divisors, colour) if len(divisors) else None
+    return sse if sse is not None else _distortion_loop(images, config, divisors, colour)
+
+
+def _psnr_of(sse, rows, cols):
+    """float64 [pictures][K] from int64 sums [pictures][bands][K]: 10 log10(255^2 * bands * rows * cols / sum over the bands); inf at
+    zero error, nan where an entry is -1."""
+    sse = np.asarray(sse)
+    total = sse.sum(axis=1).astype(np.float64)
+    peak = 255.0 ** 2 * sse.shape[1] * rows * cols
+    with np.errstate(divide="ignore", invalid="ignore"):
+        psnr = np.where(total > 0, 10.0 * np.log10(peak / np.where(total > 0, total, 1.0)), np.inf)
+    psnr[(sse < 0).any(axis=1)] = np.nan
+    return psnr
+
+
+def probe_picture_psnr(images, config, divisors, colour=None):
+    """float64 [len(images)][len(divisors)]: the PSNR of every picture under every divisor over its three coded bands,
+    10 * log10(255^2 * 3 * rows * cols / sum over the bands of probe_picture_distortion); inf where nothing is lost, nan where
+    the picture cannot be coded (an entry of -1)."""
+    return _psnr_of(probe_picture_distortion(images, config, divisors, colour), config.height, config.width)
+
+
+def _meets(psnr, min_psnr):
+    return not np.isnan(psnr) and psnr >= min_psnr
+
+
+def compress_to_quality(image, config, min_psnr, colour=None, lo=1, hi=4096, probes=16, rounds=3):
+    """(container, divisor, psnr): ``image`` compressed under ``config`` with the largest 'divide' divisor the search below finds
+    whose PSNR (probe_picture_psnr) is at least ``min_psnr`` dB; the container is Jpeg(config_divisor).compress(image)
+    (compress_rgb with colour='rgb').  compress_to_size's search mirrored; it is deterministic and costs 1 + ``rounds`` calls of
+    probe_picture_psnr at most:
+      1. candidates: ``probes`` whole numbers spaced geometrically from ``lo`` to ``hi`` inclusive;
+      2. f = the LARGEST candidate whose PSNR is not nan (BadRleCodeError) and at least min_psnr -- none: TargetQualityError;
+         g = the candidate just above f, or hi + 1;
+      3. while rounds remain and whole numbers lie strictly between f and g: up to ``probes`` of them, evenly spaced, are
+         probed; f becomes the largest of them that meets the floor (it stays if none does), g the probed number just above
+         the new f (the old g if there is none);
+      4. ONE compression, with f.
+    PSNR need not fall monotonically with the divisor: f is the largest number MEETING the floor that the search has seen below
+    a number that misses it, not a global maximum."""
+    _check_colour(colour)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lo, hi, probes, rounds)) \
+            or lo < 1 or hi < lo or probes < 1 or rounds < 0:
+        raise ValueError("compress_to_quality: lo, hi, probes and rounds must be whole numbers with 1 <= lo <= hi, probes >= 1, rounds >= 0")
+    if isinstance(min_psnr, bool) or not isinstance(min_psnr, (int, float, np.integer, np.floating)) or np.isnan(min_psnr):
+        raise ValueError("compress_to_quality: min_psnr must be a number of decibels, got %r" % (min_psnr,))
+    lo, hi, probes, rounds = int(lo), int(hi), int(probes), int(rounds)
+    seen = {}                                            # divisor -> probed PSNR
+
+    def probe(candidates):
+        psnr = probe_picture_psnr([image], config, candidates, colour)[0]
+        seen.update((d, float(p)) for d, p in zip(candidates, psnr))
+
+    candidates = _geometric(lo, hi, probes)
+    probe(candidates)
+    meeting = [d for d in candidates if _meets(seen[d], min_psnr)]
+    if not meeting:
+        coded = [(p, -d) for d, p in seen.items() if not np.isnan(p)]
+        if not coded:
+            raise TargetQualityError("no divisor in %d..%d codes the picture at all (BadRleCodeError at every candidate)" % (lo, hi))
+        best, at = max(coded)
+        raise TargetQualityError("no divisor in %d..%d keeps the picture at %.2f dB or above: the best PSNR seen is %.2f dB, at divisor %d"
+                                 % (lo, hi, min_psnr, best, -at))
+    f = meeting[-1]
+    g = min([d for d in candidates if d > f], default=hi + 1)
+    for _ in range(rounds):
+        inner = _between(f, g, probes)
+        if not inner:
+            break
+        probe(inner)
+        meeting = [d for d in inner if _meets(seen[d], min_psnr)]
+        if meeting:
+            f = meeting[-1]
+        g = min([d for d in inner if d > f], default=g)
+    return _compress_one(image, _divide_config(config, f), colour), f, seen[f]
+
+
+def compress_pictures_to_quality(images, config, min_psnr, divisors, colour=None):
+    """(containers, chosen): every picture compressed with the largest divisor of the ascending ladder ``divisors`` (at most 32
+    rungs) that keeps its PSNR at ``min_psnr`` dB or above; chosen[i] is picture i's divisor and containers[i] equals
+    Jpeg(config_chosen[i]).compress(images[i]) (compress_rgb with colour='rgb'), byte for byte, in input order.  ONE
+    probe_picture_psnr call measures the whole batch on every rung; the pictures of a rung are then one compress_pictures call.
+    TargetQualityError names the first picture that meets the floor on no rung."""
+    _check_colour(colour)
+    ladder = _checked_divisors(config, divisors)
+    if not 1 <= len(ladder) <= 32 or any(b <= a for a, b in zip(ladder, ladder[1:])):
+        raise ValueError("compress_pictures_to_quality: divisors must be 1..32 ascending rungs")
+    if not isinstance(images, np.ndarray):
+        images = list(images)
+    psnr = probe_picture_psnr(images, config, ladder, colour)
+    rung = []
+    for i, row in enumerate(psnr):
+        meeting = [j for j, p in enumerate(row) if _meets(p, min_psnr)]
+        if not meeting:
+            coded = [(float(p), -ladder[j]) for j, p in enumerate(row) if not np.isnan(p)]
+            raise TargetQualityError("picture %d meets %.2f dB on no rung%s" % (
+                i, min_psnr, ": its best PSNR is %.2f dB, at divisor %d" % (max(coded)[0], -max(coded)[1]) if coded
+                else " (BadRleCodeError at every rung)"))
+        rung.append(meeting[-1])
+    containers = [None] * len(rung)
+    for j in sorted(set(rung)):
+        members = [i for i, r in enumerate(rung) if r == j]
+        group = images[members] if isinstance(images, np.ndarray) else [images[i] for i in members]
+        for i, c in zip(members, compress_pictures(group, _divide_config(config, ladder[j]), colour)):
+            containers[i] = c
+    return containers, [ladder[j] for j in rung]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the same for a SET of pictures of unequal sizes, each under the configuration at its own size (compress_picture_set)
 # ---------------------------------------------------------------------------------------------------------------------
 # probe_picture_set_sizes takes the device road (jpegx.batch_probe_picture_set_n: one flat upload, per group of pictures one

@@ -655,6 +655,47 @@ int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nba
                                  int colour, int bs, int N, int mode, const double *h_params, int K, int group_planes,
                                  void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
 
+/* ---- distortion probe: what the decoded bands would lose under each of K candidate quantiser parameters, in one pass
+ * (csrc/jpegx_distort_n.hip; dct_size 2..32 through the run-time-N kernels; stacks of pictures of one size) ---------------------
+ * For every plane p and candidate q: the sum over the band's rows x cols pixels of (pixel - decoded pixel)^2, the decoded band
+ * being what the reference's way back leaves after Quantization with candidate q (pipeline/quantization.py,
+ * quantizers.py:23-31) -- the restored coefficients through BasisChange.invert, rounded and clamped to 0..255 (the
+ * Normalization.invert clamp), then DCTPadding.invert (pipeline/dct_padding.py:11-21), SubSampling.invert
+ * (pipeline/subsampling.py:13-14, every sample bs x bs times) and Padding.invert (pipeline/padding.py:14-16).  It is the number
+ * that jpegx_forward_fused_n, jpegx_inverse_fused_n with JPEGX_F_CLAMP_U8, jpegx_inflate_crop_stacked_u8 and a comparison with
+ * the band give when they are run once per candidate, from the SAME integers: the kernel keeps the forward kernel's float64
+ * coefficients in LDS, quantises them K times with the forward kernel's functions and repeats the inverse kernel's arithmetic.
+ * A decoded sample s stands for the cnt pixels of its bs x bs tile inside rows x cols, over which
+ * sum (v - s)^2 = S2 - 2 s S1 + cnt s^2; the moments S1 = sum v and S2 = sum v^2 come from the gather below.
+ * jpegx_band_moments_packed_stacked_n (enqueue only): arguments, limits and refusals of jpegx_band_planes_packed_stacked_n;
+ * d_moments [npictures * nbands * H][out_pitch] 64-bit words in the same plane order, 8-byte aligned, word (y, x) of plane
+ * (p, k) = S2 << 32 | S1 over the pixels [y * bs, min((y + 1) * bs, rows)) x [x * bs, min((x + 1) * bs, cols)) of band k of
+ * picture p (bs <= 255: S1 < 2^24, S2 < 2^32), 0 where that range is empty (either padding).  With colour = 1 the values are
+ * Pillow's YCbCr of the RGB pixels, as in the planes' gather.  Only those pixels are read: no read leaves its picture.
+ * jpegx_probe_distortion_n (enqueue only: one memset of d_totals, one kernel): d_planes as jpegx_probe_sizes_n takes them,
+ * d_moments [nplanes * H][mpitch] their moments; bs, rows, cols the band behind every plane.  d_totals [nplanes][K], 8-byte
+ * aligned: bits 0..62 the sum of squared differences; bit 63 = an amplitude beyond 15 bits (|a| > 16383) in plane p under
+ * candidate q, which the coded road refuses (BadRleCodeError) -- the low bits are then unspecified.  Modes, candidates and
+ * their checks as jpegx_probe_sizes_n.  Also refused before any device work (JPEGX_E_INVALID, the message names the
+ * argument): bs outside 1..255, rows and cols that do not give H and W by jpegx_band_shape_n, mpitch < W, a pointer that is
+ * not 8-byte aligned.
+ * jpegx_batch_probe_distortion_pictures_n (enqueue only): jpegx_batch_probe_pictures_n's groups, limits and refusals; per group
+ * the two gathers into the workspace and the probe into the group's rows of d_totals [nbands * npictures][K].  The workspace
+ * (16-byte aligned) is one group of float64 planes and one of moments: 2 * up256(min(group_planes, nbands * npictures) * H *
+ * W * 8) bytes; jpegx_batch_probe_distortion_pictures_workspace_bytes_n returns 0 for a shape the entry refuses.          */
+int jpegx_band_moments_packed_stacked_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                                        int colour, int bs, int N, unsigned long long *d_moments, ptrdiff_t out_pitch,
+                                        jpegx_stream_t stream);
+int jpegx_probe_distortion_n(const double *d_planes, const unsigned long long *d_moments, int nplanes, int H, int W,
+                             ptrdiff_t pitch, ptrdiff_t mpitch, int N, int bs, int rows, int cols, int mode,
+                             const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+size_t jpegx_batch_probe_distortion_pictures_workspace_bytes_n(int npictures, int nbands, int rows, int cols, int bs, int N,
+                                                               int group_planes);
+int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                            ptrdiff_t pitch, int colour, int bs, int N, int mode, const double *h_params, int K,
+                                            int group_planes, void *d_workspace, unsigned long long *d_totals,
+                                            jpegx_stream_t stream);
+
 /* ---- batch codec for a SET of pictures of UNEQUAL sizes at any DCT size but 8 (csrc/jpegx_batch_set_n.cpp,
  * csrc/jpegx_band_set_n.hip) ----------------------------------------------------------------------------------------------
  * Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124; with colour = 1 behind compress.py:9 and in
@@ -1322,6 +1363,16 @@ int jpegx_probe_sizes_set_n_on(int device, const double *d_strip, const void *h_
 int jpegx_batch_probe_picture_set_n_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table,
                                        int colour, int mode, const double *h_params, int K, long long group_samples,
                                        void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_band_moments_packed_stacked_n_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                           ptrdiff_t pitch, int colour, int bs, int N, unsigned long long *d_moments,
+                                           ptrdiff_t out_pitch, jpegx_stream_t stream);
+int jpegx_probe_distortion_n_on(int device, const double *d_planes, const unsigned long long *d_moments, int nplanes, int H,
+                                int W, ptrdiff_t pitch, ptrdiff_t mpitch, int N, int bs, int rows, int cols, int mode,
+                                const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_distortion_pictures_n_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows,
+                                               int cols, ptrdiff_t pitch, int colour, int bs, int N, int mode,
+                                               const double *h_params, int K, int group_planes, void *d_workspace,
+                                               unsigned long long *d_totals, jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
