@@ -9,22 +9,16 @@
 // plane, so the forward kernels, the scan and the emitter run once over nplanes * (H/8) * (W/8) blocks; what a batch adds
 // is the plane index (k_plane_index, jpegx_entropy.hip) and, on the way back, the cut into groups of whole planes that
 // one decode call can take.  Nothing is allocated here except the whole-stream decoder's scratch (level 2 of the
-// ladder), which is sized from a count read back from the device and therefore cannot be the caller's.
-#include <limits.h>
-#include <math.h>
-
+// ladder), which is sized from a count read back from the device and therefore cannot be the caller's.  What this file
+// shares with the other batch files -- limits, checks, the reader of a compress's verdict -- is jpegx_batch_common.h.
 #include <mutex>
 
+#include "jpegx_batch_common.h"
 #include "jpegx_entropy_decode.h"
-#include "jpegx_shared.h"
 
 namespace {
 
-constexpr unsigned long long SIZES_ONLY = ~0ull;       // the capacity noted by a compress without destination
 constexpr long long MAX_BLOCKS = 0x7FFFFFC0LL;
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // shape of a batch: false (message set) when it is not one
 int check_batch_shape(int nplanes, int H, int W, long long *nb)
@@ -68,7 +62,6 @@ int enqueue_index_and_emit(const CompressWs &c, int nplanes, long long nb, uint8
 // level, and the int16 stream of a group has to sit somewhere.  So a group is a run of whole planes of at most
 // GROUP_BLOCKS blocks and GROUP_BYTES bytes (one plane where a single plane is more than that).
 constexpr long long GROUP_BLOCKS = 1ll << 20;          // 128 MiB of int16 stream
-constexpr size_t GROUP_BYTES = (size_t)64 << 20;
 
 struct GroupLimits {
     int planes;          // planes per group at most
@@ -81,9 +74,9 @@ GroupLimits group_limits(int nplanes, long long nb)
     long long k = GROUP_BLOCKS / nb;
     if (k < 1) k = 1;
     g.planes = k > nplanes ? nplanes : (int)k;
-    const unsigned long long worst = 185ull * (unsigned long long)nb;
+    const unsigned long long worst = MAX_BLOCK_BYTES_8 * (unsigned long long)nb;
     unsigned long long b = worst > GROUP_BYTES ? worst : GROUP_BYTES;
-    if (b > 0xFFFFFFEFull) b = 0xFFFFFFEFull;          // one decode call: below 4 GiB
+    if (b > MAX_STREAM_8) b = MAX_STREAM_8;             // one decode call: below 4 GiB
     g.bytes = (size_t)b;
     return g;
 }
@@ -252,23 +245,7 @@ int jpegx_batch_compress_status(const void *d_workspace, int nplanes, int H, int
     int rc = check_batch_shape(nplanes, H, W, &nb);
     if (rc) return rc;
     const CompressWs c = carve_compress(const_cast<void *>(d_workspace), nplanes, nb * nplanes);
-    unsigned long long ehead[2] = {0, 0}, bhead[2] = {0, 0};
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(ehead, c.ews, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bhead, c.index, 16, hipMemcpyDeviceToHost, st));
-    if (h_plane_offsets)
-        HIP_TRY(hipMemcpyAsync(h_plane_offsets, static_cast<const unsigned char *>(c.index) + 16, ((size_t)nplanes + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *h_total = ehead[0];
-    if ((unsigned)(ehead[1] & 0xFFFFFFFFull) != 0)
-        return fail(JPEGX_E_INVALID, "BadRleCodeError: an amplitude needs more than 15 bits (|a| > 16383); nothing was written");
-    if (bhead[0] != SIZES_ONLY && ehead[0] > bhead[0]) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "batch: the coded stream needs %llu bytes, the buffer holds %llu; nothing was written", ehead[0], bhead[0]);
-        jpegx_internal_set_error(buf);
-        return 1;
-    }
-    return JPEGX_OK;
+    return read_compress_status(c.ews, c.index, (size_t)nplanes, "batch", h_total, h_plane_offsets, stream);
 }
 
 size_t jpegx_batch_decompress_workspace_bytes(size_t nbytes, int nplanes, int H, int W)
@@ -297,14 +274,7 @@ int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_p
         return fail(JPEGX_E_INVALID, "batch_decompress: output pitch must be >= W * bs and keep rows 16-byte (uint8 with block_size other than 2, 4: 8-byte) aligned");
     if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_workspace) & 255u) != 0)
         return fail(JPEGX_E_INVALID, "batch_decompress: output must be 16-byte, workspace 256-byte aligned");
-    for (int p = 0; p < nplanes; ++p) {
-        if (h_plane_offsets[p + 1] < h_plane_offsets[p]) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "batch_decompress: plane offsets must not decrease (plane %d starts at %llu, plane %d at %llu)", p, h_plane_offsets[p],
-                     p + 1, h_plane_offsets[p + 1]);
-            return fail(JPEGX_E_INVALID, buf);
-        }
-    }
+    if ((rc = check_offsets("batch_decompress", h_plane_offsets, nplanes))) return rc;
     const GroupLimits lim = group_limits(nplanes, nb);
     WorkspaceLadder lad;
     lad.w = carve_decompress(d_workspace, (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]), nplanes, nb);
@@ -386,10 +356,8 @@ int picture_shape(const char *who, int npictures, int nbands, int rows, int cols
         snprintf(buf, sizeof(buf), "%s takes 1..JPEGX_MAX_IMAGE_BANDS bands", who);
         return fail(JPEGX_E_INVALID, buf);
     }
-    if ((colour != 0 && colour != 1) || (colour == 1 && nbands != 3)) {
-        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
+    int rc = check_colour(who, nbands, colour);
+    if (rc) return rc;
     if (group_planes <= 0 || group_planes % nbands) {
         snprintf(buf, sizeof(buf), "%s: group_planes must be a positive multiple of the band count (jpegx_batch_group_planes_pictures_n)", who);
         return fail(JPEGX_E_INVALID, buf);
@@ -402,8 +370,7 @@ int picture_shape(const char *who, int npictures, int nbands, int rows, int cols
         snprintf(buf, sizeof(buf), "%s: block_size must be in 1..255", who);
         return fail(JPEGX_E_UNSUPPORTED, buf);
     }
-    int rc = jpegx_padded_shape(rows, cols, bs, &s->H, &s->W);
-    if (rc) return rc;
+    if ((rc = jpegx_padded_shape(rows, cols, bs, &s->H, &s->W))) return rc;
     if (npictures > INT_MAX / nbands) return fail(JPEGX_E_INVALID, "batch: more than 2^31 - 64 blocks in one batch");
     s->nplanes = npictures * nbands;
     if ((rc = check_batch_shape(s->nplanes, s->H, s->W, &s->nb))) return rc;
@@ -422,28 +389,6 @@ int picture_shape(const char *who, int npictures, int nbands, int rows, int cols
         return fail(JPEGX_E_INVALID, buf);
     }
     return JPEGX_OK;
-}
-
-// what the forward kernels refuse (fill_forward_params, jpegx_internal.h; forward_u8_common, jpegx_forward.hip), with their
-// codes, before anything is launched.  The divisor's limit is the uint8 kernels' (they pack without saturating); it holds on
-// both roads, so that a quantiser is taken or refused whatever the pictures' shape.
-int check_forward_quantiser(int mode, double param)
-{
-    switch (mode) {
-    case JPEGX_Q_NONE:
-    case JPEGX_Q_QTABLE:
-        return JPEGX_OK;
-    case JPEGX_Q_DISCARD:
-        if (!(param >= 0.0) || param != (double)(int)param) return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
-        return JPEGX_OK;
-    case JPEGX_Q_DIVIDE:
-        if (!(param != 0.0) || !(fabs(param) <= 1e30)) return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
-        if (fabsf((float)(1.0 / param)) > 2.0f)
-            return fail(JPEGX_E_UNSUPPORTED, "forward_u8: a divisor below 0.5 can overflow int16; use the fp32 entry (it saturates)");
-        return JPEGX_OK;
-    default:
-        return fail(JPEGX_E_INVALID, "unknown quantiser mode");
-    }
 }
 
 // behind carve_compress's pieces: the padded raw planes of the whole stack (uint8 road) or the float64 planes of one group
@@ -484,15 +429,12 @@ int jpegx_batch_compress_pictures(const uint8_t *d_pixels, int npictures, int nb
             return rc;
     } else {
         double *planes = reinterpret_cast<double *>(front);
-        const int gpics = s.gp / nbands;
-        for (int q0 = 0; q0 < npictures; q0 += gpics) {
-            const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
-            if ((rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, 8, planes,
-                                                         s.W, stream)) ||
-                (rc = jpegx_forward_fused_f64(planes, nq * nbands * s.H, s.W, s.W, mode, param, 0, c.zz + (size_t)q0 * nbands * (size_t)s.nb * 64, stream)))
-                return rc;
-        }
-        if ((rc = jpegx_internal_entropy_sizes_half(c.zz, nblocks, c.ews, stream))) return rc;
+        rc = for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
+            const int rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, 8,
+                                                              planes, s.W, stream);
+            return rc ? rc : jpegx_forward_fused_f64(planes, nq * nbands * s.H, s.W, s.W, mode, param, 0, c.zz + (size_t)q0 * nbands * (size_t)s.nb * 64, stream);
+        });
+        if (rc || (rc = jpegx_internal_entropy_sizes_half(c.zz, nblocks, c.ews, stream))) return rc;
     }
     if ((rc = jpegx_internal_entropy_scan(nblocks, c.ews, stream))) return rc;
     return enqueue_index_and_emit(c, s.nplanes, s.nb, d_out, out_cap, stream);

@@ -17,23 +17,11 @@
 // conversions of compress.py:9 and decompress.py:9-10 around them) is the same batch of nbands * npictures planes in
 // picture-major order: the _pictures_ entries differ in the gather and the scatter (jpegx_band_planes_packed_stacked_n,
 // jpegx_inflate_crop_pack_stacked_u8), in groups that are whole pictures, and in a staging area for a lone picture's worst
-// case; shape, workspace, status, emit and the cut itself are the band entries' code.
-#include <limits.h>
-
-#include <vector>
-
-#include "jpegx_shared.h"
+// case; shape, workspace, status, emit, the cut itself and both group walks (compress_stack, decompress_stack) are the band
+// entries' code.  What the set entries run as well -- checks, the verdict's reader, the decode walk -- is jpegx_batch_common.h.
+#include "jpegx_batch_common.h"
 
 namespace {
-
-constexpr unsigned long long SIZES_ONLY = ~0ull;       // the capacity noted by a compress without destination
-constexpr long long GROUP_SAMPLES = 1ll << 26;         // group_planes 0: the planes within this many samples H * W
-constexpr unsigned long long GROUP_BYTES = 64ull << 20;      // a group's stream at most (a lone plane may pass it)
-constexpr unsigned long long MAX_STREAM = 0xFFFFF000ull;     // jpegx_entropy_decode_n takes streams BELOW 2^32 - 4096 bytes
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-unsigned long long max_block_bytes(int N) { return (23ull * N * N + 15ull) / 8ull; }      // jpegx_entropy_n.hip: 23 bits per coefficient + the end byte
 
 struct Shape {
     int H, W;            // the plane that leaves step 3 (jpegx_band_shape_n)
@@ -57,17 +45,6 @@ int batch_shape(int nplanes, int rows, int cols, int bs, int N, int group_planes
     long long k = group_planes > 0 ? group_planes : GROUP_SAMPLES / s->samples;
     if (k < 1) k = 1;
     s->gp = k > nplanes ? nplanes : (int)k;              // gp * H * W <= nplanes * H * W <= 2^31 - 1
-    return JPEGX_OK;
-}
-
-int check_quantiser(int mode, double param)
-{
-    if (mode == JPEGX_Q_QTABLE) return fail(JPEGX_E_INVALID, "qtable: the luminance table is 8 x 8, it needs dct_size 8 (BadQuantizationError)");
-    if (mode != JPEGX_Q_NONE && mode != JPEGX_Q_DISCARD && mode != JPEGX_Q_DIVIDE) return fail(JPEGX_E_INVALID, "unknown quantiser mode");
-    if (mode == JPEGX_Q_DISCARD && (!(param >= 0.0) || !(param <= 1e9) || param != (double)(int)param))
-        return fail(JPEGX_E_INVALID, "discard: keep must be a non-negative integer");
-    if (mode == JPEGX_Q_DIVIDE && (!(param != 0.0) || !(param >= -1e30 && param <= 1e30)))
-        return fail(JPEGX_E_INVALID, "divide: divisor must be finite and non-zero");
     return JPEGX_OK;
 }
 
@@ -100,66 +77,60 @@ int enqueue_index_and_emit(const CompressWs &c, int nplanes, int N, const Shape 
     return jpegx_internal_entropy_emit_n_guarded(c.zz, s.nb * nplanes, N * N, c.ews, d_out, out_cap, stream);
 }
 
-// ---- decompress: [int32 stream of one group][the group's bytes][decoder workspace][the group's clamped tall plane] -----
-struct DecompressWs {
-    int32_t *zz;
-    uint8_t *stage;      // the group's bytes: dword aligned, 16 zero bytes behind them
-    void *dws;
-    uint8_t *plane;
-    size_t bytes;
-};
-
-// the longest stream one group can hold, given the whole stream's length; a group holds at least one unit of `unit` planes
-// (a band: 1, a picture: its bands)
-unsigned long long group_bytes_max(size_t nbytes, int N, const Shape &s, int unit)
+// The compress road of a stack of units of `unit` planes each (a band: 1, a picture: its bands): group after group,
+// gather(u0, nu, planes) makes units u0 .. u0 + nu - 1 the float64 planes of one group, jpegx_forward_fused_n writes them into
+// the right rows of the batch's int32 stream; then the sizes, the plane index and -- with a destination -- the emitter.
+template <class Gather>
+int compress_stack(int nplanes, int unit, int N, const Shape &s, int mode, double param, void *d_workspace, uint8_t *d_out, size_t out_cap,
+                   jpegx_stream_t stream, Gather gather)
 {
-    const unsigned long long lone = (unsigned long long)s.nb * unit * max_block_bytes(N);
-    unsigned long long b = lone > GROUP_BYTES ? lone : GROUP_BYTES;
-    if (b > MAX_STREAM - 1) b = MAX_STREAM - 1;
-    return nbytes < b ? nbytes : b;
+    const CompressWs c = carve_compress(d_workspace, nplanes, N, s);
+    int rc = for_each_stride(nplanes / unit, s.gp / unit, [&](int u0, int nu) {
+        const int rc = gather(u0, nu, c.planes);
+        return rc ? rc : jpegx_forward_fused_n(c.planes, nu * unit * s.H, s.W, s.W, N, mode, param, c.zz + (size_t)u0 * unit * s.samples, stream);
+    });
+    if (rc || (rc = jpegx_entropy_sizes_n(c.zz, s.nb * nplanes, N * N, c.ews, stream))) return rc;
+    return enqueue_index_and_emit(c, nplanes, N, s, d_out, out_cap, stream);
 }
 
-DecompressWs carve_decompress(void *ws, size_t nbytes, int N, const Shape &s, int unit)
+// ---- decompress: carve_decompress_n for the longest group's stream and gp planes; a group holds at least one unit ----------
+DecompressWsN carve_decompress(void *ws, size_t nbytes, int N, const Shape &s, int unit)
 {
-    const size_t bmax = (size_t)group_bytes_max(nbytes, N, s, unit);
-    unsigned char *p = static_cast<unsigned char *>(ws);
-    DecompressWs d;
-    size_t o = 0;
-    d.zz = reinterpret_cast<int32_t *>(p + o); o += up256((size_t)s.gp * s.samples * 4);
-    d.stage = p + o; o += up256(bmax + 32);
-    d.dws = p + o; o += up256(jpegx_entropy_decode_workspace_bytes_n(bmax, s.nb * s.gp, N * N));
-    d.plane = p + o; o += up256((size_t)s.gp * s.samples);
-    d.bytes = o;
-    return d;
+    return carve_decompress_n(ws, group_bytes_max(nbytes, s.nb * unit, max_block_bytes(N), STREAM_N), (size_t)s.gp * s.samples, N);
 }
 
 // The cut: the next group is whole units (of `unit` planes each: a band is 1, a picture its bands) while it holds fewer than
 // gp planes and the stream stays within GROUP_BYTES, one unit at least.  first[g] .. first[g + 1] - 1 are group g's units.
 int cut_groups(const unsigned long long *off, int nplanes, const Shape &s, int unit, const char *unit_name, std::vector<int> *first)
 {
-    for (int p = 0; p < nplanes; ++p) {
-        if (off[p + 1] < off[p]) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "batch_n: plane offsets must not decrease (plane %d starts at %llu, plane %d at %llu)", p, off[p], p + 1, off[p + 1]);
-            return fail(JPEGX_E_INVALID, buf);
-        }
-    }
+    int rc = check_offsets("batch_n", off, nplanes);
+    if (rc) return rc;
     first->clear();
     const int n = nplanes / unit, cap = s.gp / unit;
     for (int p0 = 0; p0 < n;) {
         int p1 = p0 + 1;
         while (p1 < n && p1 - p0 < cap && off[(size_t)(p1 + 1) * unit] - off[(size_t)p0 * unit] <= GROUP_BYTES) ++p1;
-        const unsigned long long held = off[(size_t)p1 * unit] - off[(size_t)p0 * unit];
-        if (held >= MAX_STREAM) {                        // only a lone unit can: one decode call is below 2^32 - 4096 bytes
-            char buf[160];
-            snprintf(buf, sizeof(buf), "batch_n: %s %d holds %llu bytes, one decode call takes fewer than 2^32 - 4096", unit_name, p0, held);
-            return fail(JPEGX_E_INVALID, buf);
-        }
+        if ((rc = check_held("batch_n", unit_name, p0, off[(size_t)p1 * unit] - off[(size_t)p0 * unit], STREAM_N))) return rc;
         first->push_back(p0);
         p0 = p1;
     }
     first->push_back(n);
     return JPEGX_OK;
+}
+
+// The way back of a stack: the cut, then decompress_groups_n over it; a group is a tall plane of width W.
+// scatter(u0, nu, planes): the clamped planes of units u0 .. u0 + nu - 1 -> the caller's samples.
+template <class Scatter>
+int decompress_stack(const char *who, bool pictures, const uint8_t *d_bytes, const unsigned long long *off, int nplanes, int unit, int N, const Shape &s,
+                     int mode, double param, void *d_workspace, jpegx_stream_t stream, Scatter scatter)
+{
+    std::vector<int> first;
+    const int rc = cut_groups(off, nplanes, s, unit, pictures ? "picture" : "plane", &first);
+    if (rc) return rc;
+    const DecompressWsN w = carve_decompress(d_workspace, (size_t)(off[nplanes] - off[0]), N, s, unit);
+    return decompress_groups_n(
+        who, pictures ? "pictures" : "planes", d_bytes, first, [&](int u) { return off[(size_t)u * unit]; },
+        [&](int u0, int u1) { return s.nb * unit * (u1 - u0); }, s.W, N, mode, param, w, [&](int u0, int nu) { return scatter(u0, nu, w.plane); }, stream);
 }
 
 // shape of a batch of pictures: the band batch of nbands * npictures planes, groups of whole pictures
@@ -174,10 +145,8 @@ int picture_shape(const char *who, int npictures, int nbands, int rows, int cols
         snprintf(buf, sizeof(buf), "%s takes 1..JPEGX_MAX_IMAGE_BANDS bands", who);
         return fail(JPEGX_E_INVALID, buf);
     }
-    if ((colour != 0 && colour != 1) || (colour == 1 && nbands != 3)) {
-        snprintf(buf, sizeof(buf), "%s: colour must be 0 (as they are) or, with three bands, 1 (RGB pixels, YCbCr planes)", who);
-        return fail(JPEGX_E_INVALID, buf);
-    }
+    const int rc = check_colour(who, nbands, colour);
+    if (rc) return rc;
     if (group_planes <= 0 || group_planes % nbands) {
         snprintf(buf, sizeof(buf), "%s: group_planes must be a positive multiple of the band count (jpegx_batch_group_planes_pictures_n)", who);
         return fail(JPEGX_E_INVALID, buf);
@@ -213,15 +182,9 @@ int jpegx_batch_compress_n(const uint8_t *d_bands, int nplanes, int rows, int co
     if (rc || (rc = check_quantiser(mode, param))) return rc;
     if (pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "batch_compress_n: pitch smaller than the row");
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_compress_n: workspace must be 16-byte aligned");
-    const CompressWs c = carve_compress(d_workspace, nplanes, N, s);
-    for (int p0 = 0; p0 < nplanes; p0 += s.gp) {
-        const int np = nplanes - p0 < s.gp ? nplanes - p0 : s.gp;
-        if ((rc = jpegx_band_planes_stacked_n(d_bands + (size_t)p0 * rows * (size_t)pitch, np, rows, cols, pitch, bs, N, c.planes, s.W, stream)) ||
-            (rc = jpegx_forward_fused_n(c.planes, np * s.H, s.W, s.W, N, mode, param, c.zz + (size_t)p0 * s.samples, stream)))
-            return rc;
-    }
-    if ((rc = jpegx_entropy_sizes_n(c.zz, s.nb * nplanes, N * N, c.ews, stream))) return rc;
-    return enqueue_index_and_emit(c, nplanes, N, s, d_out, out_cap, stream);
+    return compress_stack(nplanes, 1, N, s, mode, param, d_workspace, d_out, out_cap, stream, [&](int p0, int np, double *planes) {
+        return jpegx_band_planes_stacked_n(d_bands + (size_t)p0 * rows * (size_t)pitch, np, rows, cols, pitch, bs, N, planes, s.W, stream);
+    });
 }
 
 int jpegx_batch_emit_n(void *d_workspace, int nplanes, int rows, int cols, int bs, int N, int group_planes, uint8_t *d_out, size_t out_cap,
@@ -243,23 +206,7 @@ int jpegx_batch_compress_status_n(const void *d_workspace, int nplanes, int rows
     const int rc = batch_shape(nplanes, rows, cols, bs, N, group_planes, &s);
     if (rc) return rc;
     const CompressWs c = carve_compress(const_cast<void *>(d_workspace), nplanes, N, s);
-    unsigned long long ehead[2] = {0, 0}, bhead[2] = {0, 0};
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(ehead, c.ews, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bhead, c.index, 16, hipMemcpyDeviceToHost, st));
-    if (h_plane_offsets)
-        HIP_TRY(hipMemcpyAsync(h_plane_offsets, static_cast<const unsigned char *>(c.index) + 16, ((size_t)nplanes + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *h_total = ehead[0];
-    if ((unsigned)(ehead[1] & 0xFFFFFFFFull) != 0)
-        return fail(JPEGX_E_INVALID, "BadRleCodeError: an amplitude needs more than 15 bits (|a| > 16383); nothing was written");
-    if (bhead[0] != SIZES_ONLY && ehead[0] > bhead[0]) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "batch_n: the coded stream needs %llu bytes, the buffer holds %llu; nothing was written", ehead[0], bhead[0]);
-        jpegx_internal_set_error(buf);
-        return 1;
-    }
-    return JPEGX_OK;
+    return read_compress_status(c.ews, c.index, (size_t)nplanes, "batch_n", h_total, h_plane_offsets, stream);
 }
 
 int jpegx_batch_groups_n(const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols, int bs, int N, int group_planes,
@@ -271,10 +218,7 @@ int jpegx_batch_groups_n(const unsigned long long *h_plane_offsets, int nplanes,
     if (rc) return rc;
     std::vector<int> first;
     if ((rc = cut_groups(h_plane_offsets, nplanes, s, 1, "plane", &first))) return rc;
-    *ngroups = (int)first.size() - 1;
-    if (h_group_first)
-        for (size_t g = 0; g < first.size(); ++g) h_group_first[g] = first[g];
-    return JPEGX_OK;
+    return report_groups(first, h_group_first, ngroups);
 }
 
 size_t jpegx_batch_decompress_workspace_bytes_n(size_t nbytes, int nplanes, int rows, int cols, int bs, int N, int group_planes)
@@ -293,43 +237,11 @@ int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h
     if (rc || (rc = check_quantiser(mode, param))) return rc;
     if (out_pitch < (ptrdiff_t)cols) return fail(JPEGX_E_INVALID, "batch_decompress_n: output pitch smaller than the row");
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_decompress_n: workspace must be 16-byte aligned");
-    std::vector<int> first;
-    if ((rc = cut_groups(h_plane_offsets, nplanes, s, 1, "plane", &first))) return rc;
-    const int ngroups = (int)first.size() - 1;
-    char where[320];
-    const size_t total = (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]);
-    const unsigned long long bmax = group_bytes_max(total, N, s, 1);         // what the staging area holds
-    for (int g = 0; g < ngroups; ++g) {                  // a block is 1 .. max_block_bytes bytes: refused before any device work
-        const unsigned long long gbytes = h_plane_offsets[first[g + 1]] - h_plane_offsets[first[g]];
-        const long long gblocks = s.nb * (first[g + 1] - first[g]);
-        if (gbytes < (unsigned long long)gblocks || gbytes > bmax) {
-            snprintf(where, sizeof(where), "batch_decompress_n: planes %d..%d: %llu bytes cannot be their %lld blocks", first[g], first[g + 1] - 1, gbytes,
-                     gblocks);
-            return fail(JPEGX_E_INVALID, where);
-        }
-    }
-    const DecompressWs w = carve_decompress(d_workspace, total, N, s, 1);
-    hipStream_t st = (hipStream_t)stream;
-    for (int g = 0; g < ngroups; ++g) {
-        const int p0 = first[g], np = first[g + 1] - p0;
-        const size_t gbytes = (size_t)(h_plane_offsets[p0 + np] - h_plane_offsets[p0]);
-        const long long gblocks = s.nb * np;
-        // the group's bytes, dword aligned and with zeros behind them, as the decoder wants them
-        HIP_TRY(hipMemsetAsync(w.stage + (gbytes & ~(size_t)3), 0, 16 + (gbytes & 3), st));
-        HIP_TRY(hipMemcpyAsync(w.stage, d_bytes + h_plane_offsets[p0], gbytes, hipMemcpyDeviceToDevice, st));
-        if ((rc = jpegx_entropy_decode_n(w.stage, gbytes, gblocks, N * N, w.dws, w.zz, stream))) return rc;
-        rc = jpegx_entropy_decode_status_n(w.dws, stream);      // synchronises: nothing of a refused group is written
-        if (rc == JPEGX_E_INVALID) {
-            snprintf(where, sizeof(where), "batch_decompress_n: planes %d..%d: their %llu bytes are not %lld well-formed blocks (%.120s)", p0, p0 + np - 1,
-                     (unsigned long long)gbytes, gblocks, jpegx_last_error());
-            return fail(JPEGX_E_INVALID, where);
-        }
-        if (rc) return rc;
-        if ((rc = jpegx_inverse_fused_n(w.zz, np * s.H, s.W, N, mode, param, JPEGX_F_CLAMP_U8, w.plane, s.W, stream)) ||
-            (rc = jpegx_inflate_crop_stacked_u8(w.plane, np, s.H, s.W, rows, cols, bs, d_out + (size_t)p0 * rows * (size_t)out_pitch, out_pitch, stream)))
-            return rc;
-    }
-    return JPEGX_OK;
+    return decompress_stack("batch_decompress_n", false, d_bytes, h_plane_offsets, nplanes, 1, N, s, mode, param, d_workspace, stream,
+                            [&](int p0, int np, const uint8_t *planes) {
+                                return jpegx_inflate_crop_stacked_u8(planes, np, s.H, s.W, rows, cols, bs, d_out + (size_t)p0 * rows * (size_t)out_pitch,
+                                                                     out_pitch, stream);
+                            });
 }
 
 // ---- a stack of PICTURES: the band batch of nbands * npictures planes, picture-major, cut on picture boundaries --------
@@ -350,17 +262,10 @@ int jpegx_batch_compress_pictures_n(const uint8_t *d_pixels, int npictures, int 
     if (rc || (rc = check_quantiser(mode, param))) return rc;
     if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_compress_pictures_n: pitch smaller than the row");
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_compress_pictures_n: workspace must be 16-byte aligned");
-    const int nplanes = npictures * nbands, gpics = s.gp / nbands;
-    const CompressWs c = carve_compress(d_workspace, nplanes, N, s);
-    for (int q0 = 0; q0 < npictures; q0 += gpics) {
-        const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
-        if ((rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, c.planes,
-                                                     s.W, stream)) ||
-            (rc = jpegx_forward_fused_n(c.planes, nq * nbands * s.H, s.W, s.W, N, mode, param, c.zz + (size_t)q0 * nbands * s.samples, stream)))
-            return rc;
-    }
-    if ((rc = jpegx_entropy_sizes_n(c.zz, s.nb * nplanes, N * N, c.ews, stream))) return rc;
-    return enqueue_index_and_emit(c, nplanes, N, s, d_out, out_cap, stream);
+    return compress_stack(npictures * nbands, nbands, N, s, mode, param, d_workspace, d_out, out_cap, stream, [&](int q0, int nq, double *planes) {
+        return jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, planes, s.W,
+                                                  stream);
+    });
 }
 
 int jpegx_batch_groups_pictures_n(const unsigned long long *h_plane_offsets, int npictures, int nbands, int rows, int cols, int bs, int N,
@@ -372,10 +277,7 @@ int jpegx_batch_groups_pictures_n(const unsigned long long *h_plane_offsets, int
     if (rc) return rc;
     std::vector<int> first;
     if ((rc = cut_groups(h_plane_offsets, npictures * nbands, s, nbands, "picture", &first))) return rc;
-    *ngroups = (int)first.size() - 1;
-    if (h_group_first)
-        for (size_t g = 0; g < first.size(); ++g) h_group_first[g] = first[g];
-    return JPEGX_OK;
+    return report_groups(first, h_group_first, ngroups);
 }
 
 size_t jpegx_batch_decompress_pictures_workspace_bytes_n(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs, int N, int group_planes)
@@ -395,46 +297,11 @@ int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned lon
     if (rc || (rc = check_quantiser(mode, param))) return rc;
     if (out_pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_decompress_pictures_n: output pitch smaller than the row");
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_decompress_pictures_n: workspace must be 16-byte aligned");
-    const int nplanes = npictures * nbands;
-    std::vector<int> first;                              // pictures
-    if ((rc = cut_groups(h_plane_offsets, nplanes, s, nbands, "picture", &first))) return rc;
-    const int ngroups = (int)first.size() - 1;
-    char where[320];
-    const size_t total = (size_t)(h_plane_offsets[nplanes] - h_plane_offsets[0]);
-    const unsigned long long bmax = group_bytes_max(total, N, s, nbands);   // what the staging area holds
-    for (int g = 0; g < ngroups; ++g) {                  // a block is 1 .. max_block_bytes bytes: refused before any device work
-        const unsigned long long gbytes = h_plane_offsets[(size_t)first[g + 1] * nbands] - h_plane_offsets[(size_t)first[g] * nbands];
-        const long long gblocks = s.nb * nbands * (first[g + 1] - first[g]);
-        if (gbytes < (unsigned long long)gblocks || gbytes > bmax) {
-            snprintf(where, sizeof(where), "batch_decompress_pictures_n: pictures %d..%d: %llu bytes cannot be their %lld blocks", first[g], first[g + 1] - 1,
-                     gbytes, gblocks);
-            return fail(JPEGX_E_INVALID, where);
-        }
-    }
-    const DecompressWs w = carve_decompress(d_workspace, total, N, s, nbands);
-    hipStream_t st = (hipStream_t)stream;
-    for (int g = 0; g < ngroups; ++g) {
-        const int q0 = first[g], nq = first[g + 1] - q0, np = nq * nbands;
-        const unsigned long long start = h_plane_offsets[(size_t)q0 * nbands];
-        const size_t gbytes = (size_t)(h_plane_offsets[(size_t)(q0 + nq) * nbands] - start);
-        const long long gblocks = s.nb * np;
-        // the group's bytes, dword aligned and with zeros behind them, as the decoder wants them
-        HIP_TRY(hipMemsetAsync(w.stage + (gbytes & ~(size_t)3), 0, 16 + (gbytes & 3), st));
-        HIP_TRY(hipMemcpyAsync(w.stage, d_bytes + start, gbytes, hipMemcpyDeviceToDevice, st));
-        if ((rc = jpegx_entropy_decode_n(w.stage, gbytes, gblocks, N * N, w.dws, w.zz, stream))) return rc;
-        rc = jpegx_entropy_decode_status_n(w.dws, stream);      // synchronises: nothing of a refused group is written
-        if (rc == JPEGX_E_INVALID) {
-            snprintf(where, sizeof(where), "batch_decompress_pictures_n: pictures %d..%d: their %llu bytes are not %lld well-formed blocks (%.120s)", q0,
-                     q0 + nq - 1, (unsigned long long)gbytes, gblocks, jpegx_last_error());
-            return fail(JPEGX_E_INVALID, where);
-        }
-        if (rc) return rc;
-        if ((rc = jpegx_inverse_fused_n(w.zz, np * s.H, s.W, N, mode, param, JPEGX_F_CLAMP_U8, w.plane, s.W, stream)) ||
-            (rc = jpegx_inflate_crop_pack_stacked_u8(w.plane, nq, nbands, s.H, s.W, rows, cols, bs, colour, d_out + (size_t)q0 * rows * (size_t)out_pitch,
-                                                     out_pitch, stream)))
-            return rc;
-    }
-    return JPEGX_OK;
+    return decompress_stack("batch_decompress_pictures_n", true, d_bytes, h_plane_offsets, npictures * nbands, nbands, N, s, mode, param, d_workspace,
+                            stream, [&](int q0, int nq, const uint8_t *planes) {
+                                return jpegx_inflate_crop_pack_stacked_u8(planes, nq, nbands, s.H, s.W, rows, cols, bs, colour,
+                                                                          d_out + (size_t)q0 * rows * (size_t)out_pitch, out_pitch, stream);
+                            });
 }
 
 // ---- the size probe over a stack of pictures (jpegx_probe_n.hip): one group of float64 planes is the whole workspace ------
@@ -457,15 +324,11 @@ int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nba
     if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: d_workspace must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_totals) & 7u) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: d_totals must be 8-byte aligned");
     double *planes = static_cast<double *>(d_workspace);
-    const int gpics = s.gp / nbands;
-    for (int q0 = 0; q0 < npictures; q0 += gpics) {
-        const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
-        if ((rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, planes, s.W,
-                                                     stream)) ||
-            (rc = jpegx_probe_sizes_n(planes, nq * nbands, s.H, s.W, s.W, N, mode, h_params, K, d_totals + (size_t)q0 * nbands * K, stream)))
-            return rc;
-    }
-    return JPEGX_OK;
+    return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
+        const int rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, planes,
+                                                          s.W, stream);
+        return rc ? rc : jpegx_probe_sizes_n(planes, nq * nbands, s.H, s.W, s.W, N, mode, h_params, K, d_totals + (size_t)q0 * nbands * K, stream);
+    });
 }
 
 // ---- the distortion probe over a stack of pictures (jpegx_distort_n.hip): one group of float64 planes and one of moments ------
@@ -491,17 +354,13 @@ int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictur
     if (reinterpret_cast<uintptr_t>(d_totals) & 7u) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_totals must be 8-byte aligned");
     double *planes = static_cast<double *>(d_workspace);
     unsigned long long *moments = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(d_workspace) + up256((size_t)s.gp * s.samples * 8));
-    const int gpics = s.gp / nbands;
-    for (int q0 = 0; q0 < npictures; q0 += gpics) {
-        const int nq = npictures - q0 < gpics ? npictures - q0 : gpics;
+    return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
         const uint8_t *px = d_pixels + (size_t)q0 * rows * (size_t)pitch;
-        if ((rc = jpegx_band_planes_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, planes, s.W, stream)) ||
-            (rc = jpegx_band_moments_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, moments, s.W, stream)) ||
-            (rc = jpegx_probe_distortion_n(planes, moments, nq * nbands, s.H, s.W, s.W, s.W, N, bs, rows, cols, mode, h_params, K,
-                                           d_totals + (size_t)q0 * nbands * K, stream)))
-            return rc;
-    }
-    return JPEGX_OK;
+        int rc = jpegx_band_planes_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, planes, s.W, stream);
+        if (rc || (rc = jpegx_band_moments_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, N, moments, s.W, stream))) return rc;
+        return jpegx_probe_distortion_n(planes, moments, nq * nbands, s.H, s.W, s.W, s.W, N, bs, rows, cols, mode, h_params, K,
+                                        d_totals + (size_t)q0 * nbands * K, stream);
+    });
 }
 
 }  // extern "C"

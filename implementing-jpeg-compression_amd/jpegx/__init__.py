@@ -1524,6 +1524,94 @@ decompress_image_n = _colour_keyword(decompress_image_n, functools.partial(_deco
 
 
 # ---------------------------------------------------------------------------------------------
+# what the device wrappers and host conveniences of the batch codec share
+# ---------------------------------------------------------------------------------------------
+def _entry(name, device, *args):
+    """The return code of the C entry ``name``, or with a ``device`` of its ``_on`` form there.  Through lib() on every call."""
+    L = lib()
+    return getattr(L, name)(*args) if device is None else getattr(L, name + "_on")(int(device), *args)
+
+
+def _entry_checked(name, device, *args):
+    check(_entry(name, device, *args), name)
+
+
+def _compress_status(name, device, nplanes, head, stream):
+    """(rc, total, offsets) of a jpegx_batch_compress_status* entry, ``head`` its arguments in front of h_total: rc 0, 1 or -1
+    are the entry's verdicts, anything else raises."""
+    total = ctypes.c_ulonglong(0)
+    off = np.zeros(int(nplanes) + 1, dtype=np.uint64)
+    rc = _entry(name, device, *head, ctypes.byref(total), off.ctypes.data, stream)
+    if rc not in (0, 1, -1):
+        check(rc, name)
+    return rc, total.value, off
+
+
+def _plane_offsets(plane_offsets, nplanes, words):
+    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
+    if off.shape != (int(nplanes) + 1,):
+        raise JpegxError("plane_offsets must hold %s + 1 entries" % words)
+    return off
+
+
+def _blob_offsets(flat):
+    """(offsets, total) of byte strings laid behind each other."""
+    off = np.zeros(len(flat) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in flat])
+    return off, int(off[-1])
+
+
+def _cut_blobs(blob, off, k, nb=None):
+    """The coded stream back as k byte strings, or with ``nb`` as k lists of nb (picture-major)."""
+    flat = [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(k * (nb or 1))]
+    return flat if nb is None else [flat[p * nb:(p + 1) * nb] for p in range(k)]
+
+
+def _picture_stack(pixels):
+    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
+    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
+        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
+    return np.ascontiguousarray(src)
+
+
+def _picture_list(pictures):
+    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
+    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
+        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    return pics
+
+
+def _picture_blobs(blobs, sizes=None):
+    """(blobs as lists of bytes, pictures, bands) of what a picture compress returned; with ``sizes``, one size per picture."""
+    blobs = [[bytes(b) for b in picture] for picture in blobs]
+    k = len(blobs)
+    nb = len(blobs[0]) if k else 0
+    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs) or (sizes is not None and len(sizes) != k):
+        raise JpegxError("expected at least one picture, and the same number of bands in each" if sizes is None
+                         else "expected at least one picture, the same number of bands in each, and a size for each")
+    return blobs, k, nb
+
+
+def _probe_answer(raw):
+    """A probe's uint64 totals -> (bits 0..62, the bad-amplitude flag of bit 63)."""
+    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
+
+
+def _emit_exactly(dev, status, emit, emit_name):
+    """After a sizes-only compress: read the total (status() -> (rc, total, offsets)), emit into a buffer of exactly that
+    (emit(d_out, cap)), check that the second verdict agrees, download.  (stream, offsets)."""
+    rc, total, off = status()
+    if rc != 0:
+        check(rc, emit_name.replace("_emit", "_compress_status"))
+    dout = dev(max(1, total))
+    emit(dout.ptr, total)
+    rc, total2, off = status()
+    if rc != 0 or total2 != total:
+        check(rc if rc else -1, emit_name)
+    return dout.download((total,), np.uint8), off
+
+
+# ---------------------------------------------------------------------------------------------
 # batch codec on device buffers: a stack of planes -> one coded stream with a plane index, and back
 # ---------------------------------------------------------------------------------------------
 def batch_workspace_bytes(nplanes, height, width):
@@ -1545,40 +1633,29 @@ def batch_compress_device(in_ptr, elem_size, nplanes, height, width, d_workspace
     index: batch_compress_status."""
     args = (in_ptr, int(elem_size), int(nplanes), int(height), int(width), int(width * block_size if pitch is None else pitch),
             int(block_size), mode_of(mode), float(param), int(flags), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress(*args) if device is None else L.jpegx_batch_compress_on(int(device), *args), "jpegx_batch_compress")
+    _entry_checked("jpegx_batch_compress", device, *args)
 
 
 def batch_compress_status(d_workspace, nplanes, height, width, stream=None, device=None):
     """Synchronises; returns (rc, total, offsets): rc 0, 1 (did not fit the capacity of the last compress / emit) or
     JPEGX_E_INVALID (-1: an amplitude beyond 15 bits); offsets: uint64 (nplanes + 1,), the last one = total."""
-    total = ctypes.c_ulonglong(0)
-    off = np.zeros(int(nplanes) + 1, dtype=np.uint64)
-    args = (d_workspace, int(nplanes), int(height), int(width), ctypes.byref(total), off.ctypes.data, stream)
-    L = lib()
-    rc = L.jpegx_batch_compress_status(*args) if device is None else L.jpegx_batch_compress_status_on(int(device), *args)
-    if rc not in (0, 1, -1):
-        check(rc, "jpegx_batch_compress_status")
-    return rc, total.value, off
+    return _compress_status("jpegx_batch_compress_status", device, int(nplanes),
+                            (d_workspace, int(nplanes), int(height), int(width)), stream)
 
 
 def batch_emit_device(d_workspace, nplanes, height, width, d_out, out_cap, stream=None, device=None):
     args = (d_workspace, int(nplanes), int(height), int(width), d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_emit(*args) if device is None else L.jpegx_batch_emit_on(int(device), *args), "jpegx_batch_emit")
+    _entry_checked("jpegx_batch_emit", device, *args)
 
 
 def batch_decompress_device(d_bytes, plane_offsets, nplanes, height, width, d_workspace, d_out, out_pitch, block_size=1,
                             mode="qtable", param=0.0, flags=0, out_type=OUT_U8, stream=None, device=None):
     """jpegx_batch_decompress (synchronises the stream between groups and levels); plane_offsets: nplanes + 1 host
     integers.  Returns the C return code's success; raises JpegxError otherwise."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(nplanes) + 1,):
-        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    off = _plane_offsets(plane_offsets, int(nplanes), "nplanes")
     args = (d_bytes, off.ctypes.data, int(nplanes), int(height), int(width), int(block_size), mode_of(mode), float(param),
             int(flags), d_workspace, d_out, int(out_pitch), int(out_type), stream)
-    L = lib()
-    check(L.jpegx_batch_decompress(*args) if device is None else L.jpegx_batch_decompress_on(int(device), *args), "jpegx_batch_decompress")
+    _entry_checked("jpegx_batch_decompress", device, *args)
 
 
 def batch_compress(planes, block_size=1, mode="qtable", param=0.0, pixel_input=None):
@@ -1607,16 +1684,9 @@ def batch_compress(planes, block_size=1, mode="qtable", param=0.0, pixel_input=N
         din, dws = dev(a.nbytes), dev(batch_workspace_bytes(n, h, w))
         din.upload(a)
         batch_compress_device(din.ptr, elem, n, h, w, dws.ptr, None, 0, mode, param, flags, pitch=pitch, block_size=bs)
-        rc, total, off = batch_compress_status(dws.ptr, n, h, w)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status")
-        dout = dev(max(1, total))
-        batch_emit_device(dws.ptr, n, h, w, dout.ptr, total)
-        rc, total2, off = batch_compress_status(dws.ptr, n, h, w)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit")
-        blob = dout.download((total,), np.uint8)
-        return [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(n)]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status(dws.ptr, n, h, w),
+                                  lambda d_out, cap: batch_emit_device(dws.ptr, n, h, w, d_out, cap), "jpegx_batch_emit")
+        return _cut_blobs(blob, off, n)
 
 
 def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.0, out="u8"):
@@ -1629,9 +1699,7 @@ def batch_decompress(blobs, height, width, block_size=1, mode="qtable", param=0.
         raise JpegxError("expected at least one plane")
     out_type = _OUT_BY_NAME[out]
     dtype = np.dtype(_OUT_DTYPES[out_type])
-    off = np.zeros(n + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in blobs])
-    total = int(off[n])
+    off, total = _blob_offsets(blobs)
     stream_bytes = np.zeros(total + 16, dtype=np.uint8)               # 16 zero bytes behind the stream
     stream_bytes[:total] = np.frombuffer(b"".join(blobs), dtype=np.uint8)
     pitch = (width * bs * dtype.itemsize + 15) // 16 * 16 // dtype.itemsize
@@ -1665,9 +1733,7 @@ def batch_decompress_workspace_bytes_n(nbytes, nplanes, rows, cols, bs, n, group
 def batch_groups_n(plane_offsets, nplanes, rows, cols, bs, n, group_planes=0):
     """The cut of a coded batch into decoding groups (jpegx_batch_groups_n; host arithmetic, no device needed): the first
     plane of every group and, last, nplanes."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(nplanes) + 1,):
-        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    off = _plane_offsets(plane_offsets, int(nplanes), "nplanes")
     first = np.zeros(int(nplanes) + 1, dtype=np.int32)
     ngroups = ctypes.c_int(0)
     check(lib().jpegx_batch_groups_n(off.ctypes.data, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes),
@@ -1680,9 +1746,7 @@ def band_planes_stacked_n_device(d_bands, nplanes, rows, cols, bs, n, d_out, pit
     [nplanes * H][out_pitch] (default W), (H, W) = band_shape_n(rows, cols, bs, n)."""
     args = (d_bands, int(nplanes), int(rows), int(cols), int(cols if pitch is None else pitch), int(bs), int(n), d_out,
             int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_band_planes_stacked_n(*args) if device is None else L.jpegx_band_planes_stacked_n_on(int(device), *args),
-          "jpegx_band_planes_stacked_n")
+    _entry_checked("jpegx_band_planes_stacked_n", device, *args)
 
 
 def inflate_crop_stacked_u8_device(d_planes, nplanes, height, pitch, rows, cols, bs, d_out, out_pitch=None, stream=None, device=None):
@@ -1690,9 +1754,7 @@ def inflate_crop_stacked_u8_device(d_planes, nplanes, height, pitch, rows, cols,
     [nplanes * rows][out_pitch] (default cols)."""
     args = (d_planes, int(nplanes), int(height), int(pitch), int(rows), int(cols), int(bs), d_out,
             int(cols if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_inflate_crop_stacked_u8(*args) if device is None else L.jpegx_inflate_crop_stacked_u8_on(int(device), *args),
-          "jpegx_inflate_crop_stacked_u8")
+    _entry_checked("jpegx_inflate_crop_stacked_u8", device, *args)
 
 
 def batch_compress_n_device(d_bands, nplanes, rows, cols, bs, n, d_workspace, d_out, out_cap, mode="none", param=0.0,
@@ -1701,39 +1763,28 @@ def batch_compress_n_device(d_bands, nplanes, rows, cols, bs, n, d_workspace, d_
     (None: sizes only).  Verdict and plane index: batch_compress_status_n."""
     args = (d_bands, int(nplanes), int(rows), int(cols), int(cols if pitch is None else pitch), int(bs), int(n), mode_of(mode),
             float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress_n(*args) if device is None else L.jpegx_batch_compress_n_on(int(device), *args), "jpegx_batch_compress_n")
+    _entry_checked("jpegx_batch_compress_n", device, *args)
 
 
 def batch_compress_status_n(d_workspace, nplanes, rows, cols, bs, n, group_planes=0, stream=None, device=None):
     """Synchronises; returns (rc, total, offsets) as batch_compress_status does."""
-    total = ctypes.c_ulonglong(0)
-    off = np.zeros(int(nplanes) + 1, dtype=np.uint64)
-    args = (d_workspace, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes), ctypes.byref(total), off.ctypes.data, stream)
-    L = lib()
-    rc = L.jpegx_batch_compress_status_n(*args) if device is None else L.jpegx_batch_compress_status_n_on(int(device), *args)
-    if rc not in (0, 1, -1):
-        check(rc, "jpegx_batch_compress_status_n")
-    return rc, total.value, off
+    return _compress_status("jpegx_batch_compress_status_n", device, int(nplanes),
+                            (d_workspace, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes)), stream)
 
 
 def batch_emit_n_device(d_workspace, nplanes, rows, cols, bs, n, d_out, out_cap, group_planes=0, stream=None, device=None):
     args = (d_workspace, int(nplanes), int(rows), int(cols), int(bs), int(n), int(group_planes), d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_emit_n(*args) if device is None else L.jpegx_batch_emit_n_on(int(device), *args), "jpegx_batch_emit_n")
+    _entry_checked("jpegx_batch_emit_n", device, *args)
 
 
 def batch_decompress_n_device(d_bytes, plane_offsets, nplanes, rows, cols, bs, n, d_workspace, d_out, out_pitch=None, mode="none",
                               param=0.0, group_planes=0, stream=None, device=None):
     """jpegx_batch_decompress_n (synchronises the stream once per group); plane_offsets: nplanes + 1 host integers; bands
     stacked [nplanes * rows][out_pitch] (default cols) at d_out.  Raises JpegxError for whatever the entry refuses."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(nplanes) + 1,):
-        raise JpegxError("plane_offsets must hold nplanes + 1 entries")
+    off = _plane_offsets(plane_offsets, int(nplanes), "nplanes")
     args = (d_bytes, off.ctypes.data, int(nplanes), int(rows), int(cols), int(bs), int(n), mode_of(mode), float(param),
             int(group_planes), d_workspace, d_out, int(cols if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_batch_decompress_n(*args) if device is None else L.jpegx_batch_decompress_n_on(int(device), *args), "jpegx_batch_decompress_n")
+    _entry_checked("jpegx_batch_decompress_n", device, *args)
 
 
 def batch_compress_n(bands, bs, n, mode="none", param=0.0, group_planes=0):
@@ -1755,16 +1806,9 @@ def batch_compress_n(bands, bs, n, mode="none", param=0.0, group_planes=0):
         din, dws = dev(src.nbytes), dev(nws)
         din.upload(src)
         batch_compress_n_device(din.ptr, *shape, dws.ptr, None, 0, mode, param, group_planes)
-        rc, total, off = batch_compress_status_n(dws.ptr, *shape, group_planes)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status_n")
-        dout = dev(max(1, total))
-        batch_emit_n_device(dws.ptr, *shape, dout.ptr, total, group_planes)
-        rc, total2, off = batch_compress_status_n(dws.ptr, *shape, group_planes)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit_n")
-        blob = dout.download((total,), np.uint8)
-        return [blob[int(off[p]):int(off[p + 1])].tobytes() for p in range(k)]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status_n(dws.ptr, *shape, group_planes),
+                                  lambda d_out, cap: batch_emit_n_device(dws.ptr, *shape, d_out, cap, group_planes), "jpegx_batch_emit_n")
+        return _cut_blobs(blob, off, k)
 
 
 def batch_decompress_n(blobs, rows, cols, bs, n, mode="none", param=0.0, group_planes=0):
@@ -1775,9 +1819,7 @@ def batch_decompress_n(blobs, rows, cols, bs, n, mode="none", param=0.0, group_p
     if k < 1:
         raise JpegxError("expected at least one band")
     rows, cols = int(rows), int(cols)
-    off = np.zeros(k + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in blobs])
-    total = int(off[k])
+    off, total = _blob_offsets(blobs)
     shape = (k, rows, cols, int(bs), int(n))
     nws = batch_decompress_workspace_bytes_n(max(total, 1), *shape, group_planes)
     if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
@@ -1821,9 +1863,7 @@ def batch_decompress_pictures_workspace_bytes_n(nbytes, npictures, nbands, rows,
 def batch_groups_pictures_n(plane_offsets, npictures, nbands, rows, cols, bs, n, group_planes):
     """The cut of a coded batch of pictures into decoding groups on picture boundaries (jpegx_batch_groups_pictures_n; host
     arithmetic, no device needed): the first PICTURE of every group and, last, npictures."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(npictures) * int(nbands) + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, int(npictures) * int(nbands), "nbands * npictures")
     first = np.zeros(int(npictures) + 1, dtype=np.int32)
     ngroups = ctypes.c_int(0)
     check(lib().jpegx_batch_groups_pictures_n(off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n),
@@ -1837,9 +1877,7 @@ def band_planes_packed_stacked_n_device(d_pixels, npictures, nbands, rows, cols,
     -> float64 planes stacked picture-major [npictures * nbands * H][out_pitch] (default W); colour 0 or 1 as in the header."""
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(bs), int(n), d_out, int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_band_planes_packed_stacked_n(*args) if device is None else L.jpegx_band_planes_packed_stacked_n_on(int(device), *args),
-          "jpegx_band_planes_packed_stacked_n")
+    _entry_checked("jpegx_band_planes_packed_stacked_n", device, *args)
 
 
 def inflate_crop_pack_stacked_u8_device(d_planes, npictures, nbands, height, pitch, rows, cols, bs, d_out, colour=0, out_pitch=None,
@@ -1848,9 +1886,7 @@ def inflate_crop_pack_stacked_u8_device(d_planes, npictures, nbands, height, pit
     stacked [npictures * rows][out_pitch] (bytes, default cols * nbands)."""
     args = (d_planes, int(npictures), int(nbands), int(height), int(pitch), int(rows), int(cols), int(bs), int(colour), d_out,
             int(cols * nbands if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_inflate_crop_pack_stacked_u8(*args) if device is None else L.jpegx_inflate_crop_pack_stacked_u8_on(int(device), *args),
-          "jpegx_inflate_crop_pack_stacked_u8")
+    _entry_checked("jpegx_inflate_crop_pack_stacked_u8", device, *args)
 
 
 def batch_compress_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs, n, d_workspace, d_out, out_cap, group_planes,
@@ -1859,9 +1895,7 @@ def batch_compress_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs
     coded bytes at d_out (None: sizes only).  Verdict and plane index: batch_compress_status_n with nbands * npictures planes."""
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(bs), int(n), mode_of(mode), float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress_pictures_n(*args) if device is None else L.jpegx_batch_compress_pictures_n_on(int(device), *args),
-          "jpegx_batch_compress_pictures_n")
+    _entry_checked("jpegx_batch_compress_pictures_n", device, *args)
 
 
 def batch_decompress_pictures_n_device(d_bytes, plane_offsets, npictures, nbands, rows, cols, bs, n, d_workspace, d_out, group_planes,
@@ -1869,14 +1903,10 @@ def batch_decompress_pictures_n_device(d_bytes, plane_offsets, npictures, nbands
     """jpegx_batch_decompress_pictures_n (synchronises the stream once per group); plane_offsets: nbands * npictures + 1 host
     integers; pictures stacked [npictures * rows][out_pitch] (default cols * nbands) at d_out.  Raises JpegxError for whatever
     the entry refuses."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(npictures) * int(nbands) + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, int(npictures) * int(nbands), "nbands * npictures")
     args = (d_bytes, off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(bs), int(n), mode_of(mode), float(param),
             int(colour), int(group_planes), d_workspace, d_out, int(cols * nbands if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_batch_decompress_pictures_n(*args) if device is None else L.jpegx_batch_decompress_pictures_n_on(int(device), *args),
-          "jpegx_batch_decompress_pictures_n")
+    _entry_checked("jpegx_batch_decompress_pictures_n", device, *args)
 
 
 def batch_compress_pictures_n(pixels, bs, n, mode="none", param=0.0, colour=None, group_planes=None):
@@ -1884,10 +1914,7 @@ def batch_compress_pictures_n(pixels, bs, n, mode="none", param=0.0, colour=None
     of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host convenience over the device entries (upload,
     sizes-only compress, status, emit into a buffer of exactly the total, download).  group_planes None: the recommended
     value.  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the batch."""
-    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
-    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
-        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
-    src = np.ascontiguousarray(src)
+    src = _picture_stack(pixels)
     k, rows, cols, nb = src.shape
     flag = _colour_flag(colour, nb, "batch_compress_pictures_n")
     if group_planes is None:
@@ -1903,35 +1930,22 @@ def batch_compress_pictures_n(pixels, bs, n, mode="none", param=0.0, colour=None
         din, dws = dev(src.nbytes), dev(nws)
         din.upload(src)
         batch_compress_pictures_n_device(din.ptr, *pics, dws.ptr, None, 0, group_planes, mode, param, flag)
-        rc, total, off = batch_compress_status_n(dws.ptr, *planes, group_planes)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status_n")
-        dout = dev(max(1, total))
-        batch_emit_n_device(dws.ptr, *planes, dout.ptr, total, group_planes)
-        rc, total2, off = batch_compress_status_n(dws.ptr, *planes, group_planes)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit_n")
-        blob = dout.download((total,), np.uint8)
-        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(k)]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status_n(dws.ptr, *planes, group_planes),
+                                  lambda d_out, cap: batch_emit_n_device(dws.ptr, *planes, d_out, cap, group_planes), "jpegx_batch_emit_n")
+        return _cut_blobs(blob, off, k, nb)
 
 
 def batch_decompress_pictures_n(blobs, rows, cols, bs, n, mode="none", param=0.0, colour=None, group_planes=None):
     """k lists of nb byte strings (as batch_compress_pictures_n returns them) -> uint8 [k][rows][cols][nb], picture p the
     np.dstack of what decompress_band_n gives for its bands (with colour='rgb': Pillow's RGB of that).  JpegxError naming a
     picture range for a stream the device refuses."""
-    blobs = [[bytes(b) for b in picture] for picture in blobs]
-    k = len(blobs)
-    nb = len(blobs[0]) if k else 0
-    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs):
-        raise JpegxError("expected at least one picture, and the same number of bands in each")
+    blobs, k, nb = _picture_blobs(blobs)
     flag = _colour_flag(colour, nb, "batch_decompress_pictures_n")
     rows, cols = int(rows), int(cols)
     if group_planes is None:
         group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, n) or nb
     flat = [b for picture in blobs for b in picture]
-    off = np.zeros(k * nb + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in flat])
-    total = int(off[-1])
+    off, total = _blob_offsets(flat)
     pics = (k, nb, rows, cols, int(bs), int(n))
     nws = batch_decompress_pictures_workspace_bytes_n(max(total, 1), *pics, group_planes)
     if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
@@ -1966,8 +1980,7 @@ def probe_sizes_n_device(d_planes, nplanes, height, width, n, mode, params, d_to
     h, k = _probe_params(params)
     args = (d_planes, int(nplanes), int(height), int(width), int(width if pitch is None else pitch), int(n), mode_of(mode),
             h.ctypes.data, k, d_totals, stream)
-    L = lib()
-    check(L.jpegx_probe_sizes_n(*args) if device is None else L.jpegx_probe_sizes_n_on(int(device), *args), "jpegx_probe_sizes_n")
+    _entry_checked("jpegx_probe_sizes_n", device, *args)
 
 
 def batch_probe_pictures_workspace_bytes_n(npictures, nbands, rows, cols, bs, n, group_planes):
@@ -1982,9 +1995,7 @@ def batch_probe_pictures_n_device(d_pixels, npictures, nbands, rows, cols, bs, n
     h, k = _probe_params(params)
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(bs), int(n), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
-    L = lib()
-    check(L.jpegx_batch_probe_pictures_n(*args) if device is None else L.jpegx_batch_probe_pictures_n_on(int(device), *args),
-          "jpegx_batch_probe_pictures_n")
+    _entry_checked("jpegx_batch_probe_pictures_n", device, *args)
 
 
 def batch_probe_pictures_n(pixels, bs, n, mode, params, colour=None, group_planes=None):
@@ -1992,10 +2003,7 @@ def batch_probe_pictures_n(pixels, bs, n, mode, params, colour=None, group_plane
     batch_compress_pictures_n would code it under candidate q; bad bool [k][nb][K], True where that band holds an amplitude
     beyond 15 bits under that candidate (its size is then meaningless).  Host convenience: upload, probe, one download.
     group_planes None: the recommended value."""
-    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
-    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
-        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
-    src = np.ascontiguousarray(src)
+    src = _picture_stack(pixels)
     k, rows, cols, nb = src.shape
     flag = _colour_flag(colour, nb, "batch_probe_pictures_n")
     if group_planes is None:
@@ -2013,7 +2021,7 @@ def batch_probe_pictures_n(pixels, bs, n, mode, params, colour=None, group_plane
         din.upload(src)
         batch_probe_pictures_n_device(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
         raw = dtot.download((k, nb, nk), np.uint64)
-    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
+    return _probe_answer(raw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2028,9 +2036,7 @@ def band_moments_packed_stacked_n_device(d_pixels, npictures, nbands, rows, cols
     pixels; colour 0 or 1 as in the header."""
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(bs), int(n), d_moments, int(band_shape_n(rows, cols, bs, n)[1] if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_band_moments_packed_stacked_n(*args) if device is None else L.jpegx_band_moments_packed_stacked_n_on(int(device), *args),
-          "jpegx_band_moments_packed_stacked_n")
+    _entry_checked("jpegx_band_moments_packed_stacked_n", device, *args)
 
 
 def probe_distortion_n_device(d_planes, d_moments, nplanes, height, width, n, bs, rows, cols, mode, params, d_totals, pitch=None, mpitch=None,
@@ -2041,8 +2047,7 @@ def probe_distortion_n_device(d_planes, d_moments, nplanes, height, width, n, bs
     h, k = _probe_params(params)
     args = (d_planes, d_moments, int(nplanes), int(height), int(width), int(width if pitch is None else pitch),
             int(width if mpitch is None else mpitch), int(n), int(bs), int(rows), int(cols), mode_of(mode), h.ctypes.data, k, d_totals, stream)
-    L = lib()
-    check(L.jpegx_probe_distortion_n(*args) if device is None else L.jpegx_probe_distortion_n_on(int(device), *args), "jpegx_probe_distortion_n")
+    _entry_checked("jpegx_probe_distortion_n", device, *args)
 
 
 def batch_probe_distortion_pictures_workspace_bytes_n(npictures, nbands, rows, cols, bs, n, group_planes):
@@ -2057,9 +2062,7 @@ def batch_probe_distortion_pictures_n_device(d_pixels, npictures, nbands, rows, 
     h, k = _probe_params(params)
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(bs), int(n), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
-    L = lib()
-    check(L.jpegx_batch_probe_distortion_pictures_n(*args) if device is None
-          else L.jpegx_batch_probe_distortion_pictures_n_on(int(device), *args), "jpegx_batch_probe_distortion_pictures_n")
+    _entry_checked("jpegx_batch_probe_distortion_pictures_n", device, *args)
 
 
 def batch_probe_distortion_pictures_n(pixels, bs, n, mode, params, colour=None, group_planes=None):
@@ -2068,10 +2071,7 @@ def batch_probe_distortion_pictures_n(pixels, bs, n, mode, params, colour=None, 
     colour='rgb': in the coded YCbCr bands); bad bool [k][nb][K], True where that band holds an amplitude beyond 15 bits under
     that candidate (it cannot be coded; its sum is then meaningless).  Host convenience: upload, probe, one download.
     group_planes None: the recommended value."""
-    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
-    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
-        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
-    src = np.ascontiguousarray(src)
+    src = _picture_stack(pixels)
     k, rows, cols, nb = src.shape
     flag = _colour_flag(colour, nb, "batch_probe_distortion_pictures_n")
     if group_planes is None:
@@ -2089,7 +2089,7 @@ def batch_probe_distortion_pictures_n(pixels, bs, n, mode, params, colour=None, 
         din.upload(src)
         batch_probe_distortion_pictures_n_device(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
         raw = dtot.download((k, nb, nk), np.uint64)
-    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
+    return _probe_answer(raw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2157,9 +2157,7 @@ def batch_decompress_set_workspace_bytes_n(nbytes, table, group_samples=0):
 def batch_groups_set_n(plane_offsets, table, group_samples=0):
     """The cut of a coded set into decoding groups on picture boundaries (jpegx_batch_groups_set_n; host arithmetic): the first
     PICTURE of every group and, last, npictures."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (table.npictures * table.nbands + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, table.npictures * table.nbands, "nbands * npictures")
     first = np.zeros(table.npictures + 1, dtype=np.int32)
     ngroups = ctypes.c_int(0)
     check(lib().jpegx_batch_groups_set_n(off.ctypes.data, table.ptr, int(group_samples), first.ctypes.data, ctypes.byref(ngroups)),
@@ -2170,17 +2168,13 @@ def batch_groups_set_n(plane_offsets, table, group_samples=0):
 def picture_set_blocks_n_device(d_pixels, table, d_table, p0, k, d_strip, colour=0, stream=None, device=None):
     """Enqueue jpegx_picture_set_blocks_n: pixels of pictures p0 .. p0 + k - 1 -> their float64 block strip at d_strip."""
     args = (d_pixels, table.ptr, d_table, int(p0), int(k), int(colour), d_strip, stream)
-    L = lib()
-    check(L.jpegx_picture_set_blocks_n(*args) if device is None else L.jpegx_picture_set_blocks_n_on(int(device), *args),
-          "jpegx_picture_set_blocks_n")
+    _entry_checked("jpegx_picture_set_blocks_n", device, *args)
 
 
 def picture_set_pixels_u8_device(d_strip, table, d_table, p0, k, d_out, colour=0, stream=None, device=None):
     """Enqueue jpegx_picture_set_pixels_u8: the uint8 block strip of pictures p0 .. p0 + k - 1 -> their pixels in d_out."""
     args = (d_strip, table.ptr, d_table, int(p0), int(k), int(colour), d_out, stream)
-    L = lib()
-    check(L.jpegx_picture_set_pixels_u8(*args) if device is None else L.jpegx_picture_set_pixels_u8_on(int(device), *args),
-          "jpegx_picture_set_pixels_u8")
+    _entry_checked("jpegx_picture_set_pixels_u8", device, *args)
 
 
 def batch_compress_picture_set_n_device(d_pixels, table, d_table, d_workspace, d_out, out_cap, mode="none", param=0.0, colour=0,
@@ -2188,40 +2182,27 @@ def batch_compress_picture_set_n_device(d_pixels, table, d_table, d_workspace, d
     """Enqueue jpegx_batch_compress_picture_set_n -> coded bytes at d_out (None: sizes only).  Verdict and plane index:
     batch_compress_status_set_n."""
     args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), float(param), int(group_samples), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress_picture_set_n(*args) if device is None else L.jpegx_batch_compress_picture_set_n_on(int(device), *args),
-          "jpegx_batch_compress_picture_set_n")
+    _entry_checked("jpegx_batch_compress_picture_set_n", device, *args)
 
 
 def batch_compress_status_set_n(d_workspace, table, group_samples=0, stream=None, device=None):
     """Synchronises; returns (rc, total, offsets) as batch_compress_status_n does."""
-    total = ctypes.c_ulonglong(0)
-    off = np.zeros(table.npictures * table.nbands + 1, dtype=np.uint64)
-    args = (d_workspace, table.ptr, int(group_samples), ctypes.byref(total), off.ctypes.data, stream)
-    L = lib()
-    rc = L.jpegx_batch_compress_status_set_n(*args) if device is None else L.jpegx_batch_compress_status_set_n_on(int(device), *args)
-    if rc not in (0, 1, -1):
-        check(rc, "jpegx_batch_compress_status_set_n")
-    return rc, total.value, off
+    return _compress_status("jpegx_batch_compress_status_set_n", device, table.npictures * table.nbands,
+                            (d_workspace, table.ptr, int(group_samples)), stream)
 
 
 def batch_emit_set_n_device(d_workspace, table, d_table, d_out, out_cap, group_samples=0, stream=None, device=None):
     args = (d_workspace, table.ptr, d_table, int(group_samples), d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_emit_set_n(*args) if device is None else L.jpegx_batch_emit_set_n_on(int(device), *args), "jpegx_batch_emit_set_n")
+    _entry_checked("jpegx_batch_emit_set_n", device, *args)
 
 
 def batch_decompress_picture_set_n_device(d_bytes, plane_offsets, table, d_table, d_workspace, d_out, mode="none", param=0.0, colour=0,
                                           group_samples=0, stream=None, device=None):
     """jpegx_batch_decompress_picture_set_n (synchronises the stream once per group); plane_offsets: nbands * npictures + 1 host
     integers; every picture at its offset and pitch in d_out.  Raises JpegxError for whatever the entry refuses."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (table.npictures * table.nbands + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, table.npictures * table.nbands, "nbands * npictures")
     args = (d_bytes, off.ctypes.data, table.ptr, d_table, mode_of(mode), float(param), int(colour), int(group_samples), d_workspace, d_out, stream)
-    L = lib()
-    check(L.jpegx_batch_decompress_picture_set_n(*args) if device is None else L.jpegx_batch_decompress_picture_set_n_on(int(device), *args),
-          "jpegx_batch_decompress_picture_set_n")
+    _entry_checked("jpegx_batch_decompress_picture_set_n", device, *args)
 
 
 def batch_compress_picture_set_n(pictures, bs, n, mode="none", param=0.0, colour=None, group_samples=0):
@@ -2229,9 +2210,7 @@ def batch_compress_picture_set_n(pictures, bs, n, mode="none", param=0.0, colour
     what compress_band_n gives for that band of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host
     convenience over the device entries (ONE flat upload, sizes-only compress, status, emit into a buffer of exactly the total,
     download).  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the set."""
-    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
-    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
-        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    pics = _picture_list(pictures)
     nb = pics[0].shape[2]
     flag = _colour_flag(colour, nb, "batch_compress_picture_set_n")
     table = picture_set_table([p.shape[:2] for p in pics], nb, bs, n)      # names the refusal, before any device is touched
@@ -2247,35 +2226,22 @@ def batch_compress_picture_set_n(pictures, bs, n, mode="none", param=0.0, colour
         din.upload(flat)
         dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
         batch_compress_picture_set_n_device(din.ptr, table, dtab.ptr, dws.ptr, None, 0, mode, param, flag, group_samples)
-        rc, total, off = batch_compress_status_set_n(dws.ptr, table, group_samples)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status_set_n")
-        dout = dev(max(1, total))
-        batch_emit_set_n_device(dws.ptr, table, dtab.ptr, dout.ptr, total, group_samples)
-        rc, total2, off = batch_compress_status_set_n(dws.ptr, table, group_samples)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit_set_n")
-        blob = dout.download((total,), np.uint8)
-        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(len(pics))]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status_set_n(dws.ptr, table, group_samples),
+                                  lambda d_out, cap: batch_emit_set_n_device(dws.ptr, table, dtab.ptr, d_out, cap, group_samples), "jpegx_batch_emit_set_n")
+        return _cut_blobs(blob, off, len(pics), nb)
 
 
 def batch_decompress_picture_set_n(blobs, sizes, bs, n, mode="none", param=0.0, colour=None, group_samples=0):
     """k lists of nb byte strings (as batch_compress_picture_set_n returns them) and the k (rows, cols) -> a list of uint8 arrays
     [rows_p][cols_p][nb], picture p the np.dstack of what decompress_band_n gives for its bands (with colour='rgb': Pillow's RGB
     of that).  JpegxError naming a picture range for a stream the device refuses."""
-    blobs = [[bytes(b) for b in picture] for picture in blobs]
     sizes = [(int(r), int(c)) for r, c in sizes]
-    k = len(blobs)
-    nb = len(blobs[0]) if k else 0
-    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs) or len(sizes) != k:
-        raise JpegxError("expected at least one picture, the same number of bands in each, and a size for each")
+    blobs, k, nb = _picture_blobs(blobs, sizes)
     flag = _colour_flag(colour, nb, "batch_decompress_picture_set_n")
     table = picture_set_table(sizes, nb, bs, n)
     mode_of(mode)
     flat = [b for picture in blobs for b in picture]
-    off = np.zeros(k * nb + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in flat])
-    total = int(off[-1])
+    off, total = _blob_offsets(flat)
     nws = batch_decompress_set_workspace_bytes_n(max(total, 1), table, group_samples)
     if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
         batch_decompress_picture_set_n_device(1, off, table, 8, 16, 1, mode, param, flag, group_samples)
@@ -2300,8 +2266,7 @@ def probe_sizes_set_n_device(d_strip, table, d_table, p0, k, mode, params, d_tot
     63 the bad-amplitude flag.  ``params``: the K candidates (host numbers)."""
     h, nk = _probe_params(params)
     args = (d_strip, table.ptr, d_table, int(p0), int(k), mode_of(mode), h.ctypes.data, nk, d_totals, stream)
-    L = lib()
-    check(L.jpegx_probe_sizes_set_n(*args) if device is None else L.jpegx_probe_sizes_set_n_on(int(device), *args), "jpegx_probe_sizes_set_n")
+    _entry_checked("jpegx_probe_sizes_set_n", device, *args)
 
 
 def batch_probe_picture_set_workspace_bytes_n(table, group_samples=0):
@@ -2314,9 +2279,7 @@ def batch_probe_picture_set_n_device(d_pixels, table, d_table, mode, params, d_w
     [npictures * nbands][K] in the table's plane order."""
     h, nk = _probe_params(params)
     args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), h.ctypes.data, nk, int(group_samples), d_workspace, d_totals, stream)
-    L = lib()
-    check(L.jpegx_batch_probe_picture_set_n(*args) if device is None else L.jpegx_batch_probe_picture_set_n_on(int(device), *args),
-          "jpegx_batch_probe_picture_set_n")
+    _entry_checked("jpegx_batch_probe_picture_set_n", device, *args)
 
 
 def batch_probe_picture_set_n(pictures, bs, n, mode, params, colour=None, group_samples=0):
@@ -2324,9 +2287,7 @@ def batch_probe_picture_set_n(pictures, bs, n, mode, params, colour=None, group_
     the length of band b of picture p as batch_compress_picture_set_n would code it under candidate q; bad bool of the same
     shape, True where that band holds an amplitude beyond 15 bits under that candidate (its size is then meaningless).  Host
     convenience: ONE flat upload, the probe, one download.  JpegxError for more than 32 candidates."""
-    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
-    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
-        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    pics = _picture_list(pictures)
     nb = pics[0].shape[2]
     flag = _colour_flag(colour, nb, "batch_probe_picture_set_n")
     table = picture_set_table([p.shape[:2] for p in pics], nb, bs, n)      # names the refusal, before any device is touched
@@ -2344,7 +2305,7 @@ def batch_probe_picture_set_n(pictures, bs, n, mode, params, colour=None, group_
         dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
         batch_probe_picture_set_n_device(din.ptr, table, dtab.ptr, mode, h, dws.ptr, dtot.ptr, flag, group_samples)
         raw = dtot.download((len(pics), nb, nk), np.uint64)
-    return raw & np.uint64(PROBE_BAD - 1), (raw >> np.uint64(63)).astype(bool)
+    return _probe_answer(raw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2367,9 +2328,7 @@ def picture_planes_stacked_u8_device(d_pixels, npictures, nbands, rows, cols, bl
     padded raw uint8 planes stacked picture-major [npictures * nbands * H * block_size][out_pitch]."""
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(block_size), d_out, int(out_pitch), stream)
-    L = lib()
-    check(L.jpegx_picture_planes_stacked_u8(*args) if device is None else L.jpegx_picture_planes_stacked_u8_on(int(device), *args),
-          "jpegx_picture_planes_stacked_u8")
+    _entry_checked("jpegx_picture_planes_stacked_u8", device, *args)
 
 
 def picture_planes_stacked_u8(pixels, block_size=1, colour=None):
@@ -2400,9 +2359,7 @@ def batch_compress_pictures_device(d_pixels, npictures, nbands, rows, cols, bloc
     of padded_shape(rows, cols, block_size)."""
     args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
             int(block_size), mode_of(mode), float(param), int(group_planes), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress_pictures(*args) if device is None else L.jpegx_batch_compress_pictures_on(int(device), *args),
-          "jpegx_batch_compress_pictures")
+    _entry_checked("jpegx_batch_compress_pictures", device, *args)
 
 
 def batch_decompress_pictures_device(d_bytes, plane_offsets, npictures, nbands, rows, cols, block_size, d_workspace, d_out,
@@ -2410,14 +2367,10 @@ def batch_decompress_pictures_device(d_bytes, plane_offsets, npictures, nbands, 
     """jpegx_batch_decompress_pictures (synchronises the stream between groups and levels); plane_offsets: nbands * npictures + 1
     host integers; pictures stacked [npictures * rows][out_pitch] (default cols * nbands) at d_out.  Raises JpegxError for
     whatever the entry refuses; d_out is untouched then."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (int(npictures) * int(nbands) + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, int(npictures) * int(nbands), "nbands * npictures")
     args = (d_bytes, off.ctypes.data, int(npictures), int(nbands), int(rows), int(cols), int(block_size), mode_of(mode), float(param),
             int(colour), d_workspace, d_out, int(cols * nbands if out_pitch is None else out_pitch), stream)
-    L = lib()
-    check(L.jpegx_batch_decompress_pictures(*args) if device is None else L.jpegx_batch_decompress_pictures_on(int(device), *args),
-          "jpegx_batch_decompress_pictures")
+    _entry_checked("jpegx_batch_decompress_pictures", device, *args)
 
 
 def batch_compress_pictures(pixels, block_size=1, mode="qtable", param=0.0, colour=None, group_planes=None):
@@ -2425,10 +2378,7 @@ def batch_compress_pictures(pixels, block_size=1, mode="qtable", param=0.0, colo
     ragged=True) gives for that band of that picture (with colour='rgb': of the picture's Pillow YCbCr).  Host convenience over
     the device entries (upload, sizes-only compress, status, emit into a buffer of exactly the total, download).  group_planes
     None: the recommended value.  JpegxError naming BadRleCodeError for an amplitude beyond 15 bits anywhere in the batch."""
-    src = pixels if isinstance(pixels, np.ndarray) else np.asarray(pixels)
-    if src.ndim != 4 or src.size == 0 or src.dtype != np.uint8:
-        raise JpegxError("expected non-empty [n][rows][cols][bands] uint8 pictures, got %r of %s" % (src.shape, src.dtype))
-    src = np.ascontiguousarray(src)
+    src = _picture_stack(pixels)
     k, rows, cols, nb = src.shape
     bs = int(block_size)
     flag = _colour_flag(colour, nb, "batch_compress_pictures")
@@ -2446,33 +2396,20 @@ def batch_compress_pictures(pixels, block_size=1, mode="qtable", param=0.0, colo
         din, dws = dev(src.nbytes), dev(nws)
         din.upload(src)
         batch_compress_pictures_device(din.ptr, *pics, dws.ptr, None, 0, group_planes, mode, param, flag)
-        rc, total, off = batch_compress_status(dws.ptr, *planes)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status")
-        dout = dev(max(1, total))
-        batch_emit_device(dws.ptr, *planes, dout.ptr, total)
-        rc, total2, off = batch_compress_status(dws.ptr, *planes)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit")
-        blob = dout.download((total,), np.uint8)
-        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(k)]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status(dws.ptr, *planes),
+                                  lambda d_out, cap: batch_emit_device(dws.ptr, *planes, d_out, cap), "jpegx_batch_emit")
+        return _cut_blobs(blob, off, k, nb)
 
 
 def batch_decompress_pictures(blobs, rows, cols, block_size=1, mode="qtable", param=0.0, colour=None):
     """k lists of nb byte strings (as batch_compress_pictures returns them) -> uint8 [k][rows][cols][nb], picture p the np.dstack
     of its decoded bands cropped to rows x cols (with colour='rgb': Pillow's RGB of that).  JpegxError naming a plane range for a
     stream the device refuses."""
-    blobs = [[bytes(b) for b in picture] for picture in blobs]
-    k = len(blobs)
-    nb = len(blobs[0]) if k else 0
-    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs):
-        raise JpegxError("expected at least one picture, and the same number of bands in each")
+    blobs, k, nb = _picture_blobs(blobs)
     flag = _colour_flag(colour, nb, "batch_decompress_pictures")
     rows, cols = int(rows), int(cols)
     flat = [b for picture in blobs for b in picture]
-    off = np.zeros(k * nb + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in flat])
-    total = int(off[-1])
+    off, total = _blob_offsets(flat)
     pics = (k, nb, rows, cols, int(block_size))
     nws = batch_decompress_pictures_workspace_bytes(max(total, 1), *pics)
     if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
@@ -2508,9 +2445,7 @@ def batch_decompress_set_workspace_bytes(nbytes, table, group_samples=0):
 def batch_groups_set(plane_offsets, table, group_samples=0):
     """The cut of a coded set into decoding groups on picture boundaries (jpegx_batch_groups_set; host arithmetic): the first
     PICTURE of every group and, last, npictures."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (table.npictures * table.nbands + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, table.npictures * table.nbands, "nbands * npictures")
     first = np.zeros(table.npictures + 1, dtype=np.int32)
     ngroups = ctypes.c_int(0)
     check(lib().jpegx_batch_groups_set(off.ctypes.data, table.ptr, int(group_samples), first.ctypes.data, ctypes.byref(ngroups)),
@@ -2530,9 +2465,7 @@ def picture_set_strip_bytes_u8(table, p0=0, k=None):
 def picture_set_blocks_u8_device(d_pixels, table, d_table, p0, k, d_strip, colour=0, stream=None, device=None):
     """Enqueue jpegx_picture_set_blocks_u8: pixels of pictures p0 .. p0 + k - 1 -> their raw uint8 block strip at d_strip."""
     args = (d_pixels, table.ptr, d_table, int(p0), int(k), int(colour), d_strip, stream)
-    L = lib()
-    check(L.jpegx_picture_set_blocks_u8(*args) if device is None else L.jpegx_picture_set_blocks_u8_on(int(device), *args),
-          "jpegx_picture_set_blocks_u8")
+    _entry_checked("jpegx_picture_set_blocks_u8", device, *args)
 
 
 def picture_set_blocks_u8(pictures, block_size=1, colour=None):
@@ -2563,49 +2496,34 @@ def batch_compress_picture_set_device(d_pixels, table, d_table, d_workspace, d_o
     """Enqueue jpegx_batch_compress_picture_set -> coded bytes at d_out (None: sizes only).  Verdict and plane index:
     batch_compress_status_set."""
     args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), float(param), int(group_samples), d_workspace, d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_compress_picture_set(*args) if device is None else L.jpegx_batch_compress_picture_set_on(int(device), *args),
-          "jpegx_batch_compress_picture_set")
+    _entry_checked("jpegx_batch_compress_picture_set", device, *args)
 
 
 def batch_compress_status_set(d_workspace, table, group_samples=0, stream=None, device=None):
     """Synchronises; returns (rc, total, offsets) as batch_compress_status does."""
-    total = ctypes.c_ulonglong(0)
-    off = np.zeros(table.npictures * table.nbands + 1, dtype=np.uint64)
-    args = (d_workspace, table.ptr, int(group_samples), ctypes.byref(total), off.ctypes.data, stream)
-    L = lib()
-    rc = L.jpegx_batch_compress_status_set(*args) if device is None else L.jpegx_batch_compress_status_set_on(int(device), *args)
-    if rc not in (0, 1, -1):
-        check(rc, "jpegx_batch_compress_status_set")
-    return rc, total.value, off
+    return _compress_status("jpegx_batch_compress_status_set", device, table.npictures * table.nbands,
+                            (d_workspace, table.ptr, int(group_samples)), stream)
 
 
 def batch_emit_set_device(d_workspace, table, d_table, d_out, out_cap, group_samples=0, stream=None, device=None):
     args = (d_workspace, table.ptr, d_table, int(group_samples), d_out, int(out_cap), stream)
-    L = lib()
-    check(L.jpegx_batch_emit_set(*args) if device is None else L.jpegx_batch_emit_set_on(int(device), *args), "jpegx_batch_emit_set")
+    _entry_checked("jpegx_batch_emit_set", device, *args)
 
 
 def batch_decompress_picture_set_device(d_bytes, plane_offsets, table, d_table, d_workspace, d_out, mode="qtable", param=0.0, colour=0,
                                         group_samples=0, stream=None, device=None):
     """jpegx_batch_decompress_picture_set (synchronises the stream per group and level); plane_offsets: nbands * npictures + 1
     host integers; every picture at its offset and pitch in d_out.  Raises JpegxError for whatever the entry refuses."""
-    off = np.ascontiguousarray(plane_offsets, dtype=np.uint64)
-    if off.shape != (table.npictures * table.nbands + 1,):
-        raise JpegxError("plane_offsets must hold nbands * npictures + 1 entries")
+    off = _plane_offsets(plane_offsets, table.npictures * table.nbands, "nbands * npictures")
     args = (d_bytes, off.ctypes.data, table.ptr, d_table, mode_of(mode), float(param), int(colour), int(group_samples), d_workspace, d_out, stream)
-    L = lib()
-    check(L.jpegx_batch_decompress_picture_set(*args) if device is None else L.jpegx_batch_decompress_picture_set_on(int(device), *args),
-          "jpegx_batch_decompress_picture_set")
+    _entry_checked("jpegx_batch_decompress_picture_set", device, *args)
 
 
 def batch_compress_picture_set(pictures, block_size=1, mode="qtable", param=0.0, colour=None, group_samples=0):
     """A sequence of uint8 pictures [rows_p][cols_p][nb], sizes as they come -> per picture the list of its nb bands' bytes, each
     what compress_plane_native(band, ragged=True) gives for that band of that picture (with colour='rgb': of the picture's
     Pillow YCbCr).  Host convenience over the device entries, as batch_compress_picture_set_n."""
-    pics = [p if isinstance(p, np.ndarray) else np.asarray(p) for p in pictures]
-    if not pics or any(p.ndim != 3 or p.size == 0 or p.dtype != np.uint8 for p in pics) or len({p.shape[2] for p in pics}) != 1:
-        raise JpegxError("expected at least one non-empty [rows][cols][bands] uint8 picture, and the same number of bands in each")
+    pics = _picture_list(pictures)
     nb = pics[0].shape[2]
     flag = _colour_flag(colour, nb, "batch_compress_picture_set")
     table = picture_set_table([p.shape[:2] for p in pics], nb, block_size, 8)      # names the refusal, before any device is touched
@@ -2621,35 +2539,22 @@ def batch_compress_picture_set(pictures, block_size=1, mode="qtable", param=0.0,
         din.upload(flat)
         dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
         batch_compress_picture_set_device(din.ptr, table, dtab.ptr, dws.ptr, None, 0, mode, param, flag, group_samples)
-        rc, total, off = batch_compress_status_set(dws.ptr, table, group_samples)
-        if rc != 0:
-            check(rc, "jpegx_batch_compress_status_set")
-        dout = dev(max(1, total))
-        batch_emit_set_device(dws.ptr, table, dtab.ptr, dout.ptr, total, group_samples)
-        rc, total2, off = batch_compress_status_set(dws.ptr, table, group_samples)
-        if rc != 0 or total2 != total:
-            check(rc if rc else -1, "jpegx_batch_emit_set")
-        blob = dout.download((total,), np.uint8)
-        return [[blob[int(off[p * nb + b]):int(off[p * nb + b + 1])].tobytes() for b in range(nb)] for p in range(len(pics))]
+        blob, off = _emit_exactly(dev, lambda: batch_compress_status_set(dws.ptr, table, group_samples),
+                                  lambda d_out, cap: batch_emit_set_device(dws.ptr, table, dtab.ptr, d_out, cap, group_samples), "jpegx_batch_emit_set")
+        return _cut_blobs(blob, off, len(pics), nb)
 
 
 def batch_decompress_picture_set(blobs, sizes, block_size=1, mode="qtable", param=0.0, colour=None, group_samples=0):
     """k lists of nb byte strings (as batch_compress_picture_set returns them) and the k (rows, cols) -> a list of uint8 arrays
     [rows_p][cols_p][nb], picture p the np.dstack of its decoded bands cropped to its size (with colour='rgb': Pillow's RGB of
     that).  JpegxError naming a picture range for a stream the device refuses."""
-    blobs = [[bytes(b) for b in picture] for picture in blobs]
     sizes = [(int(r), int(c)) for r, c in sizes]
-    k = len(blobs)
-    nb = len(blobs[0]) if k else 0
-    if k < 1 or nb < 1 or any(len(picture) != nb for picture in blobs) or len(sizes) != k:
-        raise JpegxError("expected at least one picture, the same number of bands in each, and a size for each")
+    blobs, k, nb = _picture_blobs(blobs, sizes)
     flag = _colour_flag(colour, nb, "batch_decompress_picture_set")
     table = picture_set_table(sizes, nb, block_size, 8)
     mode_of(mode)
     flat = [b for picture in blobs for b in picture]
-    off = np.zeros(k * nb + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(b) for b in flat])
-    total = int(off[-1])
+    off, total = _blob_offsets(flat)
     nws = batch_decompress_set_workspace_bytes(max(total, 1), table, group_samples)
     if nws == 0 or total == 0:                          # the entry names the refusal, before any device is touched
         batch_decompress_picture_set_device(1, off, table, 8, 256, 1, mode, param, flag, group_samples)
