@@ -269,7 +269,9 @@ def test_rle_decoder_on_every_golden_stream(golden, case):
 
 
 def test_rle_decoder_fails_where_the_reference_does():
-    """Error behaviour read off the reference's code (it cannot be run: bitarray): int('', 2) for a code of size 1 and
+    """Error behaviour first read off the reference's code, and since tests/golden/streams_rle.npz also recorded from the
+    reference itself running under tests/bitarray_standin.py (the loop at the end; tests/test_reference_streams.py has
+    every recorded stream as a case of its own): int('', 2) for a code of size 1 and
     for the headers (1..14, 0); reshape for a wrong number of values.  And what it lets pass: codes behind the last end
     marker (an unfinished block is never yielded, run_length_encoding.py:91-97), damaged padding bits (stepped over
     unread, rle_byte_stream.py:26-28), a block longer than 64 values as long as the TOTAL fits (run_length_encoding.py:
@@ -303,6 +305,18 @@ def test_rle_decoder_fails_where_the_reference_does():
     long_block = [(15, 0, 0)] * 8 + [(7, 2, 1), (0, 0)]
     got = oracle.rle_tuples_decode(long_block, 2)
     assert got.shape == (2, 64) and got[1, 63] == 1 and np.count_nonzero(got) == 1
+    # the same classes as the reference itself ended them: size 1, a header (5, 0), 65 and 75 values for one block, 128 for
+    # two, a block too many, set padding bits, a cut stream
+    import reference_streams
+    recorded = {name: (n, nblocks, blob, outcome, back) for name, n, nblocks, blob, outcome, back in reference_streams.damaged()}
+    for name in ("size1_one", "size1_zero", "run5_size0", "values65_one_block", "zeros75", "one_block_too_many", "corner8_cut7"):
+        n, nblocks, blob, outcome, _ = recorded[name]
+        assert outcome == "ValueError", name
+        with pytest.raises(oracle.RleStreamError):
+            oracle.rle_decode(blob, nblocks, n * n)
+    for name in ("values128_for_two_blocks", "padding_bits_set", "trailing_chain"):
+        n, nblocks, blob, outcome, back = recorded[name]
+        assert outcome == "array" and np.array_equal(oracle.rle_decode(blob, nblocks, n * n), back), name
 
 
 def test_host_mirror_decoder_against_the_oracle_on_damaged_streams():
