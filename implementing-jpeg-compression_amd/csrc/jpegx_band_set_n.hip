@@ -101,6 +101,79 @@ __global__ __launch_bounds__(256) void k_picture_set_blocks_n(const uint8_t *__r
     }
 }
 
+// The moments of the same tiles, for the distortion probe over a set (jpegx_distort_n.hip): k_band_moments_packed_stacked_n's
+// contract (jpegx_band_n.hip) with the gather's addressing.  Item, lane, block order and element order are the gather's; the word
+// of a sample is S2 << 32 | S1 over the LIVE pixels of its bs x bs tile -- rows y * bs .. min((y + 1) * bs, rows) - 1 of the
+// picture, columns likewise --, 0 for a sample of either padding.  Only live pixels are read, so no read leaves [rows] x
+// [cols * NB] bytes of the picture's rows; writes stay inside the k pictures' blocks.
+template <int NB, bool COLOUR, int VEC>
+__global__ __launch_bounds__(256) void k_picture_set_moments_n(const uint8_t *__restrict__ px, const Entry *__restrict__ e, int k, int bs, int N,
+                                                               unsigned ipb, unsigned long long items, unsigned long long *__restrict__ out)
+{
+    static_assert(!COLOUR || NB == 3, "the colour conversion is for three bands");
+    __shared__ __attribute__((aligned(16))) int16_t t[COLOUR ? FWD_TABLES * 256 : 8];
+    __shared__ unsigned long long pre[SET_LDS_PICTURES + 1];
+    if (COLOUR) fill_colour_tables<false>(t);
+    fill_prefix<false>(pre, e, k, NB);
+    __syncthreads();
+    const size_t nn = (size_t)N * N;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < items; i += (unsigned long long)gridDim.x * 256u) {
+        const unsigned long long pos = i / ipb;                              // block position among the k pictures'
+        const unsigned el = (unsigned)(i - pos * ipb) * VEC;                 // first element of the lane inside the block
+        unsigned long long start;
+        const int q = find_picture<false>(pre, e, k, NB, pos, &start);
+        const Entry pic = e[q];
+        const unsigned b = (unsigned)(pos - start);                          // block of the band, row-major
+        const unsigned by = b / (unsigned)pic.wb, bx = b - by * (unsigned)pic.wb;
+        const unsigned bi = el / (unsigned)N, bj = el - bi * (unsigned)N;
+        const long long r0 = (long long)(by * N + bi) * bs;
+        const int nr = r0 < pic.rows ? (int)min((long long)bs, pic.rows - r0) : 0;
+        const uint8_t *base = px + pic.offset;
+        unsigned long long word[VEC][NB];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            unsigned s1[NB], s2[NB];
+#pragma unroll
+            for (int c = 0; c < NB; ++c) s1[c] = s2[c] = 0;
+            const long long c0 = (long long)(bx * N + bj + v) * bs;
+            const int nc = c0 < pic.cols ? (int)min((long long)bs, pic.cols - c0) : 0;
+            if (nc > 0) {
+                for (int u = 0; u < nr; ++u) {
+                    const uint8_t *row = base + (size_t)(r0 + u) * (size_t)pic.pitch + (size_t)c0 * NB;
+                    for (int w = 0; w < nc; ++w) {
+                        unsigned p[NB];
+#pragma unroll
+                        for (int c = 0; c < NB; ++c) p[c] = row[w * NB + c];
+                        if (COLOUR) {
+                            unsigned o0, o1, o2;
+                            colour_forward_px(t, p[0], p[1 % NB], p[2 % NB], o0, o1, o2);
+                            p[0] = o0; p[1 % NB] = o1; p[2 % NB] = o2;
+                        }
+#pragma unroll
+                        for (int c = 0; c < NB; ++c) {
+                            s1[c] += p[c];
+                            s2[c] += p[c] * p[c];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NB; ++c) word[v][c] = ((unsigned long long)s2[c] << 32) | s1[c];
+        }
+        const size_t g0 = (size_t)(pic.first - e[0].first) + b;              // the block in band 0
+#pragma unroll
+        for (int c = 0; c < NB; ++c) {
+            unsigned long long *dst = out + (g0 + (size_t)c * (unsigned)pic.nb) * nn + el;
+            if (VEC == 1) {
+                dst[0] = word[0][c];
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; v += 2) reinterpret_cast<ulonglong2 *>(dst)[v / 2] = make_ulonglong2(word[v][c], word[(v + 1) % VEC][c]);
+            }
+        }
+    }
+}
+
 // The scatter.  Item = lane of k_inflate_crop_pack_stacked_u8: PIX consecutive pixels of one output row, whole 16-byte units.
 // Source sample (y / bs, x / bs) of plane (q, c) lies in block (sy / N) * wb + sx / N of the plane at element (sy % N) * N + sx % N;
 // a (block column, column inside the block) pair is stepped with the (quotient, remainder) pair of x / bs.  sy <= (rows - 1) / bs < H
@@ -186,6 +259,22 @@ void launch_blocks(const uint8_t *px, const Entry *e, int k, int bs, int N, unsi
 }
 
 template <int NB, bool COLOUR>
+void launch_moments(const uint8_t *px, const Entry *e, int k, int bs, int N, unsigned long long positions, unsigned long long *out, hipStream_t st)
+{
+    const unsigned nn = (unsigned)(N * N);
+    if (N % 4 == 0) {
+        const unsigned long long items = positions * (nn / 4);
+        hipLaunchKernelGGL((k_picture_set_moments_n<NB, COLOUR, 4>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn / 4, items, out);
+    } else if (N % 2 == 0) {
+        const unsigned long long items = positions * (nn / 2);
+        hipLaunchKernelGGL((k_picture_set_moments_n<NB, COLOUR, 2>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn / 2, items, out);
+    } else {
+        const unsigned long long items = positions * nn;
+        hipLaunchKernelGGL((k_picture_set_moments_n<NB, COLOUR, 1>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, px, e, k, bs, N, nn, items, out);
+    }
+}
+
+template <int NB, bool COLOUR>
 void launch_pixels(const uint8_t *strip, const Entry *e, int k, int bs, int N, unsigned long long items, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL((k_picture_set_pixels_u8<NB, COLOUR>), dim3(set_blocks<COLOUR>(items)), dim3(256), 0, st, strip, e, k, (unsigned)bs, N, items, out);
@@ -212,6 +301,28 @@ int jpegx_picture_set_blocks_n(const uint8_t *d_pixels, const void *h_table, con
     case 2: launch_blocks<2, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
     case 3: launch_blocks<3, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
     default: launch_blocks<4, false>(d_pixels, de, k, h->bs, h->N, positions, d_strip, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
+}
+
+int jpegx_picture_set_moments_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour,
+                                unsigned long long *d_moments, jpegx_stream_t stream)
+{
+    const Head *h = nullptr;
+    const int rc = check_range("picture_set_moments_n", d_pixels, h_table, d_table, p0, k, colour, d_moments, &h);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_moments) % 16) return fail(JPEGX_E_INVALID, "picture_set_moments_n: the moments strip must be 16-byte aligned");
+    const Entry *he = reinterpret_cast<const Entry *>(h + 1) + p0;
+    const Entry *de = reinterpret_cast<const Entry *>(static_cast<const unsigned char *>(d_table) + sizeof(Head)) + p0;
+    const unsigned long long positions = (unsigned long long)(he[k].first - he[0].first) / (unsigned)h->nbands;   // * N * N <= 2^31 - 1: the table's limit
+    hipStream_t st = (hipStream_t)stream;
+    if (colour) launch_moments<3, true>(d_pixels, de, k, h->bs, h->N, positions, d_moments, st);
+    else switch (h->nbands) {
+    case 1: launch_moments<1, false>(d_pixels, de, k, h->bs, h->N, positions, d_moments, st); break;
+    case 2: launch_moments<2, false>(d_pixels, de, k, h->bs, h->N, positions, d_moments, st); break;
+    case 3: launch_moments<3, false>(d_pixels, de, k, h->bs, h->N, positions, d_moments, st); break;
+    default: launch_moments<4, false>(d_pixels, de, k, h->bs, h->N, positions, d_moments, st); break;
     }
     HIP_TRY(hipGetLastError());
     return JPEGX_OK;

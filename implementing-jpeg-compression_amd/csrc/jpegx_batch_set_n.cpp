@@ -226,6 +226,36 @@ int jpegx_batch_probe_picture_set_n(const uint8_t *d_pixels, const void *h_table
     });
 }
 
+// ---- the distortion probe over a set (jpegx_distort_n.hip): one group's float64 strip and one group's moments --------------
+size_t jpegx_batch_probe_distortion_picture_set_workspace_bytes_n(const void *h_table, long long group_samples)
+{
+    Set s;
+    if (open_set("batch_probe_distortion_picture_set_n", h_table, group_samples, false, &s)) return 0;
+    return 2 * up256((size_t)group_samples_max(s) * 8);
+}
+
+int jpegx_batch_probe_distortion_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
+                                               const double *h_params, int K, long long group_samples, void *d_workspace,
+                                               unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const char *who = "batch_probe_distortion_picture_set_n";
+    if (!d_pixels || !h_table || !d_table || !d_workspace || !d_totals) return fail(JPEGX_E_INVALID, "batch_probe_distortion_picture_set_n: null pointer");
+    Set s;
+    int rc = open_set(who, h_table, group_samples, false, &s);
+    if (rc || (rc = check_colour(who, s.nbands, colour)) || (rc = jpegx_internal_probe_check_params(who, mode, h_params, K))) return rc;
+    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_probe_distortion_picture_set_n: workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_table) % 8) return fail(JPEGX_E_INVALID, "batch_probe_distortion_picture_set_n: d_table must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_totals) % 8) return fail(JPEGX_E_INVALID, "batch_probe_distortion_picture_set_n: d_totals must be 8-byte aligned");
+    double *strip = static_cast<double *>(d_workspace);
+    unsigned long long *moments =
+        reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(d_workspace) + up256((size_t)group_samples_max(s) * 8));
+    return for_each_group(cut_by_samples(s), [&](int p0, int k) {
+        int rc = jpegx_picture_set_blocks_n(d_pixels, h_table, d_table, p0, k, colour, strip, stream);
+        if (rc || (rc = jpegx_picture_set_moments_n(d_pixels, h_table, d_table, p0, k, colour, moments, stream))) return rc;
+        return jpegx_probe_distortion_set_n(strip, moments, h_table, d_table, p0, k, mode, h_params, K, d_totals + (size_t)p0 * s.nbands * K, stream);
+    });
+}
+
 size_t jpegx_batch_decompress_set_workspace_bytes_n(size_t nbytes, const void *h_table, long long group_samples)
 {
     Set s;

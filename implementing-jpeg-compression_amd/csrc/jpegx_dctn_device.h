@@ -1,5 +1,6 @@
 // jpegx_dctn_device.h -- what the run-time-N kernels share (jpegx_dctn.hip: forward and inverse; jpegx_probe_n.hip: the size
-// probe): the decomposition of a launch, the quantiser and the lane mapping between a plane and the workgroup's blocks.
+// probe; jpegx_distort_n.hip: the distortion probe): the decomposition of a launch, the quantiser, the lane mapping between a
+// plane and the workgroup's blocks, and the plane of a block among ragged planes.
 // One copy, so that the integers of the probe ARE the forward kernel's.  Needs JPEGX_QM_* (jpegx_math.h, through
 // jpegx_internal.h) in front of it.
 #ifndef JPEGX_DCTN_DEVICE_H
@@ -51,6 +52,19 @@ __device__ inline PlaneSpot plane_spot(int e, int N, int bpw, long long first, i
     const long long by = g / wb, bx = g - by * wb;
     s.glob = (size_t)(by * N + i) * pitch + (size_t)bx * N + j;
     return s;
+}
+
+// the plane of block g among nplanes planes whose first blocks are pf[0] < pf[1] < ... < pf[nplanes] = pf[0] + nblk: the p
+// with pf[p] - pf[0] <= g < pf[p + 1] - pf[0], for 0 <= g < nblk
+__device__ inline int plane_of_block(const long long *__restrict__ pf, int nplanes, long long g)
+{
+    const long long v = g + pf[0];
+    int lo = 0, hi = nplanes;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pf[mid] <= v) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 }  // namespace

@@ -24,8 +24,15 @@
 // that spans planes adds lane by lane.  What does not depend on the candidate -- an element's block, row and column, its
 // moments and its live-pixel count -- is worked out once per turn and kept in registers (an element index e = (b * N + i1) * N
 // + i2 is the same in the restore, the column and the row pass; a thread owns at most four).
+//
+// Bands of unequal sizes (jpegx_probe_distortion_set_n: the block strip of a set of pictures and its moments,
+// jpegx_band_set_n.hip) go through the same kernel as k_distort_n<true>.  Two things differ: which plane a block belongs to --
+// looked up as k_probe_n<true> does, once per turn and block, the results in LDS (rowtab) -- and where the block lies in its band
+// and how large the band is, which the threads of that search take from the picture's entry of the table and leave in LDS as a
+// small record per block.  The candidate loop is the same lines.
 #include "jpegx_internal.h"
 #include "jpegx_dctn_device.h"
+#include "jpegx_picture_set_device.h"      // check_range and the table's views, for the ragged entry
 
 namespace {
 
@@ -33,6 +40,7 @@ constexpr int DISTORT_MAX_K = JPEGX_PROBE_MAX_CANDIDATES;
 constexpr int DISTORT_MAX_WORKGROUPS = 8192;            // k_probe_n's: 256 CUs x 8 resident workgroups x 4 runs each
 constexpr int DISTORT_OWN = DCTN_MAX * DCTN_MAX / DCTN_THREADS;      // elements of a turn a thread owns at most: 4
 constexpr unsigned long long DISTORT_BAD = 1ull << 63;
+constexpr int DISTORT_REC = 5;                           // RAGGED: ints of a block's record (plane, by, bx, rows, cols)
 
 // the candidates, by value in the kernarg segment: read with scalar loads at a wave-uniform index
 struct DistortParams {
@@ -53,10 +61,16 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
     return v;
 }
 
+// RAGGED: the planes' block counts and their bands' sizes differ (jpegx_probe_distortion_set_n: the block strip of a set of
+// pictures).  sh.bpp then holds the PLANE COUNT, sh.wb is 1 (the strip is a plane of width N), sh.rows and sh.cols are not read;
+// pf points at the first plane's entry of the table's device array of first blocks, ent at the first picture's entry, planes
+// are picture-major with nbands planes a picture.  Without RAGGED pf, ent and nbands are not read.
+template <bool RAGGED>
 __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__restrict__ in, size_t pitch, const unsigned long long *__restrict__ mom,
                                                            size_t mpitch, int N, DistortShape sh, const double *__restrict__ g_ct,
                                                            const double *__restrict__ g_cn, const double *__restrict__ g_dinv, int mode, int K,
-                                                           DistortParams pp, int nturns, int run, unsigned long long *__restrict__ totals)
+                                                           DistortParams pp, int nturns, int run, unsigned long long *__restrict__ totals,
+                                                           const long long *__restrict__ pf, const Entry *__restrict__ ent, int nbands)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int nn = N * N, bpw = dctn_blocks_per_wg(N), nelem = bpw * nn;
@@ -68,6 +82,10 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
     double *M = B + nelem;         // [b][.][.]: after the first pass of either direction
     unsigned long long *Mo = reinterpret_cast<unsigned long long *>(M + nelem);       // [b][i][j]: the samples' moments
     unsigned long long *acc = Mo + nelem;                                              // [plane - first plane of the turn][K]
+    // RAGGED: rowtab[b] = the plane of the turn's block b, rowtab[bpw] = the plane of the next turn's first block (-1: none);
+    // rec[b] = the record of the turn's block b, written for the blocks that exist only
+    int *rowtab = reinterpret_cast<int *>(acc + bpw * K);
+    int *rec = rowtab + bpw + 2;
     const int tid = threadIdx.x;
 
     for (int e = tid; e < nn; e += DCTN_THREADS) {
@@ -81,8 +99,26 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
     for (int turn = turn0; turn < turn1; ++turn) {
         const long long first = (long long)turn * bpw;
         const int nlive = (int)min((long long)bpw, (long long)sh.nblk - first);
-        const int plane0 = (int)(first / sh.bpp);
+        int plane0 = RAGGED ? 0 : (int)(first / sh.bpp);
         __syncthreads();                                       // the tables; the turn before is done with A, M, Mo and acc's rows
+        if (RAGGED && tid <= bpw) {
+            const long long g = first + tid;
+            int p = -1;
+            if (g < sh.nblk) {
+                p = plane_of_block(pf, sh.bpp, g);
+                if (tid < bpw) {                               // the block's place in its band, and the band: the picture's entry
+                    const Entry *pic = ent + p / nbands;
+                    const int gp = (int)(g - (pf[p] - pf[0])), wb = pic->wb, by = gp / wb;
+                    int *r = rec + tid * DISTORT_REC;
+                    r[0] = p;
+                    r[1] = by;
+                    r[2] = gp - by * wb;
+                    r[3] = pic->rows;
+                    r[4] = pic->cols;
+                }
+            }
+            rowtab[tid] = p;
+        }
         for (int e = tid; e < nelem; e += DCTN_THREADS) {
             const PlaneSpot s = plane_spot(e, N, bpw, first, sh.wb, sh.nblk, pitch);
             A[s.lds] = s.live ? in[s.glob] : 0.0;
@@ -95,6 +131,20 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
         int base[DISTORT_OWN], i1[DISTORT_OWN], i2[DISTORT_OWN];
         unsigned s1[DISTORT_OWN], s2[DISTORT_OWN], cnt[DISTORT_OWN];
         int myrow = -1;                                        // acc's row of the thread's block(s): one block when bpw > 1, one plane otherwise
+        // RAGGED: a thread's elements lie in ONE block (bpw > 1: it owns one element; bpw == 1: block 0), so its record is read once
+        int rplane = 0, rby = 0, rbx = 0, rrows = 0, rcols = 0;
+        if (RAGGED) {
+            plane0 = __builtin_amdgcn_readfirstlane(rowtab[0]);       // one value for the workgroup: keep it scalar
+            const int b0 = bpw > 1 ? tid / nn : 0;
+            if (b0 < nlive) {                                  // the record of a block that does not exist is never read
+                const int *r = rec + b0 * DISTORT_REC;
+                rplane = r[0];
+                rby = r[1];
+                rbx = r[2];
+                rrows = r[3];
+                rcols = r[4];
+            }
+        }
 #pragma unroll
         for (int it = 0; it < DISTORT_OWN; ++it) {
             const int e = tid + it * DCTN_THREADS;
@@ -107,15 +157,27 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
             i2[it] = r - i1[it] * N;
             const long long g = first + b;
             if (g >= sh.nblk) continue;                        // no such block: its samples are zeros, its term is 0
-            const int gp = (int)(g % sh.bpp), by = gp / sh.wb, bx = gp - by * sh.wb;
+            int by, bx, rows, cols;
+            if (RAGGED) {
+                by = rby;
+                bx = rbx;
+                rows = rrows;
+                cols = rcols;
+            } else {
+                const int gp = (int)(g % sh.bpp);
+                by = gp / sh.wb;
+                bx = gp - by * sh.wb;
+                rows = sh.rows;
+                cols = sh.cols;
+            }
             const long long py = (long long)(by * N + i1[it]) * sh.bs, px = (long long)(bx * N + i2[it]) * sh.bs;
-            const int ch = py < sh.rows ? (int)min((long long)sh.bs, sh.rows - py) : 0;
-            const int cw = px < sh.cols ? (int)min((long long)sh.bs, sh.cols - px) : 0;
+            const int ch = py < rows ? (int)min((long long)sh.bs, rows - py) : 0;
+            const int cw = px < cols ? (int)min((long long)sh.bs, cols - px) : 0;
             const unsigned long long word = Mo[e];
             s1[it] = (unsigned)word;
             s2[it] = (unsigned)(word >> 32);
             cnt[it] = (unsigned)(ch * cw);
-            myrow = (int)(g / sh.bpp) - plane0;
+            myrow = (RAGGED ? rplane : (int)(g / sh.bpp)) - plane0;
         }
 
         for (int e = tid; e < nelem; e += DCTN_THREADS) {          // rows: e = (b * N + i) * N + k
@@ -187,9 +249,9 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
 
         // the sums leave when the run leaves the turn's first plane or ends; otherwise the turn lay inside one plane and its
         // row 0 is the next turn's row 0
-        const bool leave = turn + 1 == turn1 || (int)(((long long)(turn + 1) * bpw) / sh.bpp) != plane0;
+        const bool leave = turn + 1 == turn1 || (RAGGED ? rowtab[bpw] : (int)(((long long)(turn + 1) * bpw) / sh.bpp)) != plane0;
         if (leave) {
-            const int nrows = (int)((first + nlive - 1) / sh.bpp) - plane0 + 1;
+            const int nrows = (RAGGED ? rowtab[nlive - 1] : (int)((first + nlive - 1) / sh.bpp)) - plane0 + 1;
             for (int e = tid; e < nrows * K; e += DCTN_THREADS) {
                 const unsigned long long v = acc[e];
                 if (v == 0ull) continue;
@@ -202,10 +264,51 @@ __global__ __launch_bounds__(DCTN_THREADS) void k_distort_n(const double *__rest
     }
 }
 
-size_t distort_lds_bytes(int N, int K)
+size_t distort_lds_bytes(int N, int K, bool ragged)
 {
     const size_t nn = (size_t)N * N, bpw = dctn_blocks_per_wg(N), nelem = nn * bpw;
-    return (2 * nn + N + 4 * nelem + bpw * K) * 8;
+    return (2 * nn + N + 4 * nelem + bpw * K) * 8 + (ragged ? (bpw + 2 + bpw * DISTORT_REC) * 4 : 0);
+}
+
+// the candidates as the kernel takes them (checked by jpegx_internal_probe_check_params)
+DistortParams distort_params(int mode, const double *h_params, int K)
+{
+    DistortParams pp;
+    for (int q = 0; q < DISTORT_MAX_K; ++q) {
+        const double param = q < K && mode != JPEGX_Q_NONE ? h_params[q] : 1.0;
+        int e2 = 0;
+        const double mant = frexp(fabs(param), &e2);
+        pp.param[q] = param;
+        pp.use_mul[q] = mode == JPEGX_Q_DIVIDE && mant == 0.5;        // jpegx_forward_fused_n's rule: d = +-2^e, y * (1 / d) is y / d
+        pp.inv[q] = mode == JPEGX_Q_DIVIDE ? 1.0 / param : 1.0;
+    }
+    return pp;
+}
+
+// one memset of the totals' rows and one launch over sh.nblk blocks: planes of sh.bpp blocks each, or (pf) nplanes ragged planes
+int distort_launch(const double *d_in, size_t pitch, const unsigned long long *d_mom, size_t mpitch, int N, DistortShape sh, int nplanes,
+                   const long long *pf, const Entry *ent, int nbands, int mode, const double *h_params, int K, unsigned long long *d_totals,
+                   jpegx_stream_t stream)
+{
+    const DistortParams pp = distort_params(mode, h_params, K);
+    const double *ct = nullptr, *cn = nullptr, *dinv = nullptr;
+    const uint16_t *zig = nullptr;
+    int rc;
+    if ((rc = jpegx_internal_dctn_forward_tables(N, &ct, &zig)) || (rc = jpegx_internal_dctn_inverse_tables(N, &cn, &dinv))) return rc;
+    const int bpw = dctn_blocks_per_wg(N);
+    const int nturns = (sh.nblk + bpw - 1) / bpw;
+    const int run = (nturns + DISTORT_MAX_WORKGROUPS - 1) / DISTORT_MAX_WORKGROUPS;
+    const unsigned grid = (unsigned)((nturns + run - 1) / run);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)nplanes * K * 8, st));
+    if (pf)
+        hipLaunchKernelGGL(k_distort_n<true>, dim3(grid), dim3(DCTN_THREADS), distort_lds_bytes(N, K, true), st, d_in, pitch, d_mom, mpitch, N, sh, ct,
+                           cn, dinv, mode, K, pp, nturns, run, d_totals, pf, ent, nbands);
+    else
+        hipLaunchKernelGGL(k_distort_n<false>, dim3(grid), dim3(DCTN_THREADS), distort_lds_bytes(N, K, false), st, d_in, pitch, d_mom, mpitch, N, sh, ct,
+                           cn, dinv, mode, K, pp, nturns, run, d_totals, pf, ent, nbands);
+    HIP_TRY(hipGetLastError());
+    return JPEGX_OK;
 }
 
 int distort_fail(const char *what)
@@ -237,21 +340,9 @@ int jpegx_probe_distortion_n(const double *d_planes, const unsigned long long *d
     if ((long long)rows * cols > 0x7FFFFFFFLL) return distort_fail("rows * cols: more than 2^31 - 1 pixels in one band");
     if ((reinterpret_cast<uintptr_t>(d_planes) & 7u) || (reinterpret_cast<uintptr_t>(d_moments) & 7u) || (reinterpret_cast<uintptr_t>(d_totals) & 7u))
         return distort_fail("d_planes / d_moments / d_totals must be 8-byte aligned");
-    int rc = jpegx_internal_probe_check_params("probe_distortion_n", mode, h_params, K);
+    const int rc = jpegx_internal_probe_check_params("probe_distortion_n", mode, h_params, K);
     if (rc) return rc;
 
-    DistortParams pp;
-    for (int q = 0; q < DISTORT_MAX_K; ++q) {
-        const double param = q < K && mode != JPEGX_Q_NONE ? h_params[q] : 1.0;
-        int e2 = 0;
-        const double mant = frexp(fabs(param), &e2);
-        pp.param[q] = param;
-        pp.use_mul[q] = mode == JPEGX_Q_DIVIDE && mant == 0.5;        // jpegx_forward_fused_n's rule: d = +-2^e, y * (1 / d) is y / d
-        pp.inv[q] = mode == JPEGX_Q_DIVIDE ? 1.0 / param : 1.0;
-    }
-    const double *ct = nullptr, *cn = nullptr, *dinv = nullptr;
-    const uint16_t *zig = nullptr;
-    if ((rc = jpegx_internal_dctn_forward_tables(N, &ct, &zig)) || (rc = jpegx_internal_dctn_inverse_tables(N, &cn, &dinv))) return rc;
     DistortShape sh;
     sh.wb = W / N;
     sh.bpp = (H / N) * sh.wb;
@@ -259,16 +350,37 @@ int jpegx_probe_distortion_n(const double *d_planes, const unsigned long long *d
     sh.bs = bs;
     sh.rows = rows;
     sh.cols = cols;
-    const int bpw = dctn_blocks_per_wg(N);
-    const int nturns = (sh.nblk + bpw - 1) / bpw;
-    const int run = (nturns + DISTORT_MAX_WORKGROUPS - 1) / DISTORT_MAX_WORKGROUPS;
-    const unsigned grid = (unsigned)((nturns + run - 1) / run);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)nplanes * K * 8, st));
-    hipLaunchKernelGGL(k_distort_n, dim3(grid), dim3(DCTN_THREADS), distort_lds_bytes(N, K), st, d_planes, (size_t)pitch, d_moments, (size_t)mpitch, N, sh,
-                       ct, cn, dinv, mode, K, pp, nturns, run, d_totals);
-    HIP_TRY(hipGetLastError());
-    return JPEGX_OK;
+    return distort_launch(d_planes, (size_t)pitch, d_moments, (size_t)mpitch, N, sh, nplanes, nullptr, nullptr, 0, mode, h_params, K, d_totals, stream);
+}
+
+int jpegx_probe_distortion_set_n(const double *d_strip, const unsigned long long *d_moments, const void *h_table, const void *d_table, int p0, int k,
+                                 int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const char *who = "probe_distortion_set_n";
+    char buf[200];
+    const Head *h = nullptr;
+    int rc = check_range(who, d_strip, h_table, d_table, p0, k, 0, d_totals, &h);
+    if (rc) return rc;
+    snprintf(buf, sizeof(buf), "%s: h_table is not a table of jpegx_picture_set_table", who);
+    if (h->N < DCTN_MIN || h->N > DCTN_MAX || h->bs < 1 || h->bs > 255) return fail(JPEGX_E_INVALID, buf);
+    if (!d_moments) return fail(JPEGX_E_INVALID, "probe_distortion_set_n: null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_strip) & 7u) || (reinterpret_cast<uintptr_t>(d_moments) & 7u) || (reinterpret_cast<uintptr_t>(d_totals) & 7u))
+        return fail(JPEGX_E_INVALID, "probe_distortion_set_n: d_strip / d_moments / d_totals must be 8-byte aligned");
+    if ((rc = jpegx_internal_probe_check_params(who, mode, h_params, K))) return rc;
+    const Entry *he = reinterpret_cast<const Entry *>(h + 1) + p0;
+    const long long nblk = he[k].first - he[0].first;                      // nblk * N * N <= 2^31 - 1: the table's limit
+    if (nblk < 1 || nblk * h->N * h->N > 0x7FFFFFFFLL) return fail(JPEGX_E_INVALID, buf);
+    // the device views behind the head: the entries from picture p0 on, and the array of first blocks at plane (p0, 0)
+    const unsigned char *dt = static_cast<const unsigned char *>(d_table) + sizeof(Head);
+    const Entry *de = reinterpret_cast<const Entry *>(dt) + p0;
+    const long long *pf = reinterpret_cast<const long long *>(dt + ((size_t)h->npictures + 1) * sizeof(Entry)) + (size_t)p0 * h->nbands;
+    DistortShape sh;
+    sh.wb = 1;                                                             // the strip is a plane of width N
+    sh.bpp = k * h->nbands;
+    sh.nblk = (int)nblk;
+    sh.bs = h->bs;
+    sh.rows = sh.cols = 0;
+    return distort_launch(d_strip, (size_t)h->N, d_moments, (size_t)h->N, h->N, sh, k * h->nbands, pf, de, h->nbands, mode, h_params, K, d_totals, stream);
 }
 
 }  // extern "C"

@@ -44,19 +44,6 @@ struct ProbeParams {
     int use_mul[PROBE_MAX_K];
 };
 
-// the plane of block g among nplanes planes whose first blocks are pf[0] < pf[1] < ... < pf[nplanes] = pf[0] + nblk: the p
-// with pf[p] - pf[0] <= g < pf[p + 1] - pf[0], for 0 <= g < nblk
-__device__ inline int plane_of_block(const long long *__restrict__ pf, int nplanes, long long g)
-{
-    const long long v = g + pf[0];
-    int lo = 0, hi = nplanes;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pf[mid] <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // bpp: blocks per plane; nturns: ceil(nblk / bpw); run: turns per workgroup.  RAGGED: the planes' block counts differ, block g
 // belongs to plane_of_block(pf, bpp, g) -- bpp then holds the PLANE COUNT and pf points at the first plane's entry of the
 // table's device array of first blocks; without RAGGED pf is not read

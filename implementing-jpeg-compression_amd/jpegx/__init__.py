@@ -231,6 +231,10 @@ SIGNATURES = {
     "jpegx_probe_sizes_set_n": [_vp, _vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp],
     "jpegx_batch_probe_picture_set_workspace_bytes_n": [_vp, _c.c_longlong],
     "jpegx_batch_probe_picture_set_n": [_vp, _vp, _vp, _int, _int, _vp, _int, _c.c_longlong, _vp, _vp, _vp],
+    "jpegx_picture_set_moments_n": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
+    "jpegx_probe_distortion_set_n": [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp],
+    "jpegx_batch_probe_distortion_picture_set_workspace_bytes_n": [_vp, _c.c_longlong],
+    "jpegx_batch_probe_distortion_picture_set_n": [_vp, _vp, _vp, _int, _int, _vp, _int, _c.c_longlong, _vp, _vp, _vp],
     "jpegx_picture_set_blocks_u8": [_vp, _vp, _vp, _int, _int, _int, _vp, _vp],
     "jpegx_batch_set_workspace_bytes": [_vp, _c.c_longlong],
     "jpegx_batch_set_max_bytes": [_vp],
@@ -275,7 +279,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_batch_compress_picture_set", "jpegx_batch_compress_status_set", "jpegx_batch_emit_set",
               "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n",
               "jpegx_probe_sizes_set_n", "jpegx_batch_probe_picture_set_n", "jpegx_band_moments_packed_stacked_n",
-              "jpegx_probe_distortion_n", "jpegx_batch_probe_distortion_pictures_n"):
+              "jpegx_probe_distortion_n", "jpegx_batch_probe_distortion_pictures_n", "jpegx_picture_set_moments_n",
+              "jpegx_probe_distortion_set_n", "jpegx_batch_probe_distortion_picture_set_n"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -288,7 +293,8 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_set_max_bytes": _sz, "jpegx_batch_decompress_set_workspace_bytes": _sz,
             "jpegx_batch_probe_pictures_workspace_bytes_n": _sz,
             "jpegx_batch_probe_distortion_pictures_workspace_bytes_n": _sz,
-            "jpegx_batch_probe_picture_set_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_probe_picture_set_workspace_bytes_n": _sz,
+            "jpegx_batch_probe_distortion_picture_set_workspace_bytes_n": _sz}   # everything else returns int
 
 
 def lib():
@@ -2304,6 +2310,64 @@ def batch_probe_picture_set_n(pictures, bs, n, mode, params, colour=None, group_
         din.upload(flat)
         dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
         batch_probe_picture_set_n_device(din.ptr, table, dtab.ptr, mode, h, dws.ptr, dtot.ptr, flag, group_samples)
+        raw = dtot.download((len(pics), nb, nk), np.uint64)
+    return _probe_answer(raw)
+
+
+# the distortion probe over a set: the moments gathered onto the block strip, and the probe's kernel with a block's plane, its
+# place in the band and the band's size looked up in the table (csrc/jpegx_distort_n.hip, k_distort_n<true>)
+def picture_set_moments_n_device(d_pixels, table, d_table, p0, k, d_moments, colour=0, stream=None, device=None):
+    """Enqueue jpegx_picture_set_moments_n: pixels of pictures p0 .. p0 + k - 1 -> uint64 words S2 << 32 | S1 over the live pixels
+    of every sample's tile, in the block and element order of picture_set_blocks_n_device, at d_moments (16-byte aligned)."""
+    args = (d_pixels, table.ptr, d_table, int(p0), int(k), int(colour), d_moments, stream)
+    _entry_checked("jpegx_picture_set_moments_n", device, *args)
+
+
+def probe_distortion_set_n_device(d_strip, d_moments, table, d_table, p0, k, mode, params, d_totals, stream=None, device=None):
+    """Enqueue jpegx_probe_distortion_set_n: the float64 block strip of pictures p0 .. p0 + k - 1 and their moments ->
+    uint64 d_totals [k * nbands][K] in the table's plane order: bits 0..62 the band's sum of squared differences over its own
+    rows x cols pixels under candidate q, bit 63 the bad-amplitude flag.  ``params``: the K candidates (host numbers)."""
+    h, nk = _probe_params(params)
+    args = (d_strip, d_moments, table.ptr, d_table, int(p0), int(k), mode_of(mode), h.ctypes.data, nk, d_totals, stream)
+    _entry_checked("jpegx_probe_distortion_set_n", device, *args)
+
+
+def batch_probe_distortion_picture_set_workspace_bytes_n(table, group_samples=0):
+    return lib().jpegx_batch_probe_distortion_picture_set_workspace_bytes_n(table.ptr, int(group_samples))
+
+
+def batch_probe_distortion_picture_set_n_device(d_pixels, table, d_table, mode, params, d_workspace, d_totals, colour=0, group_samples=0,
+                                                stream=None, device=None):
+    """Enqueue jpegx_batch_probe_distortion_picture_set_n: every picture at its offset in d_pixels -> uint64 d_totals
+    [npictures * nbands][K] in the table's plane order."""
+    h, nk = _probe_params(params)
+    args = (d_pixels, table.ptr, d_table, int(colour), mode_of(mode), h.ctypes.data, nk, int(group_samples), d_workspace, d_totals, stream)
+    _entry_checked("jpegx_batch_probe_distortion_picture_set_n", device, *args)
+
+
+def batch_probe_distortion_picture_set_n(pictures, bs, n, mode, params, colour=None, group_samples=0):
+    """A sequence of uint8 pictures [rows_p][cols_p][nb], sizes as they come -> (sse, bad): sse uint64 [npictures][nb][K], the
+    sum over band b of picture p of (pixel - decoded pixel)^2 after batch_compress_picture_set_n and
+    batch_decompress_picture_set_n under candidate q (with colour='rgb': between the YCbCr bands); bad bool of the same shape,
+    True where that band holds an amplitude beyond 15 bits under that candidate (it cannot be coded; its sum is then
+    meaningless).  Host convenience: ONE flat upload, the probe, one download.  JpegxError for more than 32 candidates."""
+    pics = _picture_list(pictures)
+    nb = pics[0].shape[2]
+    flag = _colour_flag(colour, nb, "batch_probe_distortion_picture_set_n")
+    table = picture_set_table([p.shape[:2] for p in pics], nb, bs, n)      # names the refusal, before any device is touched
+    h, nk = _probe_params(params)
+    nws = batch_probe_distortion_picture_set_workspace_bytes_n(table, group_samples)
+    if nws == 0 or not 1 <= nk <= PROBE_MAX_CANDIDATES:     # the entry names the refusal, before any device is touched
+        batch_probe_distortion_picture_set_n_device(1, table, 8, mode, h, 16, 8, flag, group_samples)
+        raise JpegxError("batch_probe_distortion_picture_set_n: the set was refused")
+    mode_of(mode)
+    require_device()
+    flat = np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pics])
+    with _Buffers() as dev:
+        din, dtab, dws, dtot = dev(flat.nbytes), dev(table.nbytes), dev(nws), dev(len(pics) * nb * nk * 8)
+        din.upload(flat)
+        dtab.upload(table.blob.view(np.uint8)[:table.nbytes])
+        batch_probe_distortion_picture_set_n_device(din.ptr, table, dtab.ptr, mode, h, dws.ptr, dtot.ptr, flag, group_samples)
         raw = dtot.download((len(pics), nb, nk), np.uint64)
     return _probe_answer(raw)
 

@@ -1969,14 +1969,11 @@ def _probe_set_row(image, config, divisors, colour):
     return row
 
 
-def _probe_set_device(images, config, divisors, colour):
-    """{index: int64 row of sizes} of the pictures that were sized on the device as one set; empty where the gates, the
-    configuration or libjpegx say no.  The vetting is _compress_picture_set's without its size ceiling."""
-    gate, least = DCTN_PROBE_MIN_CANDIDATES, DCTN_PROBE_SET_MIN_PICTURES
-    if gate is None or least is None or len(divisors) < max(gate, 1) or len(images) < max(least, 1) \
-            or not _stock_registry() or not _device_usable():
-        return {}
-    import jpegx
+def _admitted_set(images, config, colour, least):
+    """(admitted, pixels, job) of the pictures that go to the device as one set -- admitted: (index, rows, cols) per picture,
+    pixels: their uint8 arrays, job: (block_size, dct_size, mode, param), the same for every picture -- or None where fewer
+    than ``least`` pictures are admitted or the set is too large.  The vetting is _compress_picture_set's without its size
+    ceiling; the size probe and the distortion probe over a set share it."""
     admitted, job = [], None                            # (index, rows, cols)
     for at, im in enumerate(images):
         try:
@@ -1994,15 +1991,30 @@ def _probe_set_device(images, config, divisors, colour):
         job = this                                      # (block_size, dct_size, mode, param): the same for every picture
         admitted.append((at, rows, cols))
     if len(admitted) < max(least, 1):
-        return {}
+        return None
     if 3 * sum(h * w for h, w in (_blocked_shape(rows, cols, job[0], job[1]) for _, rows, cols in admitted)) > 2 ** 31 - 1:
-        return {}
+        return None
     pixels = [_picture_pixels(images[at]) for at, _, _ in admitted]      # the costly part of the vetting: last
     keep = [k for k, p in enumerate(pixels) if p is not None]
     if len(keep) != len(pixels):
         admitted, pixels = [admitted[k] for k in keep], [pixels[k] for k in keep]
         if len(admitted) < max(least, 1):
-            return {}
+            return None
+    return admitted, pixels, job
+
+
+def _probe_set_device(images, config, divisors, colour):
+    """{index: int64 row of sizes} of the pictures that were sized on the device as one set; empty where the gates, the
+    configuration or libjpegx say no.  The vetting is _admitted_set's."""
+    gate, least = DCTN_PROBE_MIN_CANDIDATES, DCTN_PROBE_SET_MIN_PICTURES
+    if gate is None or least is None or len(divisors) < max(gate, 1) or len(images) < max(least, 1) \
+            or not _stock_registry() or not _device_usable():
+        return {}
+    import jpegx
+    vetted = _admitted_set(images, config, colour, least)
+    if vetted is None:
+        return {}
+    admitted, pixels, job = vetted
     out = np.empty((len(admitted), len(divisors)), dtype=np.int64)
     heads = {}                                           # (rows, cols, divisor) -> the header's length
     for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
@@ -2072,5 +2084,115 @@ def compress_picture_set_to_size(images, config, max_bytes, divisors, colour=Non
             if len(c) != int(sizes[i][j]):
                 raise RuntimeError("compress_picture_set_to_size: picture %d was probed at %d bytes under divisor %s, its container holds %d"
                                    % (i, int(sizes[i][j]), ladder[j], len(c)))
+            containers[i] = c
+    return containers, [ladder[j] for j in rung]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# probe_picture_set_distortion takes the device road (jpegx.batch_probe_distortion_picture_set_n: one flat upload, per group
+# of pictures the two gathers onto the block strip and one pass of the distortion kernel with a block's plane, place and band
+# size looked up in the set's table, one download) from DCTN_DISTORTION_MIN_CANDIDATES divisors and this many ADMITTED pictures
+# on; None: the road is off and the function is the loop.  Read when the function is called.  Never below 1.
+# Measured (profiles/probe_distortion_set_n.json and, a second run of the same code, _run2.json; pictures with
+# sides between 64 and 128 at N 4 and N 16, 1, 2 and 16 divisors, the set probe against the loop and against one
+# probe_picture_distortion call per distinct size, alternating call by call on one MI355X; both runs agree on every verdict):
+# the set probe beat the loop at every count (6-7x with one picture and one divisor, 480-550x with 64 and 16).  Against
+# probe_picture_distortion per size: with ONE admitted picture it lost all six comparisons of either run (0.17-0.26 against
+# 0.14-0.25 ms: the table and its upload on top of the same work); with 2 pictures of 2 sizes it won all of them (0.19-0.27
+# against 0.24-0.41 ms); with 4 pictures of 3 sizes it LOST with 1 and 2 divisors in both runs (0.45-0.49 against 0.39-0.42 ms)
+# and lay within 4 % either way with 16; with 16 pictures it won by 2.4-3.0x, with 64 by 4.5-5.5x.  The smallest measured count
+# with no loss at or above it.  Between 2 and 15 admitted pictures callers who know their sizes repeat have
+# probe_picture_distortion; the loop, which this gate falls back to there, is the slowest of the three.
+DCTN_DISTORTION_SET_MIN_PICTURES = 16
+
+
+def _distortion_set_row(image, config, divisors, colour):
+    """One row of the literal loop: _distortion_loop of the one picture under the configuration at its own size."""
+    return _distortion_loop([image], _sized(config, image.height, image.width), divisors, colour)[0]
+
+
+def _distortion_set_device(images, config, divisors, colour):
+    """{index: int64 [3][K] sums} of the pictures that were measured on the device as one set; empty where the gates, the
+    configuration or libjpegx say no.  The vetting is _admitted_set's, as the size probe's over a set."""
+    gate, least = DCTN_DISTORTION_MIN_CANDIDATES, DCTN_DISTORTION_SET_MIN_PICTURES
+    if gate is None or least is None or len(divisors) < max(gate, 1) or len(images) < max(least, 1) \
+            or not _stock_registry() or not _device_usable():
+        return {}
+    import jpegx
+    vetted = _admitted_set(images, config, colour, least)
+    if vetted is None:
+        return {}
+    admitted, pixels, job = vetted
+    out = np.empty((len(admitted), 3, len(divisors)), dtype=np.int64)
+    for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
+        some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
+        got = _none_on_refusal(jpegx.batch_probe_distortion_picture_set_n, pixels, job[0], job[1], "divide", [float(d) for d in some],
+                               **_colour_kw(colour))
+        if got is None:
+            return {}
+        sse, bad = got
+        part = np.asarray(sse).astype(np.int64)
+        # Jpeg.compress raises for the whole picture when any band does
+        part[np.broadcast_to(np.asarray(bad).any(axis=1, keepdims=True), part.shape)] = -1
+        out[:, :, at:at + len(some)] = part
+    return {at: out[k] for k, (at, _, _) in enumerate(admitted)}
+
+
+def probe_picture_set_distortion(images, config, divisors, colour=None):
+    """int64 [len(images)][3][len(divisors)]: entry [i][b][j] is what probe_picture_distortion gives for picture i alone under
+    ``config`` with the picture's own width and height (``config``'s own are not read) and divisor divisors[j]: the sum over the
+    picture's pixels of the squared differences in coded band b; -1 (in all three bands) where compressing raises
+    BadRleCodeError.  ``images``: a sequence of PIL images, sizes as they come.  ValueError as probe_picture_distortion raises it.
+    The pictures that compress_picture_set admits (probe_picture_set_sizes' vetting; planes of at least DCTN_MIN_SAMPLES samples)
+    are measured on the device as ONE set, 32 divisors to a pass (jpegx.batch_probe_distortion_picture_set_n), when there are
+    at least DCTN_DISTORTION_SET_MIN_PICTURES of them and at least DCTN_DISTORTION_MIN_CANDIDATES divisors; every other picture,
+    and all of them after a refusal, are the loop.  Rows come back in input order."""
+    _check_colour(colour)
+    divisors = _checked_divisors(config, divisors)
+    images = list(images)
+    done = _distortion_set_device(images, config, divisors, colour) if images and divisors else {}
+    out = np.empty((len(images), 3, len(divisors)), dtype=np.int64)
+    for at, im in enumerate(images):
+        out[at] = done[at] if at in done else _distortion_set_row(im, config, divisors, colour)
+    return out
+
+
+def probe_picture_set_psnr(images, config, divisors, colour=None):
+    """float64 [len(images)][len(divisors)]: probe_picture_psnr for a set, every picture's PSNR over its three coded bands with
+    its OWN rows * cols: inf where nothing is lost, nan where the picture cannot be coded."""
+    images = list(images)
+    sse = probe_picture_set_distortion(images, config, divisors, colour)
+    out = np.empty((len(images), sse.shape[2]), dtype=np.float64)
+    for at, im in enumerate(images):
+        out[at] = _psnr_of(sse[at:at + 1], im.height, im.width)[0]
+    return out
+
+
+def compress_picture_set_to_quality(images, config, min_psnr, divisors, colour=None):
+    """compress_pictures_to_quality for a set of pictures of unequal sizes: (containers, chosen), every picture compressed under
+    the configuration at its own size with the largest divisor of the ascending ladder ``divisors`` (at most 32 rungs) that
+    keeps its PSNR at ``min_psnr`` dB or above; containers[i] equals Jpeg(config_i with chosen[i]).compress(images[i])
+    (compress_rgb with colour='rgb'), byte for byte, in input order.  ONE probe_picture_set_psnr call measures the set on every
+    rung; the pictures of a rung are then one compress_picture_set call.  TargetQualityError names the first picture that meets
+    the floor on no rung."""
+    _check_colour(colour)
+    ladder = _checked_divisors(config, divisors)
+    if not 1 <= len(ladder) <= 32 or any(b <= a for a, b in zip(ladder, ladder[1:])):
+        raise ValueError("compress_picture_set_to_quality: divisors must be 1..32 ascending rungs")
+    images = list(images)
+    psnr = probe_picture_set_psnr(images, config, ladder, colour)
+    rung = []
+    for i, row in enumerate(psnr):
+        meeting = [j for j, p in enumerate(row) if _meets(p, min_psnr)]
+        if not meeting:
+            coded = [(float(p), -ladder[j]) for j, p in enumerate(row) if not np.isnan(p)]
+            raise TargetQualityError("picture %d meets %.2f dB on no rung%s" % (
+                i, min_psnr, ": its best PSNR is %.2f dB, at divisor %d" % (max(coded)[0], -max(coded)[1]) if coded
+                else " (BadRleCodeError at every rung)"))
+        rung.append(meeting[-1])
+    containers = [None] * len(rung)
+    for j in sorted(set(rung)):
+        members = [i for i, r in enumerate(rung) if r == j]
+        for i, c in zip(members, compress_picture_set([images[i] for i in members], _divide_config(config, ladder[j]), colour)):
             containers[i] = c
     return containers, [ladder[j] for j in rung]

@@ -820,6 +820,32 @@ size_t jpegx_batch_probe_picture_set_workspace_bytes_n(const void *h_table, long
 int jpegx_batch_probe_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
                                     const double *h_params, int K, long long group_samples, void *d_workspace,
                                     unsigned long long *d_totals, jpegx_stream_t stream);
+/* The distortion probe (above) for a set: k_distort_n<true> finds a block's plane as the size probe over a set does, and takes
+ * the block's place in its band and the band's rows x cols from the table instead of from one shape (csrc/jpegx_distort_n.hip).
+ * jpegx_picture_set_moments_n (enqueue only, one launch): arguments and refusals of jpegx_picture_set_blocks_n; d_moments (16-byte
+ * aligned) is a strip [nblocks * N][N] of 64-bit words, pitch N, in the block and element order of jpegx_picture_set_blocks_n.
+ * Each word is S2 << 32 | S1 over the LIVE pixels of the sample's bs x bs tile, the pixels of the tile inside the picture's own
+ * rows x cols; 0 for a sample of either padding.  Only live pixels are read: no read leaves [rows] x [cols * nbands] bytes of
+ * a picture's rows.  With colour = 1 the moments are those of the YCbCr values.
+ * jpegx_probe_distortion_set_n (enqueue only: one memset of its rows of d_totals, one kernel): d_strip and d_moments are the
+ * two strips of pictures p0 .. p0 + k - 1; d_totals [k * nbands][K] in the table's plane order.  Bits 0..62 the band's sum of
+ * squared differences over its own rows x cols pixels under candidate q, bit 63 the bad-amplitude flag (the low bits are then
+ * unspecified); modes, candidates and their meaning as jpegx_probe_distortion_n.  Refused before any device work
+ * (JPEGX_E_INVALID): what jpegx_probe_sizes_set_n refuses, and d_moments null or not 8-byte aligned.
+ * jpegx_batch_probe_distortion_picture_set_n (enqueue only): jpegx_batch_probe_picture_set_n's groups, checks and refusals; per
+ * group the two gathers into the workspace and the probe into the group's rows of d_totals [npictures * nbands][K].  The
+ * workspace (16-byte aligned) is one group's strip and one group's moments:
+ * jpegx_batch_probe_distortion_picture_set_workspace_bytes_n = 2 * up256(8 * samples of the largest group), 0 for what the
+ * entry refuses of the table and group_samples.                                                                          */
+int jpegx_picture_set_moments_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour,
+                                unsigned long long *d_moments, jpegx_stream_t stream);
+int jpegx_probe_distortion_set_n(const double *d_strip, const unsigned long long *d_moments, const void *h_table,
+                                 const void *d_table, int p0, int k, int mode, const double *h_params, int K,
+                                 unsigned long long *d_totals, jpegx_stream_t stream);
+size_t jpegx_batch_probe_distortion_picture_set_workspace_bytes_n(const void *h_table, long long group_samples);
+int jpegx_batch_probe_distortion_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour,
+                                               int mode, const double *h_params, int K, long long group_samples,
+                                               void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
 
 /* ---- batch codec for whole pictures at dct_size 8(csrc/jpegx_picture_u8.hip, csrc/jpegx_batch.cpp) -------------------
  * jpegx_picture_planes_stacked_u8 (enqueue only): pictures stacked [npictures * rows][pitch], every row cols * nbands
@@ -1373,6 +1399,15 @@ int jpegx_batch_probe_distortion_pictures_n_on(int device, const uint8_t *d_pixe
                                                int cols, ptrdiff_t pitch, int colour, int bs, int N, int mode,
                                                const double *h_params, int K, int group_planes, void *d_workspace,
                                                unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_picture_set_moments_n_on(int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0,
+                                   int k, int colour, unsigned long long *d_moments, jpegx_stream_t stream);
+int jpegx_probe_distortion_set_n_on(int device, const double *d_strip, const unsigned long long *d_moments,
+                                    const void *h_table, const void *d_table, int p0, int k, int mode,
+                                    const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_distortion_picture_set_n_on(int device, const uint8_t *d_pixels, const void *h_table,
+                                                  const void *d_table, int colour, int mode, const double *h_params, int K,
+                                                  long long group_samples, void *d_workspace, unsigned long long *d_totals,
+                                                  jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
