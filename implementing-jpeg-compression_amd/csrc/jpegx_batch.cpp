@@ -397,6 +397,19 @@ size_t picture_front_bytes(const PictureShape &s, int bs)
     return s.u8 ? up256((size_t)s.nplanes * s.H * bs * ((size_t)s.W * bs)) : up256((size_t)s.gp * s.H * s.W * 8);
 }
 
+// the probes' shape: picture_shape, on the float64 road whatever block_size -- one group of planes within 2^31 - 1 samples
+int probe_picture_shape(const char *who, int npictures, int nbands, int rows, int cols, int bs, int colour, int group_planes, PictureShape *s)
+{
+    const int rc = picture_shape(who, npictures, nbands, rows, cols, bs, colour, group_planes, s);
+    if (rc) return rc;
+    if ((long long)s->H * s->W > 0x7FFFFFFFLL / s->gp) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "%s: more than 2^31 - 1 samples in one group of planes", who);
+        return fail(JPEGX_E_INVALID, buf);
+    }
+    return JPEGX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -469,6 +482,63 @@ int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long 
     if ((rc = jpegx_batch_decompress(d_bytes, h_plane_offsets, s.nplanes, s.H, s.W, 1, mode, param, 0, d_workspace, planes, s.W, JPEGX_OUT_U8, stream)))
         return rc;
     return jpegx_inflate_crop_pack_stacked_u8(planes, npictures, nbands, s.H, s.W, rows, cols, bs, colour, d_out, out_pitch, stream);
+}
+
+// ---- the size probe over a stack of pictures at dct_size 8 (jpegx_probe_8.hip): one group of float64 planes is the whole
+// workspace.  Always the float64 road: the uint8 road's integers are the same integers, both are bit-exact with the reference.
+size_t jpegx_batch_probe_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes)
+{
+    PictureShape s;
+    if (probe_picture_shape("batch_probe_pictures", npictures, nbands, rows, cols, bs, 0, group_planes, &s)) return 0;
+    return up256((size_t)s.gp * s.H * s.W * 8);
+}
+
+int jpegx_batch_probe_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int mode,
+                               const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream)
+{
+    const char *who = "batch_probe_pictures";
+    int rc = check_probe_pointers(who, d_pixels, d_workspace, d_totals);
+    if (rc) return rc;
+    PictureShape s;
+    if ((rc = probe_picture_shape(who, npictures, nbands, rows, cols, bs, colour, group_planes, &s)) ||
+        (rc = jpegx_internal_probe_check_params_8(who, mode, h_params, K)) || (rc = check_probe_buffers(who, pitch, cols, nbands, d_workspace, d_totals)))
+        return rc;
+    double *planes = static_cast<double *>(d_workspace);
+    return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
+        const int rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, 8, planes,
+                                                          s.W, stream);
+        return rc ? rc : jpegx_probe_sizes_8(planes, nq * nbands, s.H, s.W, s.W, mode, h_params, K, d_totals + (size_t)q0 * nbands * K, stream);
+    });
+}
+
+// ---- the distortion probe over a stack of pictures at dct_size 8: one group of float64 planes and one of moments ------------
+size_t jpegx_batch_probe_distortion_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes)
+{
+    PictureShape s;
+    if (probe_picture_shape("batch_probe_distortion_pictures", npictures, nbands, rows, cols, bs, 0, group_planes, &s)) return 0;
+    return 2 * up256((size_t)s.gp * s.H * s.W * 8);
+}
+
+int jpegx_batch_probe_distortion_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs,
+                                          int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals,
+                                          jpegx_stream_t stream)
+{
+    const char *who = "batch_probe_distortion_pictures";
+    int rc = check_probe_pointers(who, d_pixels, d_workspace, d_totals);
+    if (rc) return rc;
+    PictureShape s;
+    if ((rc = probe_picture_shape(who, npictures, nbands, rows, cols, bs, colour, group_planes, &s)) ||
+        (rc = jpegx_internal_probe_check_params_8(who, mode, h_params, K)) || (rc = check_probe_buffers(who, pitch, cols, nbands, d_workspace, d_totals)))
+        return rc;
+    double *planes = static_cast<double *>(d_workspace);
+    unsigned long long *moments = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(d_workspace) + up256((size_t)s.gp * s.H * s.W * 8));
+    return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
+        const uint8_t *px = d_pixels + (size_t)q0 * rows * (size_t)pitch;
+        int rc = jpegx_band_planes_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, 8, planes, s.W, stream);
+        if (rc || (rc = jpegx_band_moments_packed_stacked_n(px, nq, nbands, rows, cols, pitch, colour, bs, 8, moments, s.W, stream))) return rc;
+        return jpegx_probe_distortion_8(planes, moments, nq * nbands, s.H, s.W, s.W, s.W, bs, rows, cols, mode, h_params, K,
+                                        d_totals + (size_t)q0 * nbands * K, stream);
+    });
 }
 
 }  // extern "C"

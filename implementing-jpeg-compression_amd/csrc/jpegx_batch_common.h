@@ -95,6 +95,28 @@ int check_colour(const char *who, int nbands, int colour)
     return JPEGX_OK;
 }
 
+// what the picture probes (jpegx_batch_probe_pictures*, jpegx_batch_probe_distortion_pictures*, every dct_size) ask of their
+// buffers: the pointers first, the rest once the shape and the candidates have passed
+int check_probe_pointers(const char *who, const void *d_pixels, const void *d_workspace, const void *d_totals)
+{
+    if (d_pixels && d_workspace && d_totals) return JPEGX_OK;
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s: d_pixels / d_workspace / d_totals: null device pointer", who);
+    return fail(JPEGX_E_INVALID, buf);
+}
+
+int check_probe_buffers(const char *who, ptrdiff_t pitch, int cols, int nbands, const void *d_workspace, const void *d_totals)
+{
+    char buf[200];
+    const char *what = nullptr;
+    if (pitch < (ptrdiff_t)cols * nbands) what = "pitch smaller than the row";
+    else if (!aligned16(d_workspace)) what = "d_workspace must be 16-byte aligned";
+    else if (reinterpret_cast<uintptr_t>(d_totals) & 7u) what = "d_totals must be 8-byte aligned";
+    if (!what) return JPEGX_OK;
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return fail(JPEGX_E_INVALID, buf);
+}
+
 int check_offsets(const char *prefix, const unsigned long long *off, int nplanes)
 {
     for (int p = 0; p < nplanes; ++p) {

@@ -316,13 +316,13 @@ int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nba
                                  int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals,
                                  jpegx_stream_t stream)
 {
-    if (!d_pixels || !d_workspace || !d_totals) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: d_pixels / d_workspace / d_totals: null device pointer");
+    const char *who = "batch_probe_pictures_n";
+    int rc = check_probe_pointers(who, d_pixels, d_workspace, d_totals);
+    if (rc) return rc;
     Shape s;
-    int rc = picture_shape("batch_probe_pictures_n", npictures, nbands, rows, cols, bs, N, colour, group_planes, &s);
-    if (rc || (rc = jpegx_internal_probe_check_params("batch_probe_pictures_n", mode, h_params, K))) return rc;
-    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: pitch smaller than the row");
-    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: d_workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_totals) & 7u) return fail(JPEGX_E_INVALID, "batch_probe_pictures_n: d_totals must be 8-byte aligned");
+    if ((rc = picture_shape(who, npictures, nbands, rows, cols, bs, N, colour, group_planes, &s)) ||
+        (rc = jpegx_internal_probe_check_params(who, mode, h_params, K)) || (rc = check_probe_buffers(who, pitch, cols, nbands, d_workspace, d_totals)))
+        return rc;
     double *planes = static_cast<double *>(d_workspace);
     return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {
         const int rc = jpegx_band_planes_packed_stacked_n(d_pixels + (size_t)q0 * rows * (size_t)pitch, nq, nbands, rows, cols, pitch, colour, bs, N, planes,
@@ -344,14 +344,12 @@ int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictur
                                             unsigned long long *d_totals, jpegx_stream_t stream)
 {
     const char *who = "batch_probe_distortion_pictures_n";
-    if (!d_pixels || !d_workspace || !d_totals)
-        return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_pixels / d_workspace / d_totals: null device pointer");
+    int rc = check_probe_pointers(who, d_pixels, d_workspace, d_totals);
+    if (rc) return rc;
     Shape s;
-    int rc = picture_shape(who, npictures, nbands, rows, cols, bs, N, colour, group_planes, &s);
-    if (rc || (rc = jpegx_internal_probe_check_params(who, mode, h_params, K))) return rc;
-    if (pitch < (ptrdiff_t)cols * nbands) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: pitch smaller than the row");
-    if (!aligned16(d_workspace)) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_totals) & 7u) return fail(JPEGX_E_INVALID, "batch_probe_distortion_pictures_n: d_totals must be 8-byte aligned");
+    if ((rc = picture_shape(who, npictures, nbands, rows, cols, bs, N, colour, group_planes, &s)) ||
+        (rc = jpegx_internal_probe_check_params(who, mode, h_params, K)) || (rc = check_probe_buffers(who, pitch, cols, nbands, d_workspace, d_totals)))
+        return rc;
     double *planes = static_cast<double *>(d_workspace);
     unsigned long long *moments = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(d_workspace) + up256((size_t)s.gp * s.samples * 8));
     return for_each_stride(npictures, s.gp / nbands, [&](int q0, int nq) {

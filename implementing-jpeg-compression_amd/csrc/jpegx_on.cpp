@@ -205,6 +205,14 @@ JPEGX_ON(jpegx_probe_distortion_n, (int device, const double *d_planes, const un
          (d_planes, d_moments, nplanes, H, W, pitch, mpitch, N, bs, rows, cols, mode, h_params, K, d_totals, stream))
 JPEGX_ON(jpegx_batch_probe_distortion_pictures_n, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int N, int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream),
          (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, N, mode, h_params, K, group_planes, d_workspace, d_totals, stream))
+JPEGX_ON(jpegx_probe_sizes_8, (int device, const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_planes, nplanes, H, W, pitch, mode, h_params, K, d_totals, stream))
+JPEGX_ON(jpegx_probe_distortion_8, (int device, const double *d_planes, const unsigned long long *d_moments, int nplanes, int H, int W, ptrdiff_t pitch, ptrdiff_t mpitch, int bs, int rows, int cols, int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_planes, d_moments, nplanes, H, W, pitch, mpitch, bs, rows, cols, mode, h_params, K, d_totals, stream))
+JPEGX_ON(jpegx_batch_probe_pictures, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, mode, h_params, K, group_planes, d_workspace, d_totals, stream))
+JPEGX_ON(jpegx_batch_probe_distortion_pictures, (int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch, int colour, int bs, int mode, const double *h_params, int K, int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream),
+         (d_pixels, npictures, nbands, rows, cols, pitch, colour, bs, mode, h_params, K, group_planes, d_workspace, d_totals, stream))
 JPEGX_ON(jpegx_picture_set_moments_n, (int device, const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour, unsigned long long *d_moments, jpegx_stream_t stream),
          (d_pixels, h_table, d_table, p0, k, colour, d_moments, stream))
 JPEGX_ON(jpegx_probe_distortion_set_n, (int device, const double *d_strip, const unsigned long long *d_moments, const void *h_table, const void *d_table, int p0, int k, int mode, const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream),

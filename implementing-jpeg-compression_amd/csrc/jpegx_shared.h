@@ -45,6 +45,8 @@ int jpegx_internal_dctn_forward_tables(int N, const double **d_ct, const uint16_
 int jpegx_internal_dctn_inverse_tables(int N, const double **d_cn, const double **d_dinv);   // jpegx_dctn.hip: the same cache, Cn and Dinv
 // jpegx_probe_n.hip: the checks of jpegx_probe_sizes_n on the quantiser and its K candidates (`who` leads the message), no device touched
 int jpegx_internal_probe_check_params(const char *who, int mode, const double *h_params, int K);
+// jpegx_probe_8.hip: the same for the dct_size-8 probes, which take all four quantisers (`none` and `qtable`: K = 1, h_params not read)
+int jpegx_internal_probe_check_params_8(const char *who, int mode, const double *h_params, int K);
 int jpegx_internal_last_decode_level(void);         // jpegx_decode_ladder.cpp: the scheme that took this thread's last stream (tests)
 }
 

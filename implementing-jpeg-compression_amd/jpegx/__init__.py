@@ -211,6 +211,12 @@ SIGNATURES = {
     "jpegx_probe_distortion_n": [_vp, _vp, _int, _int, _int, _pd, _pd, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp],
     "jpegx_batch_probe_distortion_pictures_workspace_bytes_n": [_int, _int, _int, _int, _int, _int, _int],
     "jpegx_batch_probe_distortion_pictures_n": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
+    "jpegx_probe_sizes_8": [_vp, _int, _int, _int, _pd, _int, _vp, _int, _vp, _vp],
+    "jpegx_probe_distortion_8": [_vp, _vp, _int, _int, _int, _pd, _pd, _int, _int, _int, _int, _vp, _int, _vp, _vp],
+    "jpegx_batch_probe_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
+    "jpegx_batch_probe_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
+    "jpegx_batch_probe_distortion_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
+    "jpegx_batch_probe_distortion_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _vp, _int, _int, _vp, _vp, _vp],
     "jpegx_picture_planes_stacked_u8": [_vp, _int, _int, _int, _int, _pd, _int, _int, _vp, _pd, _vp],
     "jpegx_batch_pictures_workspace_bytes": [_int, _int, _int, _int, _int, _int],
     "jpegx_batch_compress_pictures": [_vp, _int, _int, _int, _int, _pd, _int, _int, _int, _dbl, _int, _vp, _vp, _sz, _vp],
@@ -280,7 +286,8 @@ for _name in ("jpegx_malloc", "jpegx_free", "jpegx_stream_create", "jpegx_genera
               "jpegx_batch_decompress_picture_set", "jpegx_probe_sizes_n", "jpegx_batch_probe_pictures_n",
               "jpegx_probe_sizes_set_n", "jpegx_batch_probe_picture_set_n", "jpegx_band_moments_packed_stacked_n",
               "jpegx_probe_distortion_n", "jpegx_batch_probe_distortion_pictures_n", "jpegx_picture_set_moments_n",
-              "jpegx_probe_distortion_set_n", "jpegx_batch_probe_distortion_picture_set_n"):
+              "jpegx_probe_distortion_set_n", "jpegx_batch_probe_distortion_picture_set_n", "jpegx_probe_sizes_8",
+              "jpegx_probe_distortion_8", "jpegx_batch_probe_pictures", "jpegx_batch_probe_distortion_pictures"):
     SIGNATURES[_name + "_on"] = [_int] + SIGNATURES[_name]
 RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes_n": _sz, "jpegx_entropy_decode_workspace_bytes": _sz, "jpegx_entropy_decode_workspace_bytes_n": _sz,
             "jpegx_batch_workspace_bytes": _sz,
@@ -294,7 +301,9 @@ RESTYPES = {"jpegx_entropy_workspace_bytes": _sz, "jpegx_entropy_workspace_bytes
             "jpegx_batch_probe_pictures_workspace_bytes_n": _sz,
             "jpegx_batch_probe_distortion_pictures_workspace_bytes_n": _sz,
             "jpegx_batch_probe_picture_set_workspace_bytes_n": _sz,
-            "jpegx_batch_probe_distortion_picture_set_workspace_bytes_n": _sz}   # everything else returns int
+            "jpegx_batch_probe_distortion_picture_set_workspace_bytes_n": _sz,
+            "jpegx_batch_probe_pictures_workspace_bytes": _sz,
+            "jpegx_batch_probe_distortion_pictures_workspace_bytes": _sz}   # everything else returns int
 
 
 def lib():
@@ -2488,6 +2497,155 @@ def batch_decompress_pictures(blobs, rows, cols, block_size=1, mode="qtable", pa
         din.upload(stream_bytes)
         batch_decompress_pictures_device(din.ptr, off, *pics, dws.ptr, dout.ptr, None, mode, param, flag)
         return dout.download((k, rows, cols, nb), np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# the size probe and the distortion probe at dct_size 8 (csrc/jpegx_probe_8.hip): the probes above for the 8x8 roads, shaped
+# like their _n namesakes without n.  All four quantiser modes; 'none' and 'qtable' have no parameter: one candidate, not read.
+# ---------------------------------------------------------------------------------------------
+def probe_sizes_8_device(d_planes, nplanes, height, width, mode, params, d_totals, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_probe_sizes_8: nplanes float64 planes stacked [nplanes * height][pitch] (elements, default width) ->
+    uint64 d_totals [nplanes][K]: bits 0..62 the coded bytes of the plane under candidate q, bit 63 the bad-amplitude flag."""
+    h, k = _probe_params(params)
+    args = (d_planes, int(nplanes), int(height), int(width), int(width if pitch is None else pitch), mode_of(mode), h.ctypes.data, k,
+            d_totals, stream)
+    _entry_checked("jpegx_probe_sizes_8", device, *args)
+
+
+def probe_distortion_8_device(d_planes, d_moments, nplanes, height, width, bs, rows, cols, mode, params, d_totals, pitch=None, mpitch=None,
+                              stream=None, device=None):
+    """Enqueue jpegx_probe_distortion_8: nplanes float64 planes stacked [nplanes * height][pitch] and their moments
+    [nplanes * height][mpitch] (elements, default width), every plane a rows x cols band pooled bs x bs -> uint64 d_totals
+    [nplanes][K]: bits 0..62 the sum of squared differences of the band under candidate q, bit 63 the bad-amplitude flag."""
+    h, k = _probe_params(params)
+    args = (d_planes, d_moments, int(nplanes), int(height), int(width), int(width if pitch is None else pitch),
+            int(width if mpitch is None else mpitch), int(bs), int(rows), int(cols), mode_of(mode), h.ctypes.data, k, d_totals, stream)
+    _entry_checked("jpegx_probe_distortion_8", device, *args)
+
+
+def _float64_planes(planes, who):
+    src = np.ascontiguousarray(planes, dtype=np.float64)
+    if src.ndim != 3 or src.size == 0:
+        raise JpegxError("%s: expected non-empty [nplanes][H][W] float64 planes, got %r" % (who, src.shape))
+    return src
+
+
+def probe_sizes_8(planes, mode, params):
+    """float64 planes [nplanes][H][W] of whole 8x8 blocks -> (sizes, bad), each [nplanes][K]: what every plane's stream weighs
+    under candidate q (the bytes of compress_plane_native on that plane), and where an amplitude beyond 15 bits makes that
+    meaningless.  Host convenience: upload, probe, one download."""
+    src = _float64_planes(planes, "probe_sizes_8")
+    n, hh, ww = src.shape
+    h, nk = _probe_params(params)
+    if not 1 <= nk <= PROBE_MAX_CANDIDATES or hh % 8 or ww % 8:     # the entry names the refusal, before any device is touched
+        probe_sizes_8_device(8, n, hh, ww, mode, h, 8)
+        raise JpegxError("probe_sizes_8: the planes were refused")
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dtot = dev(src.nbytes), dev(n * nk * 8)
+        din.upload(src)
+        probe_sizes_8_device(din.ptr, n, hh, ww, mode, h, dtot.ptr)
+        raw = dtot.download((n, nk), np.uint64)
+    return _probe_answer(raw)
+
+
+def probe_distortion_8(planes, moments, bs, rows, cols, mode, params):
+    """float64 planes [nplanes][H][W] and their uint64 moments [nplanes][H][W] (S2 << 32 | S1 of every sample's live pixels),
+    every plane a rows x cols band pooled bs x bs -> (sse, bad), each [nplanes][K].  Host convenience."""
+    src = _float64_planes(planes, "probe_distortion_8")
+    mom = np.ascontiguousarray(moments, dtype=np.uint64)
+    if mom.shape != src.shape:
+        raise JpegxError("probe_distortion_8: the moments must have the planes' shape")
+    n, hh, ww = src.shape
+    h, nk = _probe_params(params)
+    if not 1 <= nk <= PROBE_MAX_CANDIDATES or hh % 8 or ww % 8 or _padded_shape_or_none(rows, cols, bs) != (hh, ww):
+        probe_distortion_8_device(8, 8, n, hh, ww, bs, rows, cols, mode, h, 8)
+        raise JpegxError("probe_distortion_8: the planes were refused")
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dmo, dtot = dev(src.nbytes), dev(mom.nbytes), dev(n * nk * 8)
+        din.upload(src)
+        dmo.upload(mom)
+        probe_distortion_8_device(din.ptr, dmo.ptr, n, hh, ww, bs, rows, cols, mode, h, dtot.ptr)
+        raw = dtot.download((n, nk), np.uint64)
+    return _probe_answer(raw)
+
+
+def _padded_shape_or_none(rows, cols, bs):
+    try:
+        return tuple(padded_shape(rows, cols, bs))
+    except JpegxError:
+        return None
+
+
+def batch_probe_pictures_workspace_bytes(npictures, nbands, rows, cols, bs, group_planes):
+    return lib().jpegx_batch_probe_pictures_workspace_bytes(int(npictures), int(nbands), int(rows), int(cols), int(bs), int(group_planes))
+
+
+def batch_probe_distortion_pictures_workspace_bytes(npictures, nbands, rows, cols, bs, group_planes):
+    return lib().jpegx_batch_probe_distortion_pictures_workspace_bytes(int(npictures), int(nbands), int(rows), int(cols), int(bs),
+                                                                       int(group_planes))
+
+
+def batch_probe_pictures_device(d_pixels, npictures, nbands, rows, cols, bs, mode, params, group_planes, d_workspace, d_totals, colour=0,
+                                pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_probe_pictures: pictures stacked [npictures * rows][pitch] (bytes, default cols * nbands) -> uint64
+    d_totals [nbands * npictures][K], plane-major in the batch's picture-major plane order."""
+    h, k = _probe_params(params)
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
+    _entry_checked("jpegx_batch_probe_pictures", device, *args)
+
+
+def batch_probe_distortion_pictures_device(d_pixels, npictures, nbands, rows, cols, bs, mode, params, group_planes, d_workspace, d_totals,
+                                           colour=0, pitch=None, stream=None, device=None):
+    """Enqueue jpegx_batch_probe_distortion_pictures: as batch_probe_pictures_device, the totals the sums of squared differences."""
+    h, k = _probe_params(params)
+    args = (d_pixels, int(npictures), int(nbands), int(rows), int(cols), int(cols * nbands if pitch is None else pitch), int(colour),
+            int(bs), mode_of(mode), h.ctypes.data, k, int(group_planes), d_workspace, d_totals, stream)
+    _entry_checked("jpegx_batch_probe_distortion_pictures", device, *args)
+
+
+def _batch_probe_8(who, workspace_bytes, enqueue, pixels, bs, mode, params, colour, group_planes):
+    src = _picture_stack(pixels)
+    k, rows, cols, nb = src.shape
+    flag = _colour_flag(colour, nb, who)
+    if group_planes is None:
+        group_planes = batch_group_planes_pictures_n(nb, rows, cols, bs, 8) or nb
+    h, nk = _probe_params(params)
+    pics = (k, nb, rows, cols, int(bs))
+    nws = workspace_bytes(*pics, group_planes)
+    if nws == 0 or not 1 <= nk <= PROBE_MAX_CANDIDATES:     # the entry names the refusal, before any device is touched
+        enqueue(1, *pics, mode, h, group_planes, 16, 8, flag)
+        raise JpegxError("%s: the batch was refused" % who)
+    mode_of(mode)
+    require_device()
+    with _Buffers() as dev:
+        din, dws, dtot = dev(src.nbytes), dev(nws), dev(k * nb * nk * 8)
+        din.upload(src)
+        enqueue(din.ptr, *pics, mode, h, group_planes, dws.ptr, dtot.ptr, flag)
+        raw = dtot.download((k, nb, nk), np.uint64)
+    return _probe_answer(raw)
+
+
+def batch_probe_pictures(pixels, bs, mode, params, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> (sizes, bad): sizes uint64 [k][nb][K], the length of band b of picture p as
+    batch_compress_pictures would code it under candidate q; bad bool [k][nb][K], True where that band holds an amplitude
+    beyond 15 bits under that candidate (its size is then meaningless).  Host convenience: upload, probe, one download.
+    group_planes None: the recommended value."""
+    return _batch_probe_8("batch_probe_pictures", batch_probe_pictures_workspace_bytes, batch_probe_pictures_device, pixels, bs, mode,
+                          params, colour, group_planes)
+
+
+def batch_probe_distortion_pictures(pixels, bs, mode, params, colour=None, group_planes=None):
+    """uint8 pictures [k][rows][cols][nb] -> (sse, bad): sse uint64 [k][nb][K], the sum of squared differences between band b of
+    picture p and what batch_decompress_pictures gives back of batch_compress_pictures's bytes under candidate q (with
+    colour='rgb': in the coded YCbCr bands); bad as batch_probe_pictures gives it (the band cannot be coded; its sum is then
+    meaningless).  Host convenience: upload, probe, one download.  group_planes None: the recommended value."""
+    return _batch_probe_8("batch_probe_distortion_pictures", batch_probe_distortion_pictures_workspace_bytes,
+                          batch_probe_distortion_pictures_device, pixels, bs, mode, params, colour, group_planes)
 
 
 # ---------------------------------------------------------------------------------------------

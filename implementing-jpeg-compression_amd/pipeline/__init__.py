@@ -1534,6 +1534,17 @@ def decompress_picture_set(containers, colour=None):
 # candidate.  The smallest measured count with no loss at or above it; no plane size lost at every count, so there is no size
 # gate beyond DCTN_MIN_SAMPLES.
 DCTN_PROBE_MIN_CANDIDATES = 2
+# dct_size 8 has a size probe of its own (jpegx.batch_probe_pictures: csrc/jpegx_probe_8.hip, the float64 tier of the 8x8 roads
+# with the stream left out, so its sizes are the roads' sizes, exact rounding ties included) behind a gate of its OWN, with the
+# meaning of the constant above and read when the function is called.  It ships as None -- the road is off and dct_size 8 is the
+# loop, as it was (tests/test_probe_dispatch.py pins that with only the DCTN_* gates set; the precedent is
+# DCT8_PICTURE_BATCH_MIN_PICTURES) -- and a caller opts in by setting it.
+# Measured (microbench/probe_8.py, profiles/probe_8.json and, a second run of the same code, _run2.json; 1 and 8
+# pictures of 64 x 64 and 512 x 512 at block_size 4 and 1, the probe against the loop alternating call by call on one MI355X):
+# with ONE divisor the probe loses on one 512 x 512 picture at block_size 1 (0.44 against 0.37 and 0.31 ms) and wins the
+# other comparisons; from 2 divisors on it won every comparison of both runs (1.4-11x with 2, 8.3-47x with 16).  By the
+# rule of the constant above -- the smallest measured count with no loss at or above it in either run -- this gate would stand at 2.
+DCT8_PROBE_MIN_CANDIDATES = None
 
 
 class TargetSizeError(ValueError):
@@ -1582,30 +1593,59 @@ def _probe_loop(images, config, divisors, colour):
     return out
 
 
-def _probe_device(images, config, divisors, colour):
-    """The sizes from jpegx.batch_probe_pictures_n, or None: the gate, the configuration or the pictures do not admit the road,
-    or libjpegx refused or failed."""
-    gate = DCTN_PROBE_MIN_CANDIDATES
+def _probe_job(images, config, divisors, colour, gate_n, gate_8):
+    """(the pictures as _stacked_pixels gives them, the entry's arguments between them and the mode, dct_size 8?) for the two
+    probe roads, or None: the gate, the configuration or the pictures do not admit the road.  ``gate_n`` and ``gate_8`` are the
+    function's DCTN_* and DCT8_* constants as it reads them from this module.  dct_size 8 (the accelerated configuration) goes by
+    _job_config_8, the quantiser 'divide', a usable device and jpegx.padded_shape to the entries without n, (block_size,);
+    every other size by _job_sizes, _blocked_shape and dctn_on_device to the _n entries, (block_size, dct_size)."""
+    eight = _accelerated(config)
+    gate = gate_8 if eight else gate_n
     count = len(images)
     if gate is None or len(divisors) < max(gate, 1) or count < 1 or not _stock_registry():
         return None
-    sizes = _job_sizes(config)                           # transform 'DCT', dct_size 2..32 but 8, a usable device
     rows, cols = config.height, config.width
-    if sizes is None or not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
+    if not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
             or rows * cols > 2 ** 31 - 1:
         return None
-    bs, n = sizes
-    h, w = _blocked_shape(rows, cols, bs, n)
-    if not dctn_on_device(config, h * w) or 3 * count * h * w > 2 ** 31 - 1:
+    if eight:
+        job = _job_config_8(config)
+        # _job_config_8 lets a block_size such as 2.0 through; the container's header does not (the loop raises), so neither
+        # does this road: an integer, as _job_sizes asks of the other sizes
+        if job is None or job[1] != "divide" or not isinstance(job[0], (int, np.integer)) or not _device_usable():
+            return None
+        import jpegx
+        head = (int(job[0]),)
+        shape = _none_on_refusal(jpegx.padded_shape, rows, cols, head[0])
+        if shape is None:
+            return None
+        h, w = shape
+    else:
+        head = _job_sizes(config)                        # transform 'DCT', dct_size 2..32 but 8, a usable device
+        if head is None:
+            return None
+        h, w = _blocked_shape(rows, cols, *head)
+        if not dctn_on_device(config, h * w):
+            return None
+    if 3 * count * h * w > 2 ** 31 - 1:
         return None
     stack = _stacked_pixels(images, config, colour)
-    if stack is None:
+    return None if stack is None else (stack, head, eight)
+
+
+def _probe_device(images, config, divisors, colour):
+    """The sizes from jpegx.batch_probe_pictures_n -- at dct_size 8 from jpegx.batch_probe_pictures --, or None: the gate, the
+    configuration or the pictures do not admit the road (_probe_job), or libjpegx refused or failed."""
+    job = _probe_job(images, config, divisors, colour, DCTN_PROBE_MIN_CANDIDATES, DCT8_PROBE_MIN_CANDIDATES)
+    if job is None:
         return None
+    stack, head, eight = job
     import jpegx
-    out = np.empty((count, len(divisors)), dtype=np.int64)
+    entry = jpegx.batch_probe_pictures if eight else jpegx.batch_probe_pictures_n
+    out = np.empty((len(stack), len(divisors)), dtype=np.int64)
     for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
         some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
-        got = _none_on_refusal(jpegx.batch_probe_pictures_n, stack, bs, n, "divide", [float(d) for d in some], **_colour_kw(colour))
+        got = _none_on_refusal(entry, stack, *head, "divide", [float(d) for d in some], **_colour_kw(colour))
         if got is None:
             return None
         coded, bad = got
@@ -1624,7 +1664,9 @@ def probe_picture_sizes(images, config, divisors, colour=None):
     them.  ValueError for a configuration that is not 'divide' and for a divisor that is not a whole positive number.
     With at least DCTN_PROBE_MIN_CANDIDATES divisors, dct_size other than 8 with transform 'DCT', the stock steps, a usable
     device, pictures that _stacked_pixels accepts and planes of at least DCTN_MIN_SAMPLES samples, all divisors are sized on the
-    device in one pass per 32 of them (jpegx.batch_probe_pictures_n); everything else, and every refusal, is the loop."""
+    device in one pass per 32 of them (jpegx.batch_probe_pictures_n); everything else, and every refusal, is the loop.
+    dct_size 8 has the same road (_job_config_8, jpegx.batch_probe_pictures) behind a gate of its own,
+    DCT8_PROBE_MIN_CANDIDATES, which ships as None: dct_size 8 is the loop until a caller sets it."""
     _check_colour(colour)
     divisors = _checked_divisors(config, divisors)
     if not isinstance(images, np.ndarray):
@@ -1752,6 +1794,11 @@ def compress_pictures_to_size(images, config, max_bytes, divisors, colour=None):
 # 5 N 24.  The smallest measured count with no loss against the loop at or above it; no plane size lost at any count, so there
 # is no size gate beyond DCTN_MIN_SAMPLES.
 DCTN_DISTORTION_MIN_CANDIDATES = 1
+# The same at dct_size 8 (jpegx.batch_probe_distortion_pictures), behind a gate of its own that ships as None: the road is off
+# and dct_size 8 is the loop, as it was (tests/test_distortion_dispatch.py pins that) until a caller sets it.  Measured (DESIGN.md
+# 4.27, profiles/probe_8.json and _run2.json, the shapes of DCT8_PROBE_MIN_CANDIDATES): the probe won every comparison against
+# the loop, 3.1-17x with one divisor and 23-178x with 16; by the rule of the constant above the gate would stand at 1.
+DCT8_DISTORTION_MIN_CANDIDATES = None
 
 
 class TargetQualityError(ValueError):
@@ -1779,29 +1826,18 @@ def _distortion_loop(images, config, divisors, colour):
 
 
 def _distortion_device(images, config, divisors, colour):
-    """The sums from jpegx.batch_probe_distortion_pictures_n, or None: the gate, the configuration or the pictures do not admit
-    the road, or libjpegx refused or failed."""
-    gate = DCTN_DISTORTION_MIN_CANDIDATES
-    count = len(images)
-    if gate is None or len(divisors) < max(gate, 1) or count < 1 or not _stock_registry():
+    """The sums from jpegx.batch_probe_distortion_pictures_n -- at dct_size 8 from jpegx.batch_probe_distortion_pictures --, or
+    None: the gate, the configuration or the pictures do not admit the road (_probe_job), or libjpegx refused or failed."""
+    job = _probe_job(images, config, divisors, colour, DCTN_DISTORTION_MIN_CANDIDATES, DCT8_DISTORTION_MIN_CANDIDATES)
+    if job is None:
         return None
-    sizes = _job_sizes(config)                           # transform 'DCT', dct_size 2..32 but 8, a usable device
-    rows, cols = config.height, config.width
-    if sizes is None or not isinstance(rows, (int, np.integer)) or not isinstance(cols, (int, np.integer)) or rows < 1 or cols < 1 \
-            or rows * cols > 2 ** 31 - 1:
-        return None
-    bs, n = sizes
-    h, w = _blocked_shape(rows, cols, bs, n)
-    if not dctn_on_device(config, h * w) or 3 * count * h * w > 2 ** 31 - 1:
-        return None
-    stack = _stacked_pixels(images, config, colour)
-    if stack is None:
-        return None
+    stack, head, eight = job
     import jpegx
-    out = np.empty((count, 3, len(divisors)), dtype=np.int64)
+    entry = jpegx.batch_probe_distortion_pictures if eight else jpegx.batch_probe_distortion_pictures_n
+    out = np.empty((len(stack), 3, len(divisors)), dtype=np.int64)
     for at in range(0, len(divisors), jpegx.PROBE_MAX_CANDIDATES):
         some = divisors[at:at + jpegx.PROBE_MAX_CANDIDATES]
-        got = _none_on_refusal(jpegx.batch_probe_distortion_pictures_n, stack, bs, n, "divide", [float(d) for d in some], **_colour_kw(colour))
+        got = _none_on_refusal(entry, stack, *head, "divide", [float(d) for d in some], **_colour_kw(colour))
         if got is None:
             return None
         sse, bad = got
@@ -1822,7 +1858,8 @@ def probe_picture_distortion(images, config, divisors, colour=None):
     With at least DCTN_DISTORTION_MIN_CANDIDATES divisors, dct_size other than 8 with transform 'DCT', the stock steps, a usable
     device, pictures that _stacked_pixels accepts and planes of at least DCTN_MIN_SAMPLES samples, all divisors are measured on
     the device in one pass per 32 of them (jpegx.batch_probe_distortion_pictures_n); everything else, and every refusal, is the
-    loop."""
+    loop.  dct_size 8 has the same road (_job_config_8, jpegx.batch_probe_distortion_pictures) behind a gate of its own,
+    DCT8_DISTORTION_MIN_CANDIDATES, which ships as None: dct_size 8 is the loop until a caller sets it."""
     _check_colour(colour)
     divisors = _checked_divisors(config, divisors)
     if not isinstance(images, np.ndarray):

@@ -696,6 +696,48 @@ int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictur
                                             int group_planes, void *d_workspace, unsigned long long *d_totals,
                                             jpegx_stream_t stream);
 
+/* ---- size probe and distortion probe at dct_size 8 (csrc/jpegx_probe_8.hip; the batch entries in csrc/jpegx_batch.cpp) ------
+ * The probes above for the 8 x 8 roads, whose integers are bit-exact with the reference, exact rounding ties included: for
+ * every plane p and candidate q what plane p weighs in the plane index of a sizes-only jpegx_batch_compress_pictures(..., mode,
+ * h_params[q], ...), and the sum of squared differences between the band and what jpegx_batch_decompress_pictures gives back of
+ * those bytes.  The kernel is the float64 tier of both roads with the stream left out: transforms.py:46-58 rows first in the
+ * reference's operation order, quantizers.py:4-53 per candidate with a true float64 division (a multiplication only for
+ * divisors +-2^e, where both are the same double), the int16 clamp, pipeline/zigzag_order.py and the code-length rule of
+ * pipeline/run_length_encoding.py:47-64 + pipeline/rle_byte_stream.py:48-59 for the sizes; Quantizer.restore,
+ * transforms.py:60-69 columns first, np.round (pipeline/basis_change.py:43), the clamp to 0..255 and the moments of
+ * jpegx_band_moments_packed_stacked_n(..., N = 8, ...) for the distortion.  No coefficient stream and no decoded picture are
+ * written.  d_totals [nplanes][K], 8-byte aligned, bit 63 = an amplitude beyond 15 bits (BadRleCodeError), as above.
+ * jpegx_probe_sizes_8 / jpegx_probe_distortion_8 (enqueue only: one memset of d_totals, one kernel): arguments as their _n
+ * namesakes without N; H and W positive multiples of 8, rows and cols giving H, W by jpegx_padded_shape.  ALL FOUR quantiser
+ * modes are taken: JPEGX_Q_NONE and JPEGX_Q_QTABLE have no parameter, K must be 1 and h_params is not read; JPEGX_Q_DISCARD and
+ * JPEGX_Q_DIVIDE as above.  Refused before any device work (JPEGX_E_INVALID, the message names the entry and the argument): null
+ * pointers, nplanes < 1, H or W no positive multiple of 8, pitch or mpitch < W, nplanes * H * W > 2^31 - 1, bs outside 1..255,
+ * rows and cols that do not give H and W, a pointer that is not 8-byte aligned, K outside 1..JPEGX_PROBE_MAX_CANDIDATES, K != 1
+ * without a parameter, a zero, NaN or infinite divisor, a fractional or negative keep.
+ * jpegx_batch_probe_pictures / jpegx_batch_probe_distortion_pictures (enqueue only): a stack of pictures from their 8-bit pixels,
+ * group by group of whole pictures as jpegx_batch_compress_pictures walks its float64 road -- jpegx_band_planes_packed_stacked_n
+ * at N = 8 (and jpegx_band_moments_packed_stacked_n at N = 8) into the workspace, then the probe into the group's rows of
+ * d_totals [nbands * npictures][K].  Always the float64 road, whatever block_size: the uint8 road's integers are the same.
+ * Shape, limits and refusals of jpegx_batch_compress_pictures, a group of planes within 2^31 - 1 samples, the candidates'
+ * checks above; the workspace (16-byte aligned) is one group of float64 planes, up256(min(group_planes, nbands * npictures) *
+ * H * W * 8) bytes with H, W from jpegx_padded_shape, and as much again for the moments of the distortion entry; the
+ * _workspace_bytes functions return 0 for a shape the entries refuse.                                                        */
+int jpegx_probe_sizes_8(const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int mode, const double *h_params,
+                        int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_probe_distortion_8(const double *d_planes, const unsigned long long *d_moments, int nplanes, int H, int W,
+                             ptrdiff_t pitch, ptrdiff_t mpitch, int bs, int rows, int cols, int mode, const double *h_params,
+                             int K, unsigned long long *d_totals, jpegx_stream_t stream);
+size_t jpegx_batch_probe_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes);
+int jpegx_batch_probe_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
+                               int colour, int bs, int mode, const double *h_params, int K, int group_planes,
+                               void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
+size_t jpegx_batch_probe_distortion_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs,
+                                                             int group_planes);
+int jpegx_batch_probe_distortion_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                          ptrdiff_t pitch, int colour, int bs, int mode, const double *h_params, int K,
+                                          int group_planes, void *d_workspace, unsigned long long *d_totals,
+                                          jpegx_stream_t stream);
+
 /* ---- batch codec for a SET of pictures of UNEQUAL sizes at any DCT size but 8 (csrc/jpegx_batch_set_n.cpp,
  * csrc/jpegx_band_set_n.hip) ----------------------------------------------------------------------------------------------
  * Jpeg.compress and Jpeg.decompress of the reference (pipeline/__init__.py:98-124; with colour = 1 behind compress.py:9 and in
@@ -1408,6 +1450,18 @@ int jpegx_batch_probe_distortion_picture_set_n_on(int device, const uint8_t *d_p
                                                   const void *d_table, int colour, int mode, const double *h_params, int K,
                                                   long long group_samples, void *d_workspace, unsigned long long *d_totals,
                                                   jpegx_stream_t stream);
+int jpegx_probe_sizes_8_on(int device, const double *d_planes, int nplanes, int H, int W, ptrdiff_t pitch, int mode,
+                           const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_probe_distortion_8_on(int device, const double *d_planes, const unsigned long long *d_moments, int nplanes, int H,
+                                int W, ptrdiff_t pitch, ptrdiff_t mpitch, int bs, int rows, int cols, int mode,
+                                const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_pictures_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
+                                  ptrdiff_t pitch, int colour, int bs, int mode, const double *h_params, int K,
+                                  int group_planes, void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
+int jpegx_batch_probe_distortion_pictures_on(int device, const uint8_t *d_pixels, int npictures, int nbands, int rows,
+                                             int cols, ptrdiff_t pitch, int colour, int bs, int mode, const double *h_params,
+                                             int K, int group_planes, void *d_workspace, unsigned long long *d_totals,
+                                             jpegx_stream_t stream);
 int jpegx_host_pool_release_on(int device);
 int jpegx_comm_create_deadline_on(int device, jpegx_comm_t *comm, int nranks, int rank, const void *id128,
                                   double timeout_s);
