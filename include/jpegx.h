@@ -289,6 +289,9 @@ int jpegx_host_entropy_decode_n(const uint8_t *h_bytes, size_t nbytes, long long
  * byte offsets into the workspace) -> jpegx_entropy_total (synchronises, returns the total and
  * JPEGX_E_INVALID if an amplitude exceeds 15 bits, the reference's BadRleCodeError) ->
  * jpegx_entropy_emit into a buffer of at least `total` bytes.                                  */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_entropy_total, _block_sizes and _emit read what the last jpegx_entropy_sizes on it left there.
+ * The value does not shrink when a count argument grows. */
 size_t jpegx_entropy_workspace_bytes(long long nblocks);
 int jpegx_entropy_sizes(const int16_t *d_zz, long long nblocks, void *d_workspace, jpegx_stream_t stream);
 int jpegx_entropy_total(const void *d_workspace, unsigned long long *h_total, jpegx_stream_t stream);
@@ -310,6 +313,9 @@ int jpegx_host_entropy_encode(const int16_t *h_zz, long long nblocks, uint8_t *h
  * jpegx_entropy_block_sizes (as they are) -> jpegx_entropy_emit_n (enqueue; writes nothing at all when the sizes pass
  * flagged an amplitude beyond 15 bits, util.py:140-149).  d_zz 4-byte, d_workspace 16-byte aligned; nblocks * block_len
  * below 2^31; d_out may start at any byte.  A workspace may be reused from call to call without clearing.        */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_entropy_total, _block_sizes and _emit_n read what the last jpegx_entropy_sizes_n on it left there.
+ * The value does not shrink when a count argument grows. */
 size_t jpegx_entropy_workspace_bytes_n(long long nblocks, int block_len);
 int jpegx_entropy_sizes_n(const int32_t *d_zz, long long nblocks, int block_len, void *d_workspace, jpegx_stream_t stream);
 int jpegx_entropy_emit_n(const int32_t *d_zz, long long nblocks, int block_len, const void *d_workspace, uint8_t *d_out,
@@ -326,6 +332,9 @@ int jpegx_entropy_emit_n(const int32_t *d_zz, long long nblocks, int block_len, 
  * first try's filter dropped), or JPEGX_E_INVALID for a stream that is not a sequence of well-formed blocks of this
  * plane (the sequential host parser names the fault).  After level 1 answers 1 (blocks of one byte each: more
  * candidates than any segment's tables hold) the whole-stream scheme of the host conveniences is what is left. */
+/* Workspace: 256-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_entropy_decode_status reads the verdict of the last jpegx_entropy_decode on it.  The value does
+ * not shrink when a count argument grows. */
 size_t jpegx_entropy_decode_workspace_bytes(size_t nbytes, long long nblocks);
 int jpegx_entropy_decode(const uint8_t *d_bytes, size_t nbytes, long long nblocks, void *d_workspace, int16_t *d_zz,
                          int level, jpegx_stream_t stream);
@@ -344,6 +353,9 @@ int jpegx_entropy_decode_status(const void *d_workspace, jpegx_stream_t stream);
  * stream ends: d_zz's content is then unspecified, nothing outside d_zz and the workspace has been written).  There are
  * no levels.  A stream whose zero padding behind an end marker was damaged is refused here while the host parser,
  * which skips the padding unread, takes it.                                                                        */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_entropy_decode_status_n reads the verdict of the last jpegx_entropy_decode_n on it.  The value
+ * does not shrink when a count argument grows. */
 size_t jpegx_entropy_decode_workspace_bytes_n(size_t nbytes, long long nblocks, int block_len);
 int jpegx_entropy_decode_n(const uint8_t *d_bytes, size_t nbytes, long long nblocks, int block_len, void *d_workspace,
                            int32_t *d_zz, jpegx_stream_t stream);
@@ -365,6 +377,9 @@ int jpegx_entropy_decode_status_n(const void *d_workspace, jpegx_stream_t stream
  * rounded up to 188 + 64 bytes -- several times what pictures need.  The small-footprint road: compress with d_out ==
  * NULL (sizes only), jpegx_batch_compress_status for the total, jpegx_batch_emit into a buffer of exactly that size
  * (+ 16 zero bytes behind it if jpegx_batch_decompress is to read it from there).                                   */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_batch_compress_status and jpegx_batch_emit read what the last jpegx_batch_compress on the same
+ * workspace, with the same arguments, left there.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_workspace_bytes(int nplanes, int H, int W);
 size_t jpegx_batch_max_bytes(int nplanes, int H, int W);
 /* enqueue only: forward (sizing its blocks) -> scan -> plane index -> emit.  elem_size 4: fp32 planes, bs must be 1, any
@@ -402,6 +417,8 @@ int jpegx_batch_emit(void *d_workspace, int nplanes, int H, int W, uint8_t *d_ou
  * What is verified: offsets that do not decrease, and that every group's bytes hold exactly its planes' (H/8)(W/8)
  * well-formed blocks each -- else JPEGX_E_INVALID with the group's first and last plane in the message; planes of
  * earlier groups have been written by then.                                                                         */
+/* Workspace: 256-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_workspace_bytes(size_t nbytes, int nplanes, int H, int W);
 int jpegx_batch_decompress(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int H, int W,
                            int bs, int mode, double param, unsigned flags, void *d_workspace, void *d_out,
@@ -487,6 +504,10 @@ int jpegx_inflate_crop_stacked_u8(const uint8_t *d_planes, int nplanes, int H, p
  * one group + jpegx_entropy_workspace_bytes_n + the index; jpegx_batch_max_bytes_n is the worst case of the coded stream,
  * (23 N^2 + 15) / 8 bytes per block + 64.  The small-footprint road is that of the 8x8 entries: compress with d_out ==
  * NULL (sizes only), _status_n for the total, _emit_n into exactly that many bytes.                                    */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_batch_compress_status_n and jpegx_batch_emit_n read what the last jpegx_batch_compress_n (or
+ * _compress_pictures_n) on the same workspace, with the same arguments, left there.  The value does not shrink
+ * when a count argument grows. */
 size_t jpegx_batch_workspace_bytes_n(int nplanes, int rows, int cols, int bs, int N, int group_planes);
 size_t jpegx_batch_max_bytes_n(int nplanes, int rows, int cols, int bs, int N);
 /* enqueue only (the first call for a size N on a device uploads that size's tables, as jpegx_forward_fused_n does): per
@@ -524,6 +545,8 @@ int jpegx_batch_groups_n(const unsigned long long *h_plane_offsets, int nplanes,
  * A divisor that is no integer is taken as jpegx_host_decompress_band_n takes it.  d_bytes needs no alignment and no
  * slack behind it.  The workspace (16-byte aligned) is 5 bytes per sample of one group + 13 bytes per stream byte of the
  * longest group.                                                                                                        */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_workspace_bytes_n(size_t nbytes, int nplanes, int rows, int cols, int bs, int N, int group_planes);
 int jpegx_batch_decompress_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int nplanes, int rows, int cols,
                              int bs, int N, int mode, double param, int group_planes, void *d_workspace, uint8_t *d_out,
@@ -612,6 +635,8 @@ int jpegx_batch_groups_pictures_n(const unsigned long long *h_plane_offsets, int
  * and last PICTURE; earlier groups have been written.  Refused before any device work: what jpegx_batch_decompress_n
  * refuses there.  The workspace differs from the band entry's in its staging area, which holds a lone picture's worst case
  * (nbands times a plane's).                                                                                             */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_pictures_workspace_bytes_n(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs,
                                                          int N, int group_planes);
 int jpegx_batch_decompress_pictures_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures,
@@ -649,6 +674,8 @@ int jpegx_probe_sizes_n(const double *d_planes, int nplanes, int H, int W, ptrdi
  * read d_totals after synchronising the stream.  d_pixels is never written.  The workspace (16-byte aligned) is ONE group
  * of float64 planes: up256(min(group_planes, nbands * npictures) * H * W * 8) bytes with H, W from jpegx_band_shape_n and
  * up256 rounding up to 256; jpegx_batch_probe_pictures_workspace_bytes_n returns 0 for a shape the entry refuses.        */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_pictures_workspace_bytes_n(int npictures, int nbands, int rows, int cols, int bs, int N,
                                                     int group_planes);
 int jpegx_batch_probe_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
@@ -689,6 +716,8 @@ int jpegx_band_moments_packed_stacked_n(const uint8_t *d_pixels, int npictures, 
 int jpegx_probe_distortion_n(const double *d_planes, const unsigned long long *d_moments, int nplanes, int H, int W,
                              ptrdiff_t pitch, ptrdiff_t mpitch, int N, int bs, int rows, int cols, int mode,
                              const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_distortion_pictures_workspace_bytes_n(int npictures, int nbands, int rows, int cols, int bs, int N,
                                                                int group_planes);
 int jpegx_batch_probe_distortion_pictures_n(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
@@ -727,10 +756,14 @@ int jpegx_probe_sizes_8(const double *d_planes, int nplanes, int H, int W, ptrdi
 int jpegx_probe_distortion_8(const double *d_planes, const unsigned long long *d_moments, int nplanes, int H, int W,
                              ptrdiff_t pitch, ptrdiff_t mpitch, int bs, int rows, int cols, int mode, const double *h_params,
                              int K, unsigned long long *d_totals, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes);
 int jpegx_batch_probe_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
                                int colour, int bs, int mode, const double *h_params, int K, int group_planes,
                                void *d_workspace, unsigned long long *d_totals, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_distortion_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs,
                                                              int group_planes);
 int jpegx_batch_probe_distortion_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols,
@@ -827,6 +860,10 @@ int jpegx_picture_set_pixels_u8(const uint8_t *d_strip, const void *h_table, con
  * the scatter.  A refused group writes nothing and is named by its first and last picture; earlier groups have been
  * written.  Refused before any device work: what jpegx_batch_groups_set_n refuses, and a group whose bytes cannot be its
  * blocks.  Its workspace: jpegx_batch_decompress_set_workspace_bytes_n(nbytes of the whole stream, ...).                 */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_batch_compress_status_set_n and jpegx_batch_emit_set_n read what the last
+ * jpegx_batch_compress_picture_set_n on the same workspace, with the same arguments, left there.  The value does
+ * not shrink when a count argument grows. */
 size_t jpegx_batch_set_workspace_bytes_n(const void *h_table, long long group_samples);
 size_t jpegx_batch_set_max_bytes_n(const void *h_table);
 int jpegx_batch_compress_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
@@ -838,6 +875,8 @@ int jpegx_batch_emit_set_n(void *d_workspace, const void *h_table, const void *d
                            size_t out_cap, jpegx_stream_t stream);
 int jpegx_batch_groups_set_n(const unsigned long long *h_plane_offsets, const void *h_table, long long group_samples,
                              int *h_group_first, int *ngroups);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_set_workspace_bytes_n(size_t nbytes, const void *h_table, long long group_samples);
 int jpegx_batch_decompress_picture_set_n(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table,
                                          const void *d_table, int mode, double param, int colour, long long group_samples,
@@ -858,6 +897,8 @@ int jpegx_batch_decompress_picture_set_n(const uint8_t *d_bytes, const unsigned 
  * the table and group_samples.  Refused as the compress entry refuses, plus the candidates and d_totals' alignment.       */
 int jpegx_probe_sizes_set_n(const double *d_strip, const void *h_table, const void *d_table, int p0, int k, int mode,
                             const double *h_params, int K, unsigned long long *d_totals, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_picture_set_workspace_bytes_n(const void *h_table, long long group_samples);
 int jpegx_batch_probe_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
                                     const double *h_params, int K, long long group_samples, void *d_workspace,
@@ -884,6 +925,8 @@ int jpegx_picture_set_moments_n(const uint8_t *d_pixels, const void *h_table, co
 int jpegx_probe_distortion_set_n(const double *d_strip, const unsigned long long *d_moments, const void *h_table,
                                  const void *d_table, int p0, int k, int mode, const double *h_params, int K,
                                  unsigned long long *d_totals, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_probe_distortion_picture_set_workspace_bytes_n(const void *h_table, long long group_samples);
 int jpegx_batch_probe_distortion_picture_set_n(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour,
                                                int mode, const double *h_params, int K, long long group_samples,
@@ -921,6 +964,9 @@ int jpegx_picture_planes_stacked_u8(const uint8_t *d_pixels, int npictures, int 
  * finite (JPEGX_E_INVALID) or below 0.5 (JPEGX_E_UNSUPPORTED, on both roads), more than 2^31 - 64 blocks, more than
  * 2^31 - 1 rows in the stack; and rows * cols or a float64 group's samples beyond 2^31 - 1.  The workspace function
  * returns 0 for a shape that is refused.                                                                              */
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_batch_compress_status and jpegx_batch_emit read what the last jpegx_batch_compress_pictures on the
+ * same workspace, with the same arguments, left there.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_pictures_workspace_bytes(int npictures, int nbands, int rows, int cols, int bs, int group_planes);
 int jpegx_batch_compress_pictures(const uint8_t *d_pixels, int npictures, int nbands, int rows, int cols, ptrdiff_t pitch,
                                   int colour, int bs, int mode, double param, int group_planes, void *d_workspace,
@@ -929,6 +975,8 @@ int jpegx_batch_compress_pictures(const uint8_t *d_pixels, int npictures, int nb
  * [nplanes * H][W] inside the workspace (256-byte aligned), and only after it has answered JPEGX_OK
  * jpegx_inflate_crop_pack_stacked_u8 into d_out [npictures * rows][out_pitch], out_pitch >= cols * nbands: the
  * replication, both crops, the np.dstack and, with colour = 1, Pillow's RGB.  A refused stream writes NOTHING to d_out.   */
+/* Workspace: 256-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_pictures_workspace_bytes(size_t nbytes, int npictures, int nbands, int rows, int cols, int bs);
 int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, int npictures,
                                     int nbands, int rows, int cols, int bs, int mode, double param, int colour,
@@ -966,6 +1014,10 @@ int jpegx_batch_decompress_pictures(const uint8_t *d_bytes, const unsigned long 
  * and a group whose bytes cannot be its blocks (1 .. 185 bytes each).                                                     */
 int jpegx_picture_set_blocks_u8(const uint8_t *d_pixels, const void *h_table, const void *d_table, int p0, int k, int colour,
                                 uint8_t *d_strip, jpegx_stream_t stream);
+/* Workspace: 16-byte aligned at least; the declared size is enough whatever the workspace held
+ * before; jpegx_batch_compress_status_set and jpegx_batch_emit_set read what the last
+ * jpegx_batch_compress_picture_set on the same workspace, with the same arguments, left there.  The value does not
+ * shrink when a count argument grows. */
 size_t jpegx_batch_set_workspace_bytes(const void *h_table, long long group_samples);
 size_t jpegx_batch_set_max_bytes(const void *h_table);
 int jpegx_batch_compress_picture_set(const uint8_t *d_pixels, const void *h_table, const void *d_table, int colour, int mode,
@@ -977,6 +1029,8 @@ int jpegx_batch_emit_set(void *d_workspace, const void *h_table, const void *d_t
                          size_t out_cap, jpegx_stream_t stream);
 int jpegx_batch_groups_set(const unsigned long long *h_plane_offsets, const void *h_table, long long group_samples,
                            int *h_group_first, int *ngroups);
+/* Workspace: 256-byte aligned at least; the declared size is enough whatever the workspace held
+ * before.  The value does not shrink when a count argument grows. */
 size_t jpegx_batch_decompress_set_workspace_bytes(size_t nbytes, const void *h_table, long long group_samples);
 int jpegx_batch_decompress_picture_set(const uint8_t *d_bytes, const unsigned long long *h_plane_offsets, const void *h_table,
                                        const void *d_table, int mode, double param, int colour, long long group_samples,
